@@ -37,6 +37,17 @@ structure, exact point tests per query) are measured by an instrumented replay o
 figure (algorithmic bytes of the K timed bases / timed seconds / HBM peak), which does not depend on how many bases are in
 flight; rocprofv3 --pmc passes over an inner run of the same W + K bases give the HBM-side traffic, the L2 hit rate and the
 VALU issue utilisation of k_verify, and `binding` names the resource that is closest to its roof.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what `value` needs: it sets up, runs the W warm-up steps, times
+ONE region of exactly K steps and prints the line; every other leg above (the repeats of the timed region, the parity gate, the
+stage pass, the full-count region, the instrumented replays, time-to-register, the rocprofv3 passes, the HBM-bound point and the
+final-apply rows, the one-base-in-flight re-run, the `extra` sample, the CPU baselines, --ttr-configs) runs only with `--full`,
+and the line's fields of a leg that did not run are null.  A registration's trial loop stops after ~590 bases of this workload;
+longer runs go on in fresh registrations of the same pair, each set up and warmed up with the clock stopped, so K is always
+the number of bases timed.  `--dump-outputs DIR` writes what the timed path handed its caller after
+the last timed step (the matcher's best 4x4, LCP, inlier count, winning base and quad, the registration's global 4x4 and the
+candidates verified in the timed steps) as DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -64,6 +75,23 @@ from benchlib.scale import extra_sample_finish, extra_sample_start, scale_golden
 _PHASES = []
 
 
+def _bases_left(m):
+    """Bases the engine's trial loop still runs for this registration: Perform_N_steps breaks after trial i once
+    i / number_of_trials >= 0.99 (float) or i > number_of_trials."""
+    info = m.info()
+    nt, i = info.number_of_trials, info.current_trial
+
+    def stops_after(t):
+        return float(np.float32(t) / np.float32(nt)) >= 0.99 or t > nt
+
+    if i > 0 and stops_after(i - 1):            # the registration is spent
+        return 0
+    last = i
+    while not stops_after(last):
+        last += 1
+    return last - i + 1
+
+
 def _lap(name, _t=[None]):
     """Wall time of the phases of a run (config.phase_seconds): where the minutes of the default command go."""
     now = time.perf_counter()
@@ -78,7 +106,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions (same bases, fresh matcher): value = median")
+    ap.add_argument("--full", action="store_true", help="also run every leg besides the timed region (parity gate, repeats, byte model, "
+                    "profiling passes, CPU baselines, `extra`, ...); a plain run times one region of --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions (same bases, fresh matcher): value = median "
+                    "(default: 5 with --full, 1 otherwise)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the 1-core cpu_baseline sample (0 = skip)")
     ap.add_argument("--no-time-to-register", dest="time_to_register", action="store_false", default=True)
     ap.add_argument("--no-parity", dest="parity", action="store_false", default=True)
@@ -109,6 +142,13 @@ def main():
     ap.add_argument("--no-extra", dest="extra", action="store_false", default=True,
                     help="skip the `extra` object: the same clouds at SURVEY 8d's GPU-scale sample (n = 20 000), two bases, in a process of its own")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        # a plain run: the timed region and the line, nothing that only the other fields need
+        args.cpu_seconds = 0.0; args.time_to_register = False; args.parity = False; args.pmc = False; args.hbm_point = False
+        args.full_count_mode = False; args.instrumented = False; args.stage_pass = False; args.exclusive = False; args.extra = False
+        args.ttr_configs = ""
 
     scale_mode = args.sample > 5000          # the "GPU-scale" sample: bases of ~10^9 quads, seconds per base
     if scale_mode:
@@ -229,11 +269,31 @@ def main():
         sh.run_windows(warmup)
         m.profile_enable(1 if (stage_events or scale_mode) else 2, False)      # (a base of the 20 000-point sample takes seconds: events are free)
         m.profile_get(reset=True)
-        sync()
-        t0 = time.perf_counter()
-        cand = sh.run_windows(steps)            # pipelined: host base selection of step t+1 overlaps the GPU pass of step t
-        sync()
-        dt = time.perf_counter() - t0
+        if world > 1:
+            sync()
+            t0 = time.perf_counter()
+            cand = sh.run_windows(steps)        # pipelined: host base selection of step t+1 overlaps the GPU pass of step t
+            sync()
+            dt = time.perf_counter() - t0
+        else:
+            # a registration's trial loop stops at 99 % of its trials (as PerformNSteps does), ~590 bases here: beyond that the
+            # K steps go on in fresh registrations of the same pair on the same matcher (its RNG stream continues), each set up and
+            # warmed up like the first one with the clock stopped -- inputs resident, as for the first
+            cand, dt, left = 0, 0.0, steps
+            while True:
+                k = min(left, _bases_left(m))
+                if k <= 0:
+                    raise SystemExit("bench.py: --warmup %d leaves no base of the registration's %d trials to time" % (warmup, m.info().number_of_trials))
+                sync()
+                t0 = time.perf_counter()
+                cand += sh.run_windows(k)       # pipelined: host base selection of step t+1 overlaps the GPU pass of step t
+                sync()
+                dt += time.perf_counter() - t0
+                left -= k
+                if left == 0:
+                    break
+                m.init_full(P, Q)
+                sh.run_windows(warmup)
         prof = m.profile_get(reset=True)
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         tc = torch.tensor([cand], dtype=torch.int64, device=dev)
@@ -273,6 +333,15 @@ def main():
     final_info = info                           # state after the last repeat's windows (N > 1: compared across ranks below)
     chunk_stats = m.chunk_stats()
     lane_growths = m.capacity_growths()
+    if rank == 0 and args.dump_outputs:
+        # what the timed path handed its caller after its last step (the last repeat's matcher), see the module docstring
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = {"transform": np.array(info.transform, np.float32).reshape(4, 4), "global_transform": m.global_transform().astype(np.float32),
+                  "best_lcp": np.array([info.best_lcp], np.float32), "best_count": np.array([info.best_count], np.float64),
+                  "base": np.array(info.base, np.float64), "congruent": np.array(info.congruent, np.float64),
+                  "candidates_timed": np.array([runs[-1][2]], np.float64)}
+        for name, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     # which code produced this line: commit + source digest stamped at build time, the k_verify instantiation the loop launches
     import hashlib
     from super4pcs_amd import build as _build

@@ -10,26 +10,17 @@ import pytest
 from tests import helpers as H
 
 GOLD = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "oracle_golden.json")))
-REF_ASSETS = "/root/reference/assets"
 
 
 def digest(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
 
 
-def _load_obj(path):
-    v = []
-    with open(path) as f:
-        for line in f:
-            if line.startswith("v "):
-                v.append([float(x) for x in line.split()[1:4]])
-    return np.array(v, np.float32)
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_ASSETS), reason="reference assets not present on this box")
 def test_sampler_known_answer_on_reference_assets(oracle_mod):
-    """doc/Usage.md:80 publishes 5281 kd-tree points for hippo1 @ delta=0.01 (scripts/run-example.sh:68)."""
-    h1, h2 = _load_obj(REF_ASSETS + "/hippo1.obj"), _load_obj(REF_ASSETS + "/hippo2.obj")
+    """doc/Usage.md:80 publishes 5281 kd-tree points for hippo1 @ delta=0.01 (scripts/run-example.sh:68).  The vertices of the
+    two asset files are stored in tests/golden/hippo_vertices.npz (tests/golden/make_hippo_vertices.py)."""
+    from tests.golden import make_hippo_vertices
+    h1, h2 = make_hippo_vertices.load()
     assert (len(h1), len(h2)) == (30519, 21935)
     assert len(oracle_mod.sample(h1, 0.01)) == 5281
     assert [len(oracle_mod.sample(h1, 0.01)), len(oracle_mod.sample(h2, 0.01))] == GOLD["hippo_sampler"]["delta_0.01"]

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 export S4P_WAIT_TIMEOUT_S=600
 O=gpurun_out/r05_final; mkdir -p $O $O/bench_final
-timeout -s KILL 1100 python bench.py --profile-dir $O/bench_final --ttr-configs 1,3,4s > $O/bench_final.json 2> $O/bench_final.err
+timeout -s KILL 1100 python bench.py --full --profile-dir $O/bench_final --ttr-configs 1,3,4s > $O/bench_final.json 2> $O/bench_final.err
 echo "bench rc=$?"
 python - <<'PY'
 import json

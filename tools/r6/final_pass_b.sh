@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 export S4P_WAIT_TIMEOUT_S=600
 O=gpurun_out/r06_final; mkdir -p $O $O/bench_final
 cp super4pcs_amd/lib/BUILD_INFO.json $O/BUILD_INFO_b.json
-timeout -s KILL 1100 python bench.py --profile-dir $O/bench_final --ttr-configs 1,3,4s > $O/bench_final.json 2> $O/bench_final.err
+timeout -s KILL 1100 python bench.py --full --profile-dir $O/bench_final --ttr-configs 1,3,4s > $O/bench_final.json 2> $O/bench_final.err
 echo "bench rc=$?" > $O/log_b.txt
 g++ -O2 -std=c++17 -Iinclude tests/facade_app/timing.cpp -Lsuper4pcs_amd/lib -lsuper4pcs_amd -Wl,-rpath,$GRAFT_REPO_ROOT/super4pcs_amd/lib -o /tmp/facade_timing
 for i in 1 2 3; do GPU_MAX_HW_QUEUES=8 timeout -s KILL 100 /tmp/facade_timing 1000000 0.004 2000 0.5 >> $O/facade_timing.json 2>> $O/facade_timing.err; done

@@ -10,7 +10,7 @@ timeout -s KILL 500 python tools/prof_kernels.py $O/lanes1 --lanes 1 --steps 60 
 echo "kern rc=$?" > $O/log_c.txt; tail -2 $O/lanes1/log.txt >> $O/log_c.txt
 BASES=12 timeout -s KILL 300 python tools/r6/wave_prof.py > $O/wave_profile.txt 2>&1
 echo "wave_prof rc=$?" >> $O/log_c.txt; grep "lean sweep" $O/wave_profile.txt | tail -3 >> $O/log_c.txt
-S4P_BENCH_ONE_GPU=1 timeout -s KILL 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --cpu-seconds 0 --no-pmc --no-hbm-point --no-time-to-register --no-exclusive --no-instrumented --no-full-count-mode --no-stage-pass --no-extra > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
+S4P_BENCH_ONE_GPU=1 timeout -s KILL 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --steps 20 --warmup 5 --cpu-seconds 0 --no-pmc --no-hbm-point --no-time-to-register --no-exclusive --no-instrumented --no-full-count-mode --no-stage-pass --no-extra > $O/bench_2ranks_one_gpu.json 2> $O/bench_2ranks_one_gpu.err
 echo "2 ranks rc=$?" >> $O/log_c.txt
 python - <<'PY' >> gpurun_out/r06_final/log_c.txt
 import json

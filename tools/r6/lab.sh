@@ -36,9 +36,9 @@ for what in "$@"; do
     trace)
       timeout -s KILL 300 python tools/prof_kernels.py $O --lanes 1 --steps 60 --passes trace > $O/trace.log 2>&1; echo "trace rc=$?" >> $O/summary.txt; tail -3 $O/trace.log >> $O/summary.txt ;;
     bench20)
-      timeout -s KILL 400 python bench.py --gpus 1 --steps 20 --warmup 5 $BQ > $O/bench20.json 2> $O/bench20.err; echo "bench20 rc=$?" >> $O/summary.txt ;;
+      timeout -s KILL 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 $BQ > $O/bench20.json 2> $O/bench20.err; echo "bench20 rc=$?" >> $O/summary.txt ;;
     bench200)
-      timeout -s KILL 400 python bench.py --gpus 1 $BQ > $O/bench200.json 2> $O/bench200.err; echo "bench200 rc=$?" >> $O/summary.txt ;;
+      timeout -s KILL 400 python bench.py --full --gpus 1 $BQ > $O/bench200.json 2> $O/bench200.err; echo "bench200 rc=$?" >> $O/summary.txt ;;
     bench200np)
       timeout -s KILL 400 python bench.py --gpus 1 --no-parity --repeats 3 $BQ > $O/bench200np.json 2> $O/bench200np.err; echo "bench200np rc=$?" >> $O/summary.txt ;;
   esac
