@@ -4,12 +4,15 @@
 // options, 255 (-1) unreadable input.
 //   Super4PCS -i P.obj Q.obj [-o overlap] [-d delta] [-n samples] [-t seconds] [-a normal_deg] [-c colour]
 //             [-r registered_geometry] [-m polyworks_matrix] [--sampled1 file] [--sampled2 file]
+//             [--icp iterations] [--icp-dist max_distance]
+// --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written.
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
 #include <string>
 #include <vector>
 
+#include "super4pcs/algorithms/icp.h"
 #include "super4pcs/algorithms/super4pcs.h"
 #include "super4pcs/io/io.h"
 #include "super4pcs/utils/geometry.h"
@@ -79,6 +82,14 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       if (opt.sampled[k].empty()) continue;
       log.Log<Utils::Verbose>("Exporting Sampled cloud ", k + 1, " to ", opt.sampled[k].c_str(), " ...");
       save_points(io, opt.sampled[k], *sampled[k]);
+    }
+    if (opt.icp_iterations > 0) {
+      ICPOptions icp;
+      icp.max_iterations = opt.icp_iterations;
+      icp.max_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
+      ICPResult res;
+      RefineICP(P.points, &Q.points, mat, icp, &res);
+      log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);
     }
   } catch (const std::exception& e) {
     log.Log<Utils::ErrorReport>("[Error]: ", e.what());

@@ -21,6 +21,9 @@ struct Options {
   double overlap = 0.2, delta = 5.0, colour = -1, normal_deg = -1;
   int samples = 200, seconds = 10;
   bool legacy_4pcs = false;                                  // -x
+  int icp_iterations = 0;                                    // --icp  ICP refinement after the registration (0: off)
+  double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
+  bool bad_value = false;                                    // a flag's value does not parse
 };
 
 enum class Parse { Run, Help, Bad };
@@ -46,6 +49,16 @@ inline const Flag* flag_table(size_t* n) {
       {"-x", 0, [](Options& o, char**) { o.legacy_4pcs = true; }},
       {"--sampled1", 1, [](Options& o, char** v) { o.sampled[0] = v[0]; }},
       {"--sampled2", 1, [](Options& o, char** v) { o.sampled[1] = v[0]; }},
+      {"--icp", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long n = std::strtol(v[0], &end, 10);
+         if (end == v[0] || *end != '\0' || n < 0 || n > 100000) o.bad_value = true; else o.icp_iterations = int(n);
+       }},
+      {"--icp-dist", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double d = std::strtod(v[0], &end);
+         if (end == v[0] || *end != '\0' || !(d > 0)) o.bad_value = true; else o.icp_distance = d;
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -67,6 +80,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
     hit->store(o, argv + i + 1);
     i += hit->values;
   }
+  if (o.bad_value) return Parse::Bad;
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -81,6 +95,7 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ -r result_file_name (%s) ]\n\t[ -m output matrix file (%s) ]\n", o.registered.c_str(), o.matrix.c_str());
   std::fprintf(stderr, "\t[ -x (legacy 4PCS: not available in this build) ]\n");
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
+  std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -1,0 +1,94 @@
+// RefineICP: point-to-point ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
+// documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
+// of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h).
+// Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
+//
+//   MatchSuper4PCS matcher(options, logger);
+//   matcher.ComputeTransformation(P, &Q, mat);           // Q is moved by mat
+//   ICPOptions icp; icp.max_distance = 4 * options.delta;
+//   RefineICP(P, &Q, mat, icp);                           // Q moved by the refinement too; mat <- dT * mat
+#ifndef S4P_FACADE_ICP_H_
+#define S4P_FACADE_ICP_H_
+
+#include <cstdint>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "s4p_icp.h"
+#include "super4pcs/algorithms/match4pcsBase.h"
+
+namespace GlobalRegistration {
+
+struct ICPOptions {
+  int max_iterations = 30;
+  double max_distance = -1.0;       // required (> 0); 4 * delta is the usual choice after a registration at delta
+  double rel_tol = 1e-6;
+  int min_correspondences = 3;
+  int device = 0;
+};
+
+struct ICPResult {
+  int iterations = 0;
+  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / S4P_ICP_CONVERGED / S4P_ICP_TOO_FEW
+  int64_t n_corr = 0;
+  double rmse = 0.0;
+  double fitness = 0.0;             // n_corr / |Q|
+  std::vector<double> rmse_history;
+};
+
+// Q as it stands after ComputeTransformation (already moved).  Finds dT, moves Q in place (in k_apply's rounding order)
+// and sets transformation <- dT * transformation.  Returns the fitness of the refined pose.  Throws std::runtime_error
+// when there is no device (no CPU fallback) or an argument is invalid.
+inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, Match4PCSBase::MatrixRef transformation,
+                       const ICPOptions& options, ICPResult* result = nullptr) {
+  if (Q == nullptr || P.empty() || Q->empty()) throw std::invalid_argument("RefineICP: empty cloud");
+  struct Handle {
+    s4p_icp_ctx* h = nullptr;
+    ~Handle() { s4p_icp_destroy(h); }
+    void check(int32_t rc) const {
+      if (rc != S4P_ICP_OK) throw std::runtime_error(std::string("RefineICP (MI355X): ") + s4p_icp_last_error(h));
+    }
+  } H;
+  if (s4p_icp_create(options.device, &H.h) != S4P_ICP_OK)
+    throw std::runtime_error(std::string("RefineICP (MI355X): ") + s4p_icp_last_error(nullptr));
+  auto soa = [](const std::vector<Point3D>& pts, std::vector<float> (&c)[3]) {
+    for (int k = 0; k < 3; ++k) c[k].resize(pts.size());
+    for (size_t i = 0; i < pts.size(); ++i) { c[0][i] = pts[i].x(); c[1][i] = pts[i].y(); c[2][i] = pts[i].z(); }
+  };
+  std::vector<float> p[3], q[3];
+  soa(P, p);
+  soa(*Q, q);
+  H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
+  H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
+  s4p_icp_params prm;
+  s4p_icp_default_params(&prm);
+  prm.max_iterations = options.max_iterations;
+  prm.min_correspondences = options.min_correspondences;
+  prm.rel_tol = options.rel_tol;
+  double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  s4p_icp_result r;
+  H.check(s4p_icp_refine(H.h, &prm, dT, &r));
+  H.check(s4p_icp_apply(H.h, dT, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
+  for (size_t i = 0; i < Q->size(); ++i) { (*Q)[i].x() = q[0][i]; (*Q)[i].y() = q[1][i]; (*Q)[i].z() = q[2][i]; }
+  double M[16];
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b) {
+      double v = 0.0;
+      for (int k = 0; k < 4; ++k) v += dT[4 * a + k] * double(transformation(k, b));
+      M[4 * a + b] = v;
+    }
+  using Scalar = Match4PCSBase::Scalar;
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b) transformation(a, b) = Scalar(M[4 * a + b]);
+  if (result) {
+    result->iterations = r.iterations; result->status = r.status; result->n_corr = r.n_corr;
+    result->rmse = r.rmse; result->fitness = r.fitness;
+    result->rmse_history.assign(r.history_rmse, r.history_rmse + r.history_len);
+  }
+  return float(r.fitness);
+}
+
+}  // namespace GlobalRegistration
+#endif

@@ -105,6 +105,28 @@ def build_variant(name, defines):
     return _compile(os.path.join(d, "lib%s.so" % name), defines)
 
 
+ICP_SRC = os.path.join(_HERE, "icp_src")
+ICP_LIB = os.path.join(LIBDIR, "libsuper4pcs_icp.so")
+ICP_SOURCES = ["s4p_icp.hip"]
+
+
+def build_icp(force=False, verbose=False):
+    """lib/libsuper4pcs_icp.so: ICP refinement (icp_src/, include/s4p_icp.h), a library of its own so that the main
+    library's sources and kernels stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off)."""
+    deps = [os.path.join(ICP_SRC, f) for f in os.listdir(ICP_SRC)] + [os.path.join(ROOT, "include", "s4p_icp.h")]
+    if not force and os.path.exists(ICP_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(ICP_LIB) for d in deps):
+        return ICP_LIB
+    os.makedirs(LIBDIR, exist_ok=True)
+    cmd = [_hipcc()] + HIPCC_FLAGS + ["-I" + os.path.join(ROOT, "include"), "-I" + ICP_SRC]
+    for s in ICP_SOURCES:
+        cmd += ["-x", "hip", os.path.join(ICP_SRC, s)]
+    cmd += ["-o", ICP_LIB]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return ICP_LIB
+
+
 BINDIR = os.path.join(_HERE, "bin")
 CLI = os.path.join(BINDIR, "Super4PCS")
 CLI_SRC = os.path.join(ROOT, "demos", "Super4PCS", "super4pcs_cli.cc")
@@ -113,18 +135,21 @@ CLI_SRC = os.path.join(ROOT, "demos", "Super4PCS", "super4pcs_cli.cc")
 def build_cli(force=False):
     """The command-line program (demos/Super4PCS) against the facade headers and the library: plain host C++."""
     build()
-    deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB,
+    build_icp(force=force)
+    deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB, ICP_LIB,
+            os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp.h"),
             os.path.join(ROOT, "include", "super4pcs", "io", "io.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "match4pcsBase.h")]
     if not force and os.path.exists(CLI) and all(os.path.getmtime(d) <= os.path.getmtime(CLI) for d in deps):
         return CLI
     os.makedirs(BINDIR, exist_ok=True)
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), CLI_SRC,
-           "-L" + LIBDIR, "-lsuper4pcs_amd", "-Wl,-rpath,$ORIGIN/../lib", "-o", CLI]
+           "-L" + LIBDIR, "-lsuper4pcs_amd", "-lsuper4pcs_icp", "-Wl,-rpath,$ORIGIN/../lib", "-o", CLI]
     subprocess.check_call(cmd)
     return CLI
 
 
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
+    print(build_icp(force="--force" in sys.argv, verbose=True))
     print(build_cli(force="--force" in sys.argv))

@@ -1,0 +1,239 @@
+"""ctypes binding of include/s4p_icp.h (libsuper4pcs_icp.so): point-to-point ICP refinement on the full-resolution clouds.
+
+    from super4pcs_amd import icp
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
+
+Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
+through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
+ICPError with code -2.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "lib", "libsuper4pcs_icp.so")
+
+NSUMS = 17
+HISTORY = 64
+MAX_ITERATIONS, CONVERGED, TOO_FEW = 0, 1, 2
+STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged", TOO_FEW: "too few correspondences"}
+ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE"}
+
+SYMBOLS = [
+    "s4p_icp_default_params", "s4p_icp_create", "s4p_icp_destroy", "s4p_icp_last_error", "s4p_icp_set_target",
+    "s4p_icp_set_source", "s4p_icp_set_target_device", "s4p_icp_set_source_device", "s4p_icp_frame",
+    "s4p_icp_correspondences", "s4p_icp_sums", "s4p_icp_solve", "s4p_icp_refine", "s4p_icp_apply",
+]
+
+
+class ICPError(RuntimeError):
+    def __init__(self, code, msg):
+        super().__init__("s4p_icp error %s (%d): %s" % (ERR_NAMES.get(code, "?"), code, msg))
+        self.code = code
+
+
+class Params(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("min_correspondences", C.c_int32), ("rel_tol", C.c_double),
+                ("order_source", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Result(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("status", C.c_int32), ("n_corr", C.c_int64), ("rmse", C.c_double),
+                ("fitness", C.c_double), ("history_len", C.c_int32), ("reserved", C.c_int32),
+                ("history_rmse", C.c_double * HISTORY), ("history_n", C.c_int64 * HISTORY)]
+
+    def as_dict(self):
+        k = self.history_len
+        return {"iterations": self.iterations, "status": STATUS_NAMES[self.status], "n_corr": self.n_corr, "rmse": self.rmse,
+                "fitness": self.fitness, "history_rmse": list(self.history_rmse[:k]), "history_n": list(self.history_n[:k])}
+
+
+_LIB = None
+
+
+def load_library():
+    global _LIB
+    if _LIB is not None:
+        return _LIB
+    if not os.path.exists(LIB_PATH):
+        raise ICPError(-7, "libsuper4pcs_icp.so not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
+    L = C.CDLL(LIB_PATH)
+    fp, dp, ip, vp = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
+    L.s4p_icp_default_params.restype = None
+    L.s4p_icp_default_params.argtypes = [C.POINTER(Params)]
+    L.s4p_icp_create.restype = C.c_int32
+    L.s4p_icp_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.s4p_icp_destroy.restype = None
+    L.s4p_icp_destroy.argtypes = [vp]
+    L.s4p_icp_last_error.restype = C.c_char_p
+    L.s4p_icp_last_error.argtypes = [vp]
+    for name in ("s4p_icp_set_target", "s4p_icp_set_target_device"):
+        getattr(L, name).restype = C.c_int32
+        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float]
+    for name in ("s4p_icp_set_source", "s4p_icp_set_source_device"):
+        getattr(L, name).restype = C.c_int32
+        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.s4p_icp_frame.restype = C.c_int32
+    L.s4p_icp_frame.argtypes = [vp, fp]
+    L.s4p_icp_correspondences.restype = C.c_int32
+    L.s4p_icp_correspondences.argtypes = [vp, fp, ip, fp]
+    L.s4p_icp_sums.restype = C.c_int32
+    L.s4p_icp_sums.argtypes = [vp, fp, dp]
+    L.s4p_icp_solve.restype = C.c_int32
+    L.s4p_icp_solve.argtypes = [dp, dp]
+    L.s4p_icp_refine.restype = C.c_int32
+    L.s4p_icp_refine.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
+    L.s4p_icp_apply.restype = C.c_int32
+    L.s4p_icp_apply.argtypes = [vp, dp, fp, fp, fp, C.c_int64]
+    _LIB = L
+    return L
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def solve(sums):
+    """Horn's closed form on the 17 sums (host only, no device): the 4x4 dT mapping q^ onto p'."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, np.float64).reshape(NSUMS)
+    out = np.empty(16, np.float64)
+    rc = L.s4p_icp_solve(_dp(s), _dp(out))
+    if rc != 0:
+        raise ICPError(rc, "solve: n < 1")
+    return out.reshape(4, 4)
+
+
+def compose(A, B):
+    """A @ B for 4x4 float64 in the facade's order (sum over k = 0..3 left to right, no fused multiply-add), so that a
+    matrix composed here equals the one RefineICP / the command line composes."""
+    A = np.asarray(A, np.float64); B = np.asarray(B, np.float64)
+    out = np.empty((4, 4), np.float64)
+    for a in range(4):
+        for b in range(4):
+            v = 0.0
+            for k in range(4):
+                v += float(A[a, k]) * float(B[k, b])
+            out[a, b] = v
+    return out
+
+
+def _is_torch(t):
+    return type(t).__module__.startswith("torch")
+
+
+class ICP:
+    """One s4p_icp context (one GPU)."""
+
+    def __init__(self, device=0):
+        self.L = load_library()
+        self.device = device
+        h = C.c_void_p()
+        rc = self.L.s4p_icp_create(device, C.byref(h))
+        if rc != 0:
+            raise ICPError(rc, self.L.s4p_icp_last_error(None).decode())
+        self.h = h
+        self.n_q = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.s4p_icp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise ICPError(rc, self.L.s4p_icp_last_error(self.h).decode())
+
+    def _cols(self, X):
+        """(entry-point suffix, three column pointers, n, keep-alive) of a numpy array or a CUDA/HIP torch tensor."""
+        if _is_torch(X):
+            import torch
+            if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == 3):
+                raise ValueError("torch input must be a (N, 3) float32 tensor on the GPU")
+            cols = [X[:, k].contiguous() for k in range(3)]
+            torch.cuda.synchronize(X.device)          # the copies run on torch's stream; the library reads on its own
+            return "_device", [c.data_ptr() for c in cols], int(X.shape[0]), cols
+        X = np.asarray(X)
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError("clouds are (N, 3)")
+        cols = [np.ascontiguousarray(X[:, k], dtype=np.float32) for k in range(3)]
+        return "", [c.ctypes.data for c in cols], int(X.shape[0]), cols
+
+    def set_target(self, P, max_distance):
+        suf, ptr, n, keep = self._cols(P)
+        self._chk(getattr(self.L, "s4p_icp_set_target" + suf)(self.h, ptr[0], ptr[1], ptr[2], n, float(max_distance)))
+        del keep
+
+    def set_source(self, Q):
+        suf, ptr, n, keep = self._cols(Q)
+        self._chk(getattr(self.L, "s4p_icp_set_source" + suf)(self.h, ptr[0], ptr[1], ptr[2], n))
+        self.n_q = n
+        del keep
+
+    def frame(self):
+        c = np.empty(3, np.float32)
+        self._chk(self.L.s4p_icp_frame(self.h, _fp(c)))
+        return c
+
+    @staticmethod
+    def _t32(T):
+        T = np.ascontiguousarray(np.asarray(T).reshape(4, 4), np.float32).reshape(16)
+        return T
+
+    def correspondences(self, T):
+        """(idx int32[n_Q], d2 float32[n_Q]) for a float T in the centred frame; idx -1 where nothing is within d."""
+        T = self._t32(T)
+        idx = np.empty(self.n_q, np.int32); d2 = np.empty(self.n_q, np.float32)
+        self._chk(self.L.s4p_icp_correspondences(self.h, _fp(T), idx.ctypes.data_as(C.POINTER(C.c_int32)), _fp(d2)))
+        return idx, d2
+
+    def sums(self, T):
+        """The 17 double sums for a float T in the centred frame: n, sum q^, sum p', sum q^ p'^T (row-major), sum d2."""
+        T = self._t32(T)
+        out = np.empty(NSUMS, np.float64)
+        self._chk(self.L.s4p_icp_sums(self.h, _fp(T), _dp(out)))
+        return out
+
+    def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True):
+        """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity)."""
+        T = np.ascontiguousarray(np.eye(4) if T0 is None else np.asarray(T0, np.float64).reshape(4, 4), np.float64).reshape(16).copy()
+        p = Params()
+        self.L.s4p_icp_default_params(C.byref(p))
+        p.max_iterations, p.rel_tol, p.min_correspondences = int(max_iterations), float(rel_tol), int(min_correspondences)
+        p.order_source = int(bool(order_source))
+        r = Result()
+        self._chk(self.L.s4p_icp_refine(self.h, C.byref(p), _dp(T), C.byref(r)))
+        return T.reshape(4, 4), r
+
+    def apply(self, T, X):
+        """float32 (N, 3): float(T) applied to X on the device in k_apply's rounding order."""
+        T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        X = np.asarray(X, np.float32)
+        cols = [np.ascontiguousarray(X[:, k]).copy() for k in range(3)]
+        self._chk(self.L.s4p_icp_apply(self.h, _dp(T), _fp(cols[0]), _fp(cols[1]), _fp(cols[2]), X.shape[0]))
+        return np.stack(cols, axis=1)
+
+
+def refine(P, Q, T0=None, max_distance=None, device=0, **params):
+    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required."""
+    if max_distance is None:
+        raise ValueError("max_distance is required (4 * delta after a registration at delta)")
+    ctx = ICP(device)
+    try:
+        ctx.set_target(P, max_distance)
+        ctx.set_source(Q)
+        return ctx.refine(T0, **params)
+    finally:
+        ctx.close()

@@ -1,0 +1,741 @@
+// s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point ICP on the full-resolution clouds (include/s4p_icp.h, DESIGN.md
+// section "ICP refinement").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
+//
+// Device path:
+//   set_target   k_stats (per-block double sums and float bounds of P) -> host frame c and grid plan ->
+//                k_cell_keys (cell of fl(P - c)) -> radix sort of (cell, index) -> k_cell_starts + k_gather_target:
+//                the target as cell-ordered float4 (x', y', z', index bits) and the start of every cell.
+//   refine       once: k_source_keys (cell of the T0-image) -> radix sort -> k_gather_source (the source in that order);
+//                per iteration: k_match (correspondence + 17 double sums per lane -> wave -> workgroup -> one slab row),
+//                k_final (fixed-order sum of the slab), one pinned read-back, host solve.
+// No float or double atomics anywhere: every sum has a fixed order, so two calls return identical bits.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "s4p_icp.h"
+
+namespace s4p_icp {
+
+constexpr int kBlock = 256;
+constexpr int kMaxBlocks = 2048;            // grid-stride beyond this: the slab and its final sum stay small
+constexpr int kPitch = 18;                  // doubles per slab row (17 used)
+constexpr int kStatsPitch = 9;              // k_stats row: 3 double sums, 3 float minima, 3 float maxima (as doubles)
+constexpr float kCellFactor = 1.02f;        // cell edge >= 1.02 d: a match is always in the 27 cells around the query's
+constexpr uint64_t kMaxCells = 1ull << 28;
+
+// The dense target grid.  Cells are located in double: cell(x) = floor((x - o) * inv_h), monotone in x.
+struct GridDev {
+  double ox, oy, oz, h, inv_h;
+  int32_t nx, ny, nz;
+  const float4* tgt;          // cell-ordered target: x', y', z', original index (bits)
+  const uint32_t* start;      // ncell + 1 entries
+};
+
+__host__ __device__ inline double cell_coord(float x, double o, double inv_h) { return floor((double(x) - o) * inv_h); }
+
+inline int blocks_for(int64_t n) { return int(std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, kMaxBlocks))); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// frame and bounds of P: per-block partials in a fixed order (summed on the host in row order)
+__global__ __launch_bounds__(kBlock) void k_stats(const float* x, const float* y, const float* z, uint64_t n, double* rows) {
+  double s[3] = {0.0, 0.0, 0.0};
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const float v[3] = {x[i], y[i], z[i]};
+    for (int a = 0; a < 3; ++a) { s[a] += double(v[a]); lo[a] = fminf(lo[a], v[a]); hi[a] = fmaxf(hi[a], v[a]); }
+  }
+  __shared__ double sh[kBlock];
+  for (int k = 0; k < kStatsPitch; ++k) {
+    const double mine = k < 3 ? s[k] : (k < 6 ? double(lo[k - 3]) : double(hi[k - 6]));
+    sh[threadIdx.x] = mine;
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+      if (threadIdx.x < unsigned(w)) {
+        const double a = sh[threadIdx.x], b = sh[threadIdx.x + w];
+        sh[threadIdx.x] = k < 3 ? a + b : (k < 6 ? fmin(a, b) : fmax(a, b));
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) rows[blockIdx.x * kStatsPitch + k] = sh[0];
+    __syncthreads();
+  }
+}
+
+// cell key of every target point fl(P - c); value = its index
+__global__ __launch_bounds__(kBlock) void k_cell_keys(const float* x, const float* y, const float* z, uint64_t n, float cx, float cy,
+                                                      float cz, GridDev g, uint32_t* keys, uint32_t* vals) {
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const float px = x[i] - cx, py = y[i] - cy, pz = z[i] - cz;
+    const int ix = int(cell_coord(px, g.ox, g.inv_h)), iy = int(cell_coord(py, g.oy, g.inv_h)), iz = int(cell_coord(pz, g.oz, g.inv_h));
+    keys[i] = (uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix);
+    vals[i] = uint32_t(i);
+  }
+}
+
+// start[c] = first sorted position with key >= c (lower bound), for every c in [0, ncell]
+__global__ __launch_bounds__(kBlock) void k_cell_starts(const uint32_t* keys, uint64_t n, uint64_t ncell, uint32_t* start) {
+  for (uint64_t c = blockIdx.x * (uint64_t)kBlock + threadIdx.x; c <= ncell; c += (uint64_t)gridDim.x * kBlock) {
+    uint64_t lo = 0, hi = n;
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi) >> 1;
+      if (uint64_t(keys[mid]) < c) lo = mid + 1; else hi = mid;
+    }
+    start[c] = uint32_t(lo);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_gather_target(const float* x, const float* y, const float* z, uint64_t n, float cx, float cy,
+                                                          float cz, const uint32_t* order, float4* tgt) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t i = order[k];
+    tgt[k] = make_float4(x[i] - cx, y[i] - cy, z[i] - cz, __uint_as_float(i));
+  }
+}
+
+// Q' = fl(Q - c), w = original index (bits)
+__global__ __launch_bounds__(kBlock) void k_center_source(const float* x, const float* y, const float* z, uint64_t n, float cx, float cy,
+                                                          float cz, float4* src) {
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock)
+    src[j] = make_float4(x[j] - cx, y[j] - cy, z[j] - cz, __uint_as_float(uint32_t(j)));
+}
+
+struct Tf { float m[12]; };
+
+__device__ inline void apply_t(const Tf& T, float x, float y, float z, float& ox, float& oy, float& oz) {
+  ox = ((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3];
+  oy = ((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7];
+  oz = ((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11];
+}
+
+// source order for a refine call: cell of the T0-image (ncell for a query outside the grid: sorted last)
+__global__ __launch_bounds__(kBlock) void k_source_keys(const float4* src, uint64_t n, Tf T, GridDev g, uint32_t* keys, uint32_t* vals) {
+  const uint32_t ncell = uint32_t(g.nx) * uint32_t(g.ny) * uint32_t(g.nz);
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = src[j];
+    float x, y, z;
+    apply_t(T, q.x, q.y, q.z, x, y, z);
+    const double fx = cell_coord(x, g.ox, g.inv_h), fy = cell_coord(y, g.oy, g.inv_h), fz = cell_coord(z, g.oz, g.inv_h);
+    const bool in = fx >= 0.0 && fx < double(g.nx) && fy >= 0.0 && fy < double(g.ny) && fz >= 0.0 && fz < double(g.nz);
+    keys[j] = in ? (uint32_t(fz) * uint32_t(g.ny) + uint32_t(fy)) * uint32_t(g.nx) + uint32_t(fx) : ncell;
+    vals[j] = uint32_t(j);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_gather_source(const float4* src, const uint32_t* order, uint64_t n, float4* out) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) out[k] = src[order[k]];
+}
+
+// Nearest target within d of q^ (ties to the smallest index).  The 27 cells around q^'s cell hold every candidate: a
+// point with fl(d2) <= fl(d*d) is within d (1 + 2^-21) of q^ along each axis, less than the cell edge (>= 1.02 d).  A cell
+// is skipped when its box (in double, widened by 1e-6 h for the rounding of the cell location) is farther than the running
+// best by a margin (factor 1 - 1e-5) that exceeds the rounding of any float d2 of a point inside it: such a point can
+// neither win nor tie.
+__device__ inline void nearest(const GridDev& g, float x, float y, float z, float d2max, float& best, uint32_t& bi, float4& bp) {
+  best = d2max;
+  bi = 0xFFFFFFFFu;
+  bp = make_float4(0.f, 0.f, 0.f, 0.f);
+  const double fx = cell_coord(x, g.ox, g.inv_h), fy = cell_coord(y, g.oy, g.inv_h), fz = cell_coord(z, g.oz, g.inv_h);
+  // NaN fails every comparison; a query more than one cell outside the grid has no neighbour cell inside it
+  if (!(fx >= -1.0 && fx <= double(g.nx) && fy >= -1.0 && fy <= double(g.ny) && fz >= -1.0 && fz <= double(g.nz))) return;
+  const int cx = int(fx), cy = int(fy), cz = int(fz);
+  const double eps = 1e-6 * g.h;
+  const double qx = double(x), qy = double(y), qz = double(z);
+  // centre cell first (it usually sets a tight bound), then the other 26 in a fixed order
+  for (int s = 0; s < 27; ++s) {
+    const int t = s == 0 ? 13 : (s <= 13 ? s - 1 : s);
+    const int ix = cx + t % 3 - 1, iy = cy + (t / 3) % 3 - 1, iz = cz + t / 9 - 1;
+    if (ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny || iz < 0 || iz >= g.nz) continue;
+    const double bx0 = g.ox + ix * g.h, by0 = g.oy + iy * g.h, bz0 = g.oz + iz * g.h;
+    const double ex = fmax(0.0, fmax(bx0 - qx, qx - (bx0 + g.h)) - eps);
+    const double ey = fmax(0.0, fmax(by0 - qy, qy - (by0 + g.h)) - eps);
+    const double ez = fmax(0.0, fmax(bz0 - qz, qz - (bz0 + g.h)) - eps);
+    if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(best)) continue;
+    const uint32_t c = (uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix);
+    const uint32_t b = g.start[c], e = g.start[c + 1];
+    for (uint32_t k = b; k < e; ++k) {
+      const float4 p = g.tgt[k];
+      const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
+      const float d2 = dx * dx + (dy * dy + dz * dz);
+      const uint32_t i = __float_as_uint(p.w);
+      if (d2 < best || (d2 == best && i < bi)) { best = d2; bi = i; bp = p; }
+    }
+  }
+}
+
+
+struct MatchArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;        // w = original source index (bits)
+  uint64_t n;
+  float d2max;
+  int32_t* idx;             // WRITE only: per source point, in the uploaded order
+  float* d2;
+  double* slab;             // one kPitch row per workgroup
+};
+
+// The hot path.  One lane per source point: apply T, nearest target, 17 double sums in registers; then the wave (xor
+// butterfly), the workgroup (LDS, waves in order) and one slab row.  No transformed cloud is written.
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void k_match(MatchArgs A) {
+  double s[S4P_ICP_NSUMS];
+#pragma unroll
+  for (int k = 0; k < S4P_ICP_NSUMS; ++k) s[k] = 0.0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    float best;
+    uint32_t bi;
+    float4 p;
+    nearest(A.g, x, y, z, A.d2max, best, bi, p);
+    const bool hit = bi != 0xFFFFFFFFu;
+    if (WRITE) {
+      const uint32_t o = __float_as_uint(q.w);
+      A.idx[o] = hit ? int32_t(bi) : -1;
+      A.d2[o] = hit ? best : 0.f;
+    }
+    if (hit) {
+      const double qd[3] = {double(x), double(y), double(z)}, pd[3] = {double(p.x), double(p.y), double(p.z)};
+      s[0] += 1.0;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) { s[1 + a] += qd[a]; s[4 + a] += pd[a]; }
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) s[7 + 3 * a + b] += qd[a] * pd[b];      // exact products (24 + 24 bits)
+      s[16] += double(best);
+    }
+  }
+  __shared__ double red[kBlock / 64][S4P_ICP_NSUMS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < S4P_ICP_NSUMS; ++k) {
+    double v = s[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < S4P_ICP_NSUMS) {
+    double v = red[0][threadIdx.x];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][threadIdx.x];
+    A.slab[uint64_t(blockIdx.x) * kPitch + threadIdx.x] = v;
+  }
+}
+
+// the slab's nb rows -> 17 sums, in a fixed order: 15 parts per column (rows part, part + 15, ...), then the parts in order
+__global__ __launch_bounds__(kBlock) void k_final(const double* slab, int nb, double* out) {
+  constexpr int kParts = kBlock / S4P_ICP_NSUMS;       // 15
+  __shared__ double part[kParts][S4P_ICP_NSUMS];
+  const int col = threadIdx.x % S4P_ICP_NSUMS, prt = threadIdx.x / S4P_ICP_NSUMS;
+  if (prt < kParts) {
+    double v = 0.0;
+    for (int r = prt; r < nb; r += kParts) v += slab[uint64_t(r) * kPitch + col];
+    part[prt][col] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < S4P_ICP_NSUMS) {
+    double v = part[0][threadIdx.x];
+    for (int p = 1; p < kParts; ++p) v += part[p][threadIdx.x];
+    out[threadIdx.x] = v;
+  }
+}
+
+// the returned transform on the caller's cloud, in k_apply's rounding order
+__global__ __launch_bounds__(kBlock) void k_apply_icp(Tf T, float* x, float* y, float* z, uint64_t n) {
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    float ox, oy, oz;
+    apply_t(T, x[i], y[i], z[i], ox, oy, oz);
+    x[i] = ox; y[i] = oy; z[i] = oz;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host: Horn's closed form.  N (4x4 symmetric) from the centred cross-covariance; its eigenvector of the largest
+// eigenvalue (cyclic Jacobi) is the unit quaternion of the rotation.
+void jacobi4(double A[4][4], double V[4][4]) {
+  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int i = 0; i < 4; ++i) { diag += A[i][i] * A[i][i]; for (int j = i + 1; j < 4; ++j) off += A[i][j] * A[i][j]; }
+    if (off == 0.0 || off <= 1e-36 * diag) break;
+    for (int p = 0; p < 3; ++p)
+      for (int q = p + 1; q < 4; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < 4; ++k) {            // A <- J^T A J, columns then rows
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
+        }
+        for (int k = 0; k < 4; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
+        }
+        for (int k = 0; k < 4; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+}
+
+void mat_mul4(const double* A, const double* B, double* C) {    // C = A B (row-major 4x4); C may not alias
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) {
+      double v = 0.0;
+      for (int k = 0; k < 4; ++k) v += A[4 * r + k] * B[4 * k + c];
+      C[4 * r + c] = v;
+    }
+}
+
+// caller frame <-> centred frame (p' = p - c, q' = q - c): T' = [R | R c + t - c], T = [R | t' - R c + c]
+void to_centred(const double* T, const float* c, double* Tc) {
+  std::memcpy(Tc, T, 16 * sizeof(double));
+  for (int r = 0; r < 3; ++r) Tc[4 * r + 3] = T[4 * r + 3] + (T[4 * r] * c[0] + T[4 * r + 1] * c[1] + T[4 * r + 2] * c[2]) - double(c[r]);
+}
+void from_centred(const double* Tc, const float* c, double* T) {
+  std::memcpy(T, Tc, 16 * sizeof(double));
+  for (int r = 0; r < 3; ++r) T[4 * r + 3] = Tc[4 * r + 3] - (Tc[4 * r] * c[0] + Tc[4 * r + 1] * c[1] + Tc[4 * r + 2] * c[2]) + double(c[r]);
+}
+Tf to_float(const double* T) {
+  Tf f;
+  for (int k = 0; k < 12; ++k) f.m[k] = float(T[k]);
+  return f;
+}
+
+}  // namespace s4p_icp
+
+using namespace s4p_icp;
+
+struct s4p_icp_ctx {
+  int device = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t ev = nullptr;
+  std::string err;
+  bool has_target = false, has_source = false, src_dirty = true;
+  float c[3] = {0.f, 0.f, 0.f};
+  float d = 0.f, d2max = 0.f;
+  GridDev g{};
+  uint64_t ncell = 0;
+  int64_t n_p = 0, n_q = 0;
+  float4* tgt = nullptr;
+  uint32_t* start = nullptr;
+  float* qraw[3] = {nullptr, nullptr, nullptr};
+  float4* src = nullptr;
+  float4* src_ord = nullptr;
+  double* slab = nullptr;
+  double* dsum = nullptr;
+  double* hsum = nullptr;            // pinned
+};
+
+namespace {
+
+std::string g_create_error;
+
+int32_t fail(s4p_icp_ctx* h, int32_t code, const std::string& msg) {
+  h->err = msg;
+  return code;
+}
+
+#define ICP_HIP(expr)                                                                                             \
+  do {                                                                                                            \
+    const hipError_t e_ = (expr);                                                                                 \
+    if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? S4P_ICP_ERR_OOM : S4P_ICP_ERR_HIP,          \
+                                      std::string(#expr) + ": " + hipGetErrorString(e_));                        \
+  } while (0)
+
+void dfree(void* p) { if (p) (void)hipFree(p); }
+
+// device temporaries of one call, released on every exit
+struct Scratch {
+  std::vector<void*> ptrs;
+  ~Scratch() { for (void* p : ptrs) dfree(p); }
+  hipError_t alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e == hipSuccess) ptrs.push_back(*p); else *p = nullptr;
+    return e;
+  }
+};
+
+int end_bit(uint64_t max_key) {
+  int b = 1;
+  while (b < 32 && (max_key >> b) != 0) ++b;
+  return b;
+}
+
+// (keys, vals) sorted by key into (keys_out, vals_out): radix sort (stable, deterministic)
+int32_t sort_pairs(s4p_icp_ctx* h, Scratch& S, const uint32_t* keys, uint32_t* keys_out, const uint32_t* vals, uint32_t* vals_out,
+                   uint64_t n, uint64_t max_key) {
+  size_t bytes = 0;
+  ICP_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
+  void* tmp = nullptr;
+  ICP_HIP(S.alloc(&tmp, bytes));
+  ICP_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
+  return S4P_ICP_OK;
+}
+
+int32_t set_target_impl(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n, float d, hipMemcpyKind kind) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!x || !y || !z || n < 1) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: empty or null cloud");
+  if (n >= int64_t(0x7FFFFFFF)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: more than 2^31 - 1 points");
+  if (!(d > 0.f) || !std::isfinite(d)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: max_distance must be finite and > 0");
+  ICP_HIP(hipSetDevice(h->device));
+  h->has_target = false;
+  dfree(h->tgt); h->tgt = nullptr;
+  dfree(h->start); h->start = nullptr;
+  Scratch S;
+  const uint64_t un = uint64_t(n);
+  float* p[3];
+  const float* in[3] = {x, y, z};
+  for (int a = 0; a < 3; ++a) {
+    ICP_HIP(S.alloc((void**)&p[a], un * sizeof(float)));
+    ICP_HIP(hipMemcpyAsync(p[a], in[a], un * sizeof(float), kind, h->st));
+  }
+  // frame and bounds
+  const int nb = blocks_for(n);
+  double* rows = nullptr;
+  ICP_HIP(S.alloc((void**)&rows, size_t(nb) * kStatsPitch * sizeof(double)));
+  hipLaunchKernelGGL(k_stats, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, rows);
+  ICP_HIP(hipGetLastError());
+  std::vector<double> hr(size_t(nb) * kStatsPitch);
+  ICP_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  double sum[3] = {0.0, 0.0, 0.0};
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) { lo[a] = float(hr[3 + a]); hi[a] = float(hr[6 + a]); }
+  for (int b = 0; b < nb; ++b)
+    for (int a = 0; a < 3; ++a) {
+      sum[a] += hr[size_t(b) * kStatsPitch + a];
+      lo[a] = std::min(lo[a], float(hr[size_t(b) * kStatsPitch + 3 + a]));
+      hi[a] = std::max(hi[a], float(hr[size_t(b) * kStatsPitch + 6 + a]));
+    }
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: non-finite coordinates");
+    h->c[a] = float(sum[a] / double(n));
+  }
+  // bounds of P' = fl(P - c): rounding is monotone, so they are fl(lo - c), fl(hi - c)
+  float plo[3], phi[3];
+  for (int a = 0; a < 3; ++a) { plo[a] = lo[a] - h->c[a]; phi[a] = hi[a] - h->c[a]; }
+  // grid plan: cell edge 1.02 d, enlarged x 1.25 until the dense grid fits the cell cap (cf. LcpGridHost::plan)
+  const uint64_t cap = std::min<uint64_t>(kMaxCells, std::max<uint64_t>(1ull << 20, 2 * un));
+  double hh = double(d) * double(kCellFactor);
+  int dims[3];
+  for (int guard = 0;; ++guard) {
+    const double inv = 1.0 / hh;
+    bool ok = true;
+    uint64_t nc = 1;
+    for (int a = 0; a < 3; ++a) {
+      const double cc = cell_coord(phi[a], double(plo[a]), inv);
+      if (!(cc < 1.0e9)) { ok = false; break; }
+      dims[a] = int(cc) + 1;
+      nc *= uint64_t(dims[a]);
+      if (nc > cap) { ok = false; break; }
+    }
+    if (ok) { h->g.h = hh; h->g.inv_h = inv; h->ncell = nc; break; }
+    if (guard > 400) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: no grid fits the cloud's extent");
+    hh *= 1.25;
+  }
+  h->g.ox = plo[0]; h->g.oy = plo[1]; h->g.oz = plo[2];
+  h->g.nx = dims[0]; h->g.ny = dims[1]; h->g.nz = dims[2];
+  h->d = d;
+  h->d2max = d * d;
+  // cell-ordered target
+  uint32_t *keys, *vals, *keys2, *vals2;
+  ICP_HIP(S.alloc((void**)&keys, un * 4)); ICP_HIP(S.alloc((void**)&vals, un * 4));
+  ICP_HIP(S.alloc((void**)&keys2, un * 4)); ICP_HIP(S.alloc((void**)&vals2, un * 4));
+  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, h->c[0], h->c[1], h->c[2], h->g, keys, vals);
+  ICP_HIP(hipGetLastError());
+  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell - 1)) return rc;
+  ICP_HIP(hipMalloc((void**)&h->start, (h->ncell + 1) * sizeof(uint32_t)));
+  ICP_HIP(hipMalloc((void**)&h->tgt, un * sizeof(float4)));
+  hipLaunchKernelGGL(k_cell_starts, dim3(blocks_for(int64_t(h->ncell) + 1)), dim3(kBlock), 0, h->st, keys2, un, h->ncell, h->start);
+  ICP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_gather_target, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, h->c[0], h->c[1], h->c[2], vals2, h->tgt);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipStreamSynchronize(h->st));          // the scratch is freed on return
+  h->g.tgt = h->tgt;
+  h->g.start = h->start;
+  h->n_p = n;
+  h->has_target = true;
+  h->src_dirty = true;                          // Q' depends on c
+  return S4P_ICP_OK;
+}
+
+int32_t set_source_impl(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n, hipMemcpyKind kind) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!x || !y || !z || n < 1) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source: empty or null cloud");
+  if (n >= int64_t(0x7FFFFFFF)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source: more than 2^31 - 1 points");
+  ICP_HIP(hipSetDevice(h->device));
+  h->has_source = false;
+  if (n != h->n_q) {
+    for (int a = 0; a < 3; ++a) { dfree(h->qraw[a]); h->qraw[a] = nullptr; }
+    dfree(h->src); dfree(h->src_ord); h->src = h->src_ord = nullptr;
+    dfree(h->slab); h->slab = nullptr;
+    h->n_q = 0;
+    for (int a = 0; a < 3; ++a) ICP_HIP(hipMalloc((void**)&h->qraw[a], size_t(n) * sizeof(float)));
+    ICP_HIP(hipMalloc((void**)&h->src, size_t(n) * sizeof(float4)));
+    ICP_HIP(hipMalloc((void**)&h->src_ord, size_t(n) * sizeof(float4)));
+    ICP_HIP(hipMalloc((void**)&h->slab, size_t(blocks_for(n)) * kPitch * sizeof(double)));
+    h->n_q = n;
+  }
+  const float* in[3] = {x, y, z};
+  for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(h->qraw[a], in[a], size_t(n) * sizeof(float), kind, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  h->has_source = true;
+  h->src_dirty = true;
+  return S4P_ICP_OK;
+}
+
+int32_t ready(s4p_icp_ctx* h) {
+  if (!h->has_target || !h->has_source) return fail(h, S4P_ICP_ERR_STATE, "set_target and set_source first");
+  ICP_HIP(hipSetDevice(h->device));
+  if (h->src_dirty) {
+    hipLaunchKernelGGL(k_center_source, dim3(blocks_for(h->n_q)), dim3(kBlock), 0, h->st, h->qraw[0], h->qraw[1], h->qraw[2],
+                       uint64_t(h->n_q), h->c[0], h->c[1], h->c[2], h->src);
+    ICP_HIP(hipGetLastError());
+    h->src_dirty = false;
+  }
+  return S4P_ICP_OK;
+}
+
+// one correspondence pass over `src` for T: the 17 sums (and, if idx, the per-point answers) on the host
+int32_t pass(s4p_icp_ctx* h, const Tf& T, const float4* src, int32_t* idx_dev, float* d2_dev, double* out) {
+  MatchArgs A;
+  A.T = T; A.g = h->g; A.src = src; A.n = uint64_t(h->n_q); A.d2max = h->d2max; A.idx = idx_dev; A.d2 = d2_dev; A.slab = h->slab;
+  const int nb = blocks_for(h->n_q);
+  if (idx_dev) hipLaunchKernelGGL(k_match<true>, dim3(nb), dim3(kBlock), 0, h->st, A);
+  else hipLaunchKernelGGL(k_match<false>, dim3(nb), dim3(kBlock), 0, h->st, A);
+  ICP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_final, dim3(1), dim3(kBlock), 0, h->st, (const double*)h->slab, nb, h->dsum);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(h->hsum, h->dsum, S4P_ICP_NSUMS * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipEventRecord(h->ev, h->st));
+  ICP_HIP(hipEventSynchronize(h->ev));
+  std::memcpy(out, h->hsum, S4P_ICP_NSUMS * sizeof(double));
+  return S4P_ICP_OK;
+}
+
+Tf centred_from_float16(const float* T16) {
+  Tf f;
+  for (int k = 0; k < 12; ++k) f.m[k] = T16[k];
+  return f;
+}
+
+}  // namespace
+
+extern "C" {
+
+void s4p_icp_default_params(s4p_icp_params* p) {
+  if (!p) return;
+  p->max_iterations = 30;
+  p->min_correspondences = 3;
+  p->rel_tol = 1e-6;
+  p->order_source = 1;
+  p->reserved = 0;
+}
+
+const char* s4p_icp_last_error(const s4p_icp_ctx* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int32_t s4p_icp_create(int32_t device, s4p_icp_ctx** out) {
+  if (!out) { g_create_error = "null argument"; return S4P_ICP_ERR_BAD_ARG; }
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    g_create_error = "no HIP device visible: the MI355X path has no CPU fallback";
+    return S4P_ICP_ERR_NO_DEVICE;
+  }
+  if (device < 0 || device >= ndev) { g_create_error = "bad device index"; return S4P_ICP_ERR_BAD_ARG; }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) { g_create_error = "hipGetDeviceProperties failed"; return S4P_ICP_ERR_HIP; }
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
+    g_create_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
+    return S4P_ICP_ERR_NO_DEVICE;
+  }
+  s4p_icp_ctx* h = new s4p_icp_ctx();
+  h->device = device;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess ||
+      hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess ||
+      hipMalloc((void**)&h->dsum, S4P_ICP_NSUMS * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&h->hsum, S4P_ICP_NSUMS * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+    g_create_error = "HIP stream / event / buffer creation failed";
+    s4p_icp_destroy(h);
+    return S4P_ICP_ERR_HIP;
+  }
+  *out = h;
+  return S4P_ICP_OK;
+}
+
+void s4p_icp_destroy(s4p_icp_ctx* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  dfree(h->tgt); dfree(h->start); dfree(h->src); dfree(h->src_ord); dfree(h->slab); dfree(h->dsum);
+  for (int a = 0; a < 3; ++a) dfree(h->qraw[a]);
+  if (h->hsum) (void)hipHostFree(h->hsum);
+  if (h->ev) (void)hipEventDestroy(h->ev);
+  if (h->st) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+
+int32_t s4p_icp_set_target(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n, float max_distance) {
+  return set_target_impl(h, x, y, z, n, max_distance, hipMemcpyHostToDevice);
+}
+int32_t s4p_icp_set_target_device(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n, float max_distance) {
+  return set_target_impl(h, x, y, z, n, max_distance, hipMemcpyDeviceToDevice);
+}
+int32_t s4p_icp_set_source(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n) {
+  return set_source_impl(h, x, y, z, n, hipMemcpyHostToDevice);
+}
+int32_t s4p_icp_set_source_device(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n) {
+  return set_source_impl(h, x, y, z, n, hipMemcpyDeviceToDevice);
+}
+
+int32_t s4p_icp_frame(const s4p_icp_ctx* h, float* c3) {
+  if (!h || !c3) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return S4P_ICP_ERR_STATE;
+  for (int a = 0; a < 3; ++a) c3[a] = h->c[a];
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_correspondences(s4p_icp_ctx* h, const float* T16_centred, int32_t* idx, float* d2) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !idx || !d2) return fail(h, S4P_ICP_ERR_BAD_ARG, "correspondences: null argument");
+  if (int32_t rc = ready(h)) return rc;
+  Scratch S;
+  int32_t* di;
+  float* dd;
+  ICP_HIP(S.alloc((void**)&di, size_t(h->n_q) * 4));
+  ICP_HIP(S.alloc((void**)&dd, size_t(h->n_q) * 4));
+  double sums[S4P_ICP_NSUMS];
+  if (int32_t rc = pass(h, centred_from_float16(T16_centred), h->src, di, dd, sums)) return rc;
+  ICP_HIP(hipMemcpy(idx, di, size_t(h->n_q) * 4, hipMemcpyDeviceToHost));
+  ICP_HIP(hipMemcpy(d2, dd, size_t(h->n_q) * 4, hipMemcpyDeviceToHost));
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_sums(s4p_icp_ctx* h, const float* T16_centred, double* sums) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "sums: null argument");
+  if (int32_t rc = ready(h)) return rc;
+  return pass(h, centred_from_float16(T16_centred), h->src, nullptr, nullptr, sums);
+}
+
+int32_t s4p_icp_solve(const double* sums, double* dT16) {
+  if (!sums || !dT16) return S4P_ICP_ERR_BAD_ARG;
+  const double n = sums[0];
+  if (!(n >= 1.0)) return S4P_ICP_ERR_BAD_ARG;
+  double mq[3], mp[3], S[3][3];
+  for (int a = 0; a < 3; ++a) { mq[a] = sums[1 + a] / n; mp[a] = sums[4 + a] / n; }
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) S[a][b] = sums[7 + 3 * a + b] / n - mq[a] * mp[b];
+  const double Sxx = S[0][0], Sxy = S[0][1], Sxz = S[0][2], Syx = S[1][0], Syy = S[1][1], Syz = S[1][2], Szx = S[2][0],
+               Szy = S[2][1], Szz = S[2][2];
+  double N[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                    {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
+                    {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
+                    {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
+  double V[4][4];
+  jacobi4(N, V);
+  int best = 0;
+  for (int k = 1; k < 4; ++k) if (N[k][k] > N[best][best]) best = k;
+  double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
+  const double nq = std::sqrt(w * w + x * x + y * y + z * z);
+  w /= nq; x /= nq; y /= nq; z /= nq;
+  const double R[3][3] = {{w * w + x * x - y * y - z * z, 2.0 * (x * y - w * z), 2.0 * (x * z + w * y)},
+                          {2.0 * (x * y + w * z), w * w - x * x + y * y - z * z, 2.0 * (y * z - w * x)},
+                          {2.0 * (x * z - w * y), 2.0 * (y * z + w * x), w * w - x * x - y * y + z * z}};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) dT16[4 * r + c] = R[r][c];
+    dT16[4 * r + 3] = mp[r] - (R[r][0] * mq[0] + R[r][1] * mq[1] + R[r][2] * mq[2]);
+  }
+  dT16[12] = dT16[13] = dT16[14] = 0.0;
+  dT16[15] = 1.0;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_refine(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_inout) return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: null transform");
+  s4p_icp_params P;
+  s4p_icp_default_params(&P);
+  if (params) P = *params;
+  if (P.max_iterations < 0 || P.min_correspondences < 0 || !(P.rel_tol >= 0.0))
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: negative max_iterations / min_correspondences / rel_tol");
+  if (int32_t rc = ready(h)) return rc;
+  s4p_icp_result R;
+  std::memset(&R, 0, sizeof(R));
+  double T[16], Tn[16], dT[16], sums[S4P_ICP_NSUMS];
+  to_centred(T16_inout, h->c, T);
+  const float4* src = h->src;
+  if (P.order_source) {            // visit the source in the cell order of its T0-image: a wave's lanes read neighbouring cells
+    Scratch S;
+    const uint64_t un = uint64_t(h->n_q);
+    uint32_t *keys, *vals, *keys2, *vals2;
+    ICP_HIP(S.alloc((void**)&keys, un * 4)); ICP_HIP(S.alloc((void**)&vals, un * 4));
+    ICP_HIP(S.alloc((void**)&keys2, un * 4)); ICP_HIP(S.alloc((void**)&vals2, un * 4));
+    const int nb = blocks_for(h->n_q);
+    hipLaunchKernelGGL(k_source_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, un, to_float(T), h->g, keys, vals);
+    ICP_HIP(hipGetLastError());
+    if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell)) return rc;
+    hipLaunchKernelGGL(k_gather_source, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, (const uint32_t*)vals2, un, h->src_ord);
+    ICP_HIP(hipGetLastError());
+    ICP_HIP(hipStreamSynchronize(h->st));
+    src = h->src_ord;
+  }
+  double prev = 0.0;
+  R.status = S4P_ICP_MAX_ITERATIONS;
+  for (int k = 0; k < P.max_iterations; ++k) {
+    if (int32_t rc = pass(h, to_float(T), src, nullptr, nullptr, sums)) return rc;
+    const double n = sums[0];
+    const double rmse = n > 0.0 ? std::sqrt(sums[16] / n) : 0.0;
+    if (k < S4P_ICP_HISTORY) { R.history_rmse[k] = rmse; R.history_n[k] = int64_t(n); R.history_len = k + 1; }
+    if (n < double(std::max(P.min_correspondences, 1))) { R.status = S4P_ICP_TOO_FEW; break; }
+    s4p_icp_solve(sums, dT);
+    mat_mul4(dT, T, Tn);
+    std::memcpy(T, Tn, sizeof(T));
+    R.iterations = k + 1;
+    if (k + 1 == P.max_iterations) { R.status = S4P_ICP_MAX_ITERATIONS; break; }
+    if (k > 0 && std::fabs(rmse - prev) <= P.rel_tol * prev) { R.status = S4P_ICP_CONVERGED; break; }
+    prev = rmse;
+  }
+  // final pass: the statistics of the returned transform
+  if (int32_t rc = pass(h, to_float(T), src, nullptr, nullptr, sums)) return rc;
+  R.n_corr = int64_t(sums[0]);
+  R.rmse = sums[0] > 0.0 ? std::sqrt(sums[16] / sums[0]) : 0.0;
+  R.fitness = double(R.n_corr) / double(h->n_q);
+  from_centred(T, h->c, T16_inout);
+  if (result) *result = R;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_apply(s4p_icp_ctx* h, const double* T16, float* x, float* y, float* z, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16 || !x || !y || !z || n < 0) return fail(h, S4P_ICP_ERR_BAD_ARG, "apply: null argument");
+  if (n == 0) return S4P_ICP_OK;
+  ICP_HIP(hipSetDevice(h->device));
+  Scratch S;
+  float* p[3];
+  float* io[3] = {x, y, z};
+  for (int a = 0; a < 3; ++a) {
+    ICP_HIP(S.alloc((void**)&p[a], size_t(n) * sizeof(float)));
+    ICP_HIP(hipMemcpyAsync(p[a], io[a], size_t(n) * sizeof(float), hipMemcpyHostToDevice, h->st));
+  }
+  hipLaunchKernelGGL(k_apply_icp, dim3(blocks_for(n)), dim3(kBlock), 0, h->st, to_float(T16), p[0], p[1], p[2], uint64_t(n));
+  ICP_HIP(hipGetLastError());
+  for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(io[a], p[a], size_t(n) * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  return S4P_ICP_OK;
+}
+
+}  // extern "C"

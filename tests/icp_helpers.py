@@ -1,0 +1,108 @@
+"""Test-side restatement of the ICP contract (include/s4p_icp.h): tests/icp_cpu/icp_cpu.cpp through ctypes, and the
+refine loop on top of it with the library's host solve (s4p_icp_solve)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "icp_cpu", "icp_cpu.cpp")
+
+
+def build_cpu(outdir):
+    so = os.path.join(str(outdir), "libicp_cpu.so")
+    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
+    L = C.CDLL(so)
+    fp, vp = C.POINTER(C.c_float), C.c_void_p
+    L.icp_cpu_pass.restype = C.c_int64
+    L.icp_cpu_pass.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_float, vp, vp, vp, C.c_int32]
+    L.icp_cpu_brute.restype = None
+    L.icp_cpu_brute.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_float, vp, vp]
+    return CPU(L)
+
+
+class CPU:
+    def __init__(self, L):
+        self.L = L
+
+    @staticmethod
+    def _cols(X):
+        return [np.ascontiguousarray(X[:, k], np.float32) for k in range(3)]
+
+    def pass_(self, Pc, Qc, T, d, want_idx=True, threads=0):
+        """(idx, d2, sums[17]) for centred clouds and a float 4x4 T (centred frame)."""
+        p, q = self._cols(Pc), self._cols(Qc)
+        T12 = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16)[:12])
+        nq = q[0].shape[0]
+        idx = np.empty(nq, np.int32) if want_idx else None
+        d2 = np.empty(nq, np.float32) if want_idx else None
+        sums = np.empty(17, np.float64)
+        self.L.icp_cpu_pass(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, p[0].shape[0], q[0].ctypes.data, q[1].ctypes.data,
+                            q[2].ctypes.data, nq, T12.ctypes.data, float(d), idx.ctypes.data if want_idx else None,
+                            d2.ctypes.data if want_idx else None, sums.ctypes.data, int(threads))
+        return idx, d2, sums
+
+    def brute(self, Pc, Qc, T, d):
+        p, q = self._cols(Pc), self._cols(Qc)
+        T12 = np.ascontiguousarray(np.asarray(T, np.float32).reshape(16)[:12])
+        nq = q[0].shape[0]
+        idx = np.empty(nq, np.int32); d2 = np.empty(nq, np.float32)
+        self.L.icp_cpu_brute(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, p[0].shape[0], q[0].ctypes.data, q[1].ctypes.data,
+                             q[2].ctypes.data, nq, T12.ctypes.data, float(d), idx.ctypes.data, d2.ctypes.data)
+        return idx, d2
+
+
+def numpy_brute(Pc, Qc, T, d):
+    """The contract in numpy (float32 throughout, same rounding order): small clouds only."""
+    T = np.asarray(T, np.float32).reshape(4, 4)
+    x, y, z = Qc[:, 0], Qc[:, 1], Qc[:, 2]
+    qh = [((T[r, 0] * x + T[r, 1] * y) + T[r, 2] * z) + T[r, 3] for r in range(3)]
+    dx = qh[0][:, None] - Pc[None, :, 0]; dy = qh[1][:, None] - Pc[None, :, 1]; dz = qh[2][:, None] - Pc[None, :, 2]
+    D = dx * dx + (dy * dy + dz * dz)
+    d2max = np.float32(d) * np.float32(d)
+    D = np.where(D <= d2max, D, np.float32(np.inf))
+    idx = np.argmin(D, axis=1).astype(np.int32)                 # first index of the minimum: ties to the smallest
+    best = D[np.arange(len(idx)), idx]
+    none = ~np.isfinite(best)
+    idx[none] = -1
+    return idx, np.where(none, np.float32(0), best).astype(np.float32)
+
+
+def to_centred(T, c):
+    Tc = np.array(T, np.float64).reshape(4, 4).copy()
+    for r in range(3):
+        Tc[r, 3] = T[r, 3] + (T[r, 0] * float(c[0]) + T[r, 1] * float(c[1]) + T[r, 2] * float(c[2])) - float(c[r])
+    return Tc
+
+
+def from_centred(Tc, c):
+    T = np.array(Tc, np.float64).reshape(4, 4).copy()
+    for r in range(3):
+        T[r, 3] = Tc[r, 3] - (Tc[r, 0] * float(c[0]) + Tc[r, 1] * float(c[1]) + Tc[r, 2] * float(c[2])) + float(c[r])
+    return T
+
+
+def cpu_refine(cpu, solve, Pc, Qc, c, T0, d, max_iterations=30, rel_tol=1e-6, min_correspondences=3, threads=0):
+    """The refine loop of s4p_icp_refine on the CPU restatement: (T caller frame, iterations, status, history)."""
+    from super4pcs_amd import icp
+    T = to_centred(np.asarray(T0, np.float64), c)
+    prev, status, its, hist = 0.0, icp.MAX_ITERATIONS, 0, []
+    for k in range(max_iterations):
+        _, _, s = cpu.pass_(Pc, Qc, T.astype(np.float32), d, want_idx=False, threads=threads)
+        n = s[0]
+        rmse = float(np.sqrt(s[16] / n)) if n > 0 else 0.0
+        hist.append(rmse)
+        if n < max(min_correspondences, 1):
+            status = icp.TOO_FEW
+            break
+        T = icp.compose(solve(s), T)
+        its = k + 1
+        if k + 1 == max_iterations:
+            status = icp.MAX_ITERATIONS
+            break
+        if k > 0 and abs(rmse - prev) <= rel_tol * prev:
+            status = icp.CONVERGED
+            break
+        prev = rmse
+    return from_centred(T, c), its, status, hist
