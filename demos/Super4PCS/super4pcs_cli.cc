@@ -4,8 +4,9 @@
 // options, 255 (-1) unreadable input.
 //   Super4PCS -i P.obj Q.obj [-o overlap] [-d delta] [-n samples] [-t seconds] [-a normal_deg] [-c colour]
 //             [-r registered_geometry] [-m polyworks_matrix] [--sampled1 file] [--sampled2 file]
-//             [--icp iterations] [--icp-dist max_distance]
-// --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written.
+//             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane] [--icp-normal-radius r]
+// --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
+// with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
@@ -87,6 +88,8 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       ICPOptions icp;
       icp.max_iterations = opt.icp_iterations;
       icp.max_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
+      icp.metric = opt.icp_plane ? ICPMetric::PointToPlane : ICPMetric::PointToPoint;
+      icp.normal_radius = opt.icp_normal_radius;
       ICPResult res;
       RefineICP(P.points, &Q.points, mat, icp, &res);
       log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);

@@ -4,6 +4,7 @@
 #ifndef S4P_CLI_OPTIONS_H_
 #define S4P_CLI_OPTIONS_H_
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +24,8 @@ struct Options {
   bool legacy_4pcs = false;                                  // -x
   int icp_iterations = 0;                                    // --icp  ICP refinement after the registration (0: off)
   double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
+  bool icp_plane = false;                                    // --icp-metric point|plane  (default point)
+  double icp_normal_radius = -1;                             // --icp-normal-radius  (default: the ICP max distance)
   bool bad_value = false;                                    // a flag's value does not parse
 };
 
@@ -58,6 +61,16 @@ inline const Flag* flag_table(size_t* n) {
          char* end = nullptr;
          const double d = std::strtod(v[0], &end);
          if (end == v[0] || *end != '\0' || !(d > 0)) o.bad_value = true; else o.icp_distance = d;
+       }},
+      {"--icp-metric", 1, [](Options& o, char** v) {
+         if (!std::strcmp(v[0], "point")) o.icp_plane = false;
+         else if (!std::strcmp(v[0], "plane")) o.icp_plane = true;
+         else o.bad_value = true;
+       }},
+      {"--icp-normal-radius", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double r = std::strtod(v[0], &end);
+         if (end == v[0] || *end != '\0' || !(r > 0) || !std::isfinite(r)) o.bad_value = true; else o.icp_normal_radius = r;
        }},
   };
   *n = sizeof(table) / sizeof(table[0]);
@@ -96,6 +109,7 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ -x (legacy 4PCS: not available in this build) ]\n");
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
   std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
+  std::fprintf(stderr, "\t[ --icp-metric point|plane (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

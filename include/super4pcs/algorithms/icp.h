@@ -1,6 +1,7 @@
-// RefineICP: point-to-point ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
+// RefineICP: point-to-point or point-to-plane ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
 // documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
-// of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h).
+// of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h,
+// include/s4p_icp_plane.h).
 // Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
 //
 //   MatchSuper4PCS matcher(options, logger);
@@ -17,9 +18,12 @@
 #include <vector>
 
 #include "s4p_icp.h"
+#include "s4p_icp_plane.h"
 #include "super4pcs/algorithms/match4pcsBase.h"
 
 namespace GlobalRegistration {
+
+enum class ICPMetric { PointToPoint, PointToPlane };
 
 struct ICPOptions {
   int max_iterations = 30;
@@ -27,11 +31,15 @@ struct ICPOptions {
   double rel_tol = 1e-6;
   int min_correspondences = 3;
   int device = 0;
+  ICPMetric metric = ICPMetric::PointToPoint;
+  // PointToPlane: P's normals when every point of P has a nonzero one, else normals estimated on the device from the
+  // neighbours within normal_radius (<= 0: max_distance; at most max_distance) with at least 6 of them
+  double normal_radius = -1.0;
 };
 
 struct ICPResult {
   int iterations = 0;
-  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / S4P_ICP_CONVERGED / S4P_ICP_TOO_FEW
+  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane)
   int64_t n_corr = 0;
   double rmse = 0.0;
   double fitness = 0.0;             // n_corr / |Q|
@@ -62,6 +70,23 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   soa(*Q, q);
   H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
   H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
+  const bool plane = options.metric == ICPMetric::PointToPlane;
+  if (plane) {
+    bool all = true;
+    for (const Point3D& pt : P) {
+      const auto& nv = pt.normal();
+      if (!(nv(0) != 0 || nv(1) != 0 || nv(2) != 0)) { all = false; break; }
+    }
+    if (all) {
+      std::vector<float> n[3];
+      for (int k = 0; k < 3; ++k) n[k].resize(P.size());
+      for (size_t i = 0; i < P.size(); ++i) for (int k = 0; k < 3; ++k) n[k][i] = float(P[i].normal()(k));
+      H.check(s4p_icp_set_target_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(P.size())));
+    } else {
+      const double r = options.normal_radius > 0 ? options.normal_radius : options.max_distance;
+      H.check(s4p_icp_estimate_normals(H.h, float(r), 6));
+    }
+  }
   s4p_icp_params prm;
   s4p_icp_default_params(&prm);
   prm.max_iterations = options.max_iterations;
@@ -69,7 +94,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   prm.rel_tol = options.rel_tol;
   double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   s4p_icp_result r;
-  H.check(s4p_icp_refine(H.h, &prm, dT, &r));
+  H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
   H.check(s4p_icp_apply(H.h, dT, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
   for (size_t i = 0; i < Q->size(); ++i) { (*Q)[i].x() = q[0][i]; (*Q)[i].y() = q[1][i]; (*Q)[i].z() = q[2][i]; }
   double M[16];

@@ -1,7 +1,9 @@
-"""ctypes binding of include/s4p_icp.h (libsuper4pcs_icp.so): point-to-point ICP refinement on the full-resolution clouds.
+"""ctypes binding of include/s4p_icp.h and include/s4p_icp_plane.h (libsuper4pcs_icp.so): point-to-point and
+point-to-plane ICP refinement on the full-resolution clouds.
 
     from super4pcs_amd import icp
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="plane")   # target normals estimated on the device
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -16,15 +18,24 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsuper4pcs_icp.so")
 
 NSUMS = 17
+PLANE_NSUMS = 31
 HISTORY = 64
-MAX_ITERATIONS, CONVERGED, TOO_FEW = 0, 1, 2
-STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged", TOO_FEW: "too few correspondences"}
-ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE"}
+MAX_ITERATIONS, CONVERGED, TOO_FEW, DEGENERATE = 0, 1, 2, 3
+STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged", TOO_FEW: "too few correspondences",
+                DEGENERATE: "degenerate plane system"}
+ERR_DEGENERATE = -8
+ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE", ERR_DEGENERATE: "DEGENERATE"}
+METRICS = ("point", "plane")
+MIN_NEIGHBOURS = 6              # estimate_normals' default
 
 SYMBOLS = [
     "s4p_icp_default_params", "s4p_icp_create", "s4p_icp_destroy", "s4p_icp_last_error", "s4p_icp_set_target",
     "s4p_icp_set_source", "s4p_icp_set_target_device", "s4p_icp_set_source_device", "s4p_icp_frame",
     "s4p_icp_correspondences", "s4p_icp_sums", "s4p_icp_solve", "s4p_icp_refine", "s4p_icp_apply",
+]
+PLANE_SYMBOLS = [                                          # include/s4p_icp_plane.h
+    "s4p_icp_set_target_normals", "s4p_icp_set_target_normals_device", "s4p_icp_estimate_normals", "s4p_icp_target_normals",
+    "s4p_icp_plane_sums", "s4p_icp_solve_plane", "s4p_icp_refine_plane",
 ]
 
 
@@ -87,6 +98,19 @@ def load_library():
     L.s4p_icp_refine.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
     L.s4p_icp_apply.restype = C.c_int32
     L.s4p_icp_apply.argtypes = [vp, dp, fp, fp, fp, C.c_int64]
+    for name in ("s4p_icp_set_target_normals", "s4p_icp_set_target_normals_device"):
+        getattr(L, name).restype = C.c_int32
+        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.s4p_icp_estimate_normals.restype = C.c_int32
+    L.s4p_icp_estimate_normals.argtypes = [vp, C.c_float, C.c_int32]
+    L.s4p_icp_target_normals.restype = C.c_int32
+    L.s4p_icp_target_normals.argtypes = [vp, fp, fp, fp]
+    L.s4p_icp_plane_sums.restype = C.c_int32
+    L.s4p_icp_plane_sums.argtypes = [vp, fp, dp]
+    L.s4p_icp_solve_plane.restype = C.c_int32
+    L.s4p_icp_solve_plane.argtypes = [dp, dp]
+    L.s4p_icp_refine_plane.restype = C.c_int32
+    L.s4p_icp_refine_plane.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
     _LIB = L
     return L
 
@@ -107,6 +131,18 @@ def solve(sums):
     rc = L.s4p_icp_solve(_dp(s), _dp(out))
     if rc != 0:
         raise ICPError(rc, "solve: n < 1")
+    return out.reshape(4, 4)
+
+
+def solve_plane(sums):
+    """The point-to-plane step on the 31 plane sums (host only, no device): dT = [Rodrigues(omega) | t] with A (omega, t) = b.
+    Raises ICPError with code ERR_DEGENERATE when n_plane < 6 or A is not safely positive definite."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, np.float64).reshape(PLANE_NSUMS)
+    out = np.empty(16, np.float64)
+    rc = L.s4p_icp_solve_plane(_dp(s), _dp(out))
+    if rc != 0:
+        raise ICPError(rc, "solve_plane: degenerate system" if rc == ERR_DEGENERATE else "solve_plane: bad argument")
     return out.reshape(4, 4)
 
 
@@ -139,6 +175,7 @@ class ICP:
         if rc != 0:
             raise ICPError(rc, self.L.s4p_icp_last_error(None).decode())
         self.h = h
+        self.n_p = 0
         self.n_q = 0
 
     def close(self):
@@ -174,6 +211,7 @@ class ICP:
     def set_target(self, P, max_distance):
         suf, ptr, n, keep = self._cols(P)
         self._chk(getattr(self.L, "s4p_icp_set_target" + suf)(self.h, ptr[0], ptr[1], ptr[2], n, float(max_distance)))
+        self.n_p = n
         del keep
 
     def set_source(self, Q):
@@ -192,6 +230,30 @@ class ICP:
         T = np.ascontiguousarray(np.asarray(T).reshape(4, 4), np.float32).reshape(16)
         return T
 
+    def set_target_normals(self, N):
+        """One normal per target point (N, 3), in the uploaded order: normalised in double, zero / non-finite -> 0."""
+        suf, ptr, n, keep = self._cols(N)
+        self._chk(getattr(self.L, "s4p_icp_set_target_normals" + suf)(self.h, ptr[0], ptr[1], ptr[2], n))
+        del keep
+
+    def estimate_normals(self, radius, min_neighbours=MIN_NEIGHBOURS):
+        """Target normals on the device from the neighbours within radius (0 < radius <= max_distance)."""
+        self._chk(self.L.s4p_icp_estimate_normals(self.h, float(radius), int(min_neighbours)))
+
+    def target_normals(self):
+        """float32 (n_P, 3): the current target normals, in the uploaded order."""
+        n = self.n_p
+        cols = [np.empty(n, np.float32) for _ in range(3)]
+        self._chk(self.L.s4p_icp_target_normals(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
+        return np.stack(cols, axis=1)
+
+    def plane_sums(self, T):
+        """The 31 plane sums for a float T in the centred frame (layout in include/s4p_icp_plane.h)."""
+        T = self._t32(T)
+        out = np.empty(PLANE_NSUMS, np.float64)
+        self._chk(self.L.s4p_icp_plane_sums(self.h, _fp(T), _dp(out)))
+        return out
+
     def correspondences(self, T):
         """(idx int32[n_Q], d2 float32[n_Q]) for a float T in the centred frame; idx -1 where nothing is within d."""
         T = self._t32(T)
@@ -206,15 +268,19 @@ class ICP:
         self._chk(self.L.s4p_icp_sums(self.h, _fp(T), _dp(out)))
         return out
 
-    def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True):
-        """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity)."""
+    def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True, metric="point"):
+        """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity).  metric "plane"
+        minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals)."""
+        if metric not in METRICS:
+            raise ValueError("metric must be one of %s" % (METRICS,))
         T = np.ascontiguousarray(np.eye(4) if T0 is None else np.asarray(T0, np.float64).reshape(4, 4), np.float64).reshape(16).copy()
         p = Params()
         self.L.s4p_icp_default_params(C.byref(p))
         p.max_iterations, p.rel_tol, p.min_correspondences = int(max_iterations), float(rel_tol), int(min_correspondences)
         p.order_source = int(bool(order_source))
         r = Result()
-        self._chk(self.L.s4p_icp_refine(self.h, C.byref(p), _dp(T), C.byref(r)))
+        fn = self.L.s4p_icp_refine_plane if metric == "plane" else self.L.s4p_icp_refine
+        self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
         return T.reshape(4, 4), r
 
     def apply(self, T, X):
@@ -226,14 +292,22 @@ class ICP:
         return np.stack(cols, axis=1)
 
 
-def refine(P, Q, T0=None, max_distance=None, device=0, **params):
-    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required."""
+def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None, **params):
+    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane": the
+    target normals are target_normals if given, else estimated within normal_radius (default max_distance)."""
     if max_distance is None:
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
+    if metric not in METRICS:
+        raise ValueError("metric must be one of %s" % (METRICS,))
     ctx = ICP(device)
     try:
         ctx.set_target(P, max_distance)
         ctx.set_source(Q)
-        return ctx.refine(T0, **params)
+        if metric == "plane":
+            if target_normals is not None:
+                ctx.set_target_normals(target_normals)
+            else:
+                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
+        return ctx.refine(T0, metric=metric, **params)
     finally:
         ctx.close()

@@ -1,5 +1,5 @@
-// s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point ICP on the full-resolution clouds (include/s4p_icp.h, DESIGN.md
-// section "ICP refinement").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
+// s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point and point-to-plane ICP on the full-resolution clouds (include/s4p_icp.h,
+// include/s4p_icp_plane.h, DESIGN.md sections "ICP refinement" and "Point-to-plane ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
 //
 // Device path:
 //   set_target   k_stats (per-block double sums and float bounds of P) -> host frame c and grid plan ->
@@ -8,6 +8,8 @@
 //   refine       once: k_source_keys (cell of the T0-image) -> radix sort -> k_gather_source (the source in that order);
 //                per iteration: k_match (correspondence + 17 double sums per lane -> wave -> workgroup -> one slab row),
 //                k_final (fixed-order sum of the slab), one pinned read-back, host solve.
+//   plane        (include/s4p_icp_plane.h) target normals, cell-ordered next to tgt: k_normals (estimated) or
+//                k_gather_normals (the caller's); per iteration k_match_plane (31 double sums) + k_final_plane, host solve.
 // No float or double atomics anywhere: every sum has a fixed order, so two calls return identical bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "s4p_icp.h"
+#include "s4p_icp_plane.h"
 
 namespace s4p_icp {
 
@@ -138,10 +141,14 @@ __global__ __launch_bounds__(kBlock) void k_gather_source(const float4* src, con
 // is skipped when its box (in double, widened by 1e-6 h for the rounding of the cell location) is farther than the running
 // best by a margin (factor 1 - 1e-5) that exceeds the rounding of any float d2 of a point inside it: such a point can
 // neither win nor tie.
-__device__ inline void nearest(const GridDev& g, float x, float y, float z, float d2max, float& best, uint32_t& bi, float4& bp) {
+// SLOT: also report the winner's cell-order position (the slot of its normal); the winner itself is the same.
+template <bool SLOT>
+__device__ inline void nearest_t(const GridDev& g, float x, float y, float z, float d2max, float& best, uint32_t& bi, float4& bp,
+                                 uint32_t& slot) {
   best = d2max;
   bi = 0xFFFFFFFFu;
   bp = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (SLOT) slot = 0;
   const double fx = cell_coord(x, g.ox, g.inv_h), fy = cell_coord(y, g.oy, g.inv_h), fz = cell_coord(z, g.oz, g.inv_h);
   // NaN fails every comparison; a query more than one cell outside the grid has no neighbour cell inside it
   if (!(fx >= -1.0 && fx <= double(g.nx) && fy >= -1.0 && fy <= double(g.ny) && fz >= -1.0 && fz <= double(g.nz))) return;
@@ -165,9 +172,17 @@ __device__ inline void nearest(const GridDev& g, float x, float y, float z, floa
       const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
       const float d2 = dx * dx + (dy * dy + dz * dz);
       const uint32_t i = __float_as_uint(p.w);
-      if (d2 < best || (d2 == best && i < bi)) { best = d2; bi = i; bp = p; }
+      if (d2 < best || (d2 == best && i < bi)) {
+        best = d2; bi = i; bp = p;
+        if (SLOT) slot = k;
+      }
     }
   }
+}
+
+__device__ inline void nearest(const GridDev& g, float x, float y, float z, float d2max, float& best, uint32_t& bi, float4& bp) {
+  uint32_t unused;
+  nearest_t<false>(g, x, y, z, d2max, best, bi, bp, unused);
 }
 
 
@@ -260,6 +275,207 @@ __global__ __launch_bounds__(kBlock) void k_apply_icp(Tf T, float* x, float* y, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// point-to-plane (include/s4p_icp_plane.h): target normals as a cell-ordered float4 array next to tgt (w unused)
+
+constexpr int kPlanePitch = 32;             // doubles per plane slab row (31 used)
+constexpr int kJacobiSweeps = 64;           // as jacobi4
+
+// Cyclic Jacobi on a symmetric N x N matrix: A <- V^T A V (eigenvalues on the diagonal), V orthonormal.  Fully unrolled
+// inner loops, so that on the device every index is a constant and A, V stay in registers.
+template <int N>
+__host__ __device__ inline void jacobi_sym(double (&A)[N][N], double (&V)[N][N]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+    double off = 0.0, diag = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      diag += A[i][i] * A[i][i];
+#pragma unroll
+      for (int j = i + 1; j < N; ++j) off += A[i][j] * A[i][j];
+    }
+    if (off == 0.0 || off <= 1e-36 * diag) break;
+#pragma unroll
+    for (int p = 0; p < N - 1; ++p)
+#pragma unroll
+      for (int q = p + 1; q < N; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
+        }
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+}
+
+// Normal of every target point, one lane per point in cell order: the neighbours within r (float d2 <= r2, the point
+// itself included) in the 27 cells around it (r <= d < cell edge), cells pruned by box distance with nearest()'s margin.
+// Covariance in double, eigenvector of the smallest eigenvalue (first on ties), largest component positive.
+__global__ __launch_bounds__(kBlock) void k_normals(GridDev g, uint64_t n, float r2, int32_t min_nb, float4* nrm) {
+  const double eps = 1e-6 * g.h;
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) {
+    const float4 p = g.tgt[k];
+    const int cx = int(cell_coord(p.x, g.ox, g.inv_h)), cy = int(cell_coord(p.y, g.oy, g.inv_h)), cz = int(cell_coord(p.z, g.oz, g.inv_h));
+    const double qx = double(p.x), qy = double(p.y), qz = double(p.z);
+    double se[3] = {0.0, 0.0, 0.0}, see[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};    // sum e; sum e e^T (xx xy xz yy yz zz)
+    int32_t cnt = 0;
+    for (int t = 0; t < 27; ++t) {
+      const int ix = cx + t % 3 - 1, iy = cy + (t / 3) % 3 - 1, iz = cz + t / 9 - 1;
+      if (ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny || iz < 0 || iz >= g.nz) continue;
+      const double bx0 = g.ox + ix * g.h, by0 = g.oy + iy * g.h, bz0 = g.oz + iz * g.h;
+      const double ex = fmax(0.0, fmax(bx0 - qx, qx - (bx0 + g.h)) - eps);
+      const double ey = fmax(0.0, fmax(by0 - qy, qy - (by0 + g.h)) - eps);
+      const double ez = fmax(0.0, fmax(bz0 - qz, qz - (bz0 + g.h)) - eps);
+      if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(r2)) continue;
+      const uint32_t c = (uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix);
+      const uint32_t b = g.start[c], e = g.start[c + 1];
+      for (uint32_t j = b; j < e; ++j) {
+        const float4 o = g.tgt[j];
+        const float dx = p.x - o.x, dy = p.y - o.y, dz = p.z - o.z;
+        if (dx * dx + (dy * dy + dz * dz) > r2) continue;
+        const double e0 = double(o.x) - qx, e1 = double(o.y) - qy, e2 = double(o.z) - qz;
+        ++cnt;
+        se[0] += e0; se[1] += e1; se[2] += e2;
+        see[0] += e0 * e0; see[1] += e0 * e1; see[2] += e0 * e2; see[3] += e1 * e1; see[4] += e1 * e2; see[5] += e2 * e2;
+      }
+    }
+    float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (cnt >= min_nb) {
+      const double kk = double(cnt);
+      const double m0 = se[0] / kk, m1 = se[1] / kk, m2 = se[2] / kk;
+      double C[3][3], V[3][3];
+      C[0][0] = see[0] / kk - m0 * m0; C[0][1] = see[1] / kk - m0 * m1; C[0][2] = see[2] / kk - m0 * m2;
+      C[1][1] = see[3] / kk - m1 * m1; C[1][2] = see[4] / kk - m1 * m2; C[2][2] = see[5] / kk - m2 * m2;
+      C[1][0] = C[0][1]; C[2][0] = C[0][2]; C[2][1] = C[1][2];
+      jacobi_sym<3>(C, V);
+      int best = 0;
+      if (C[1][1] < C[best][best]) best = 1;
+      if (C[2][2] < (best == 0 ? C[0][0] : C[1][1])) best = 2;
+      double v0 = best == 0 ? V[0][0] : (best == 1 ? V[0][1] : V[0][2]);
+      double v1 = best == 0 ? V[1][0] : (best == 1 ? V[1][1] : V[1][2]);
+      double v2 = best == 0 ? V[2][0] : (best == 1 ? V[2][1] : V[2][2]);
+      const double nv = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+      v0 /= nv; v1 /= nv; v2 /= nv;
+      const double a0 = fabs(v0), a1 = fabs(v1), a2 = fabs(v2);
+      const double lead = (a0 >= a1 && a0 >= a2) ? v0 : (a1 >= a2 ? v1 : v2);
+      if (lead < 0.0) { v0 = -v0; v1 = -v1; v2 = -v2; }
+      out = make_float4(float(v0), float(v1), float(v2), 0.f);
+    }
+    nrm[k] = out;
+  }
+}
+
+// caller normals (uploaded order, already normalised) -> cell order, and back
+__global__ __launch_bounds__(kBlock) void k_gather_normals(const float* x, const float* y, const float* z, const float4* tgt, uint64_t n,
+                                                           float4* nrm) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t i = __float_as_uint(tgt[k].w);
+    nrm[k] = make_float4(x[i], y[i], z[i], 0.f);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_scatter_normals(const float4* nrm, const float4* tgt, uint64_t n, float* x, float* y, float* z) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t i = __float_as_uint(tgt[k].w);
+    const float4 v = nrm[k];
+    x[i] = v.x; y[i] = v.y; z[i] = v.z;
+  }
+}
+
+struct PlaneArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;
+  const float4* nrm;        // cell order, as g.tgt
+  uint64_t n;
+  float d2max;
+  double* slab;             // one kPlanePitch row per workgroup
+};
+
+// The point-to-plane hot path: k_match's correspondence (nearest_t reports the winner's slot, where its normal lies), then
+// 31 double sums in registers -> wave butterfly -> LDS over the waves -> one slab row.
+__global__ __launch_bounds__(kBlock) void k_match_plane(PlaneArgs A) {
+  double s[S4P_ICP_PLANE_NSUMS];
+#pragma unroll
+  for (int k = 0; k < S4P_ICP_PLANE_NSUMS; ++k) s[k] = 0.0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    float best;
+    uint32_t bi, slot;
+    float4 p;
+    nearest_t<true>(A.g, x, y, z, A.d2max, best, bi, p, slot);
+    if (bi == 0xFFFFFFFFu) continue;
+    s[0] += 1.0;
+    s[1] += double(best);
+    const float4 nf = A.nrm[slot];
+    if (nf.x == 0.f && nf.y == 0.f && nf.z == 0.f) continue;
+    const double qd[3] = {double(x), double(y), double(z)}, nd[3] = {double(nf.x), double(nf.y), double(nf.z)};
+    const double a[6] = {qd[1] * nd[2] - qd[2] * nd[1], qd[2] * nd[0] - qd[0] * nd[2], qd[0] * nd[1] - qd[1] * nd[0], nd[0], nd[1], nd[2]};
+    const double r = ((double(p.x) - qd[0]) * nd[0] + (double(p.y) - qd[1]) * nd[1]) + (double(p.z) - qd[2]) * nd[2];
+    s[2] += 1.0;
+    s[3] += r * r;
+    int o = 4;
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+      for (int v = u; v < 6; ++v) s[o++] += a[u] * a[v];
+#pragma unroll
+    for (int u = 0; u < 6; ++u) s[25 + u] += a[u] * r;
+  }
+  __shared__ double red[kBlock / 64][S4P_ICP_PLANE_NSUMS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < S4P_ICP_PLANE_NSUMS; ++k) {
+    double v = s[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < S4P_ICP_PLANE_NSUMS) {
+    double v = red[0][threadIdx.x];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][threadIdx.x];
+    A.slab[uint64_t(blockIdx.x) * kPlanePitch + threadIdx.x] = v;
+  }
+}
+
+// the plane slab's nb rows -> 31 sums, in a fixed order: 8 parts per column (rows part, part + 8, ...), then the parts in order
+__global__ __launch_bounds__(kBlock) void k_final_plane(const double* slab, int nb, double* out) {
+  constexpr int kParts = kBlock / S4P_ICP_PLANE_NSUMS;     // 8
+  __shared__ double part[kParts][S4P_ICP_PLANE_NSUMS];
+  const int col = threadIdx.x % S4P_ICP_PLANE_NSUMS, prt = threadIdx.x / S4P_ICP_PLANE_NSUMS;
+  if (prt < kParts) {
+    double v = 0.0;
+    for (int r = prt; r < nb; r += kParts) v += slab[uint64_t(r) * kPlanePitch + col];
+    part[prt][col] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < S4P_ICP_PLANE_NSUMS) {
+    double v = part[0][threadIdx.x];
+    for (int p = 1; p < kParts; ++p) v += part[p][threadIdx.x];
+    out[threadIdx.x] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // host: Horn's closed form.  N (4x4 symmetric) from the centred cross-covariance; its eigenvector of the largest
 // eigenvalue (cyclic Jacobi) is the unit quaternion of the rotation.
 void jacobi4(double A[4][4], double V[4][4]) {
@@ -337,11 +553,16 @@ struct s4p_icp_ctx {
   double* slab = nullptr;
   double* dsum = nullptr;
   double* hsum = nullptr;            // pinned
+  float4* nrm = nullptr;             // target normals, cell order (point-to-plane)
+  bool has_normals = false;
+  double* pslab = nullptr;           // plane slab: kMaxBlocks rows of kPlanePitch
 };
 
 namespace {
 
 std::string g_create_error;
+constexpr int kSumsCap = S4P_ICP_PLANE_NSUMS;       // dsum / hsum hold the 17 point or the 31 plane sums
+static_assert(S4P_ICP_PLANE_NSUMS >= S4P_ICP_NSUMS, "sum buffers");
 
 int32_t fail(s4p_icp_ctx* h, int32_t code, const std::string& msg) {
   h->err = msg;
@@ -392,6 +613,8 @@ int32_t set_target_impl(s4p_icp_ctx* h, const float* x, const float* y, const fl
   if (!(d > 0.f) || !std::isfinite(d)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: max_distance must be finite and > 0");
   ICP_HIP(hipSetDevice(h->device));
   h->has_target = false;
+  h->has_normals = false;
+  dfree(h->nrm); h->nrm = nullptr;
   dfree(h->tgt); h->tgt = nullptr;
   dfree(h->start); h->start = nullptr;
   Scratch S;
@@ -526,10 +749,139 @@ int32_t pass(s4p_icp_ctx* h, const Tf& T, const float4* src, int32_t* idx_dev, f
   return S4P_ICP_OK;
 }
 
+// one point-to-plane pass over `src` for T: the 31 sums on the host
+int32_t plane_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double* out) {
+  if (!h->pslab) ICP_HIP(hipMalloc((void**)&h->pslab, size_t(kMaxBlocks) * kPlanePitch * sizeof(double)));
+  PlaneArgs A;
+  A.T = T; A.g = h->g; A.src = src; A.nrm = h->nrm; A.n = uint64_t(h->n_q); A.d2max = h->d2max; A.slab = h->pslab;
+  const int nb = blocks_for(h->n_q);
+  hipLaunchKernelGGL(k_match_plane, dim3(nb), dim3(kBlock), 0, h->st, A);
+  ICP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_final_plane, dim3(1), dim3(kBlock), 0, h->st, (const double*)h->pslab, nb, h->dsum);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(h->hsum, h->dsum, S4P_ICP_PLANE_NSUMS * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipEventRecord(h->ev, h->st));
+  ICP_HIP(hipEventSynchronize(h->ev));
+  std::memcpy(out, h->hsum, S4P_ICP_PLANE_NSUMS * sizeof(double));
+  return S4P_ICP_OK;
+}
+
+int32_t plane_ready(s4p_icp_ctx* h) {
+  if (int32_t rc = ready(h)) return rc;
+  if (!h->has_normals) return fail(h, S4P_ICP_ERR_STATE, "target normals first (set_target_normals or estimate_normals)");
+  return S4P_ICP_OK;
+}
+
+int32_t alloc_normals(s4p_icp_ctx* h) {
+  h->has_normals = false;
+  if (!h->nrm) ICP_HIP(hipMalloc((void**)&h->nrm, size_t(h->n_p) * sizeof(float4)));
+  return S4P_ICP_OK;
+}
+
+// caller normals in the uploaded order (host): normalised in double, rounded to float; zero or non-finite -> (0, 0, 0)
+int32_t set_normals_host(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz) {
+  const size_t n = size_t(h->n_p);
+  std::vector<float> v[3];
+  for (int a = 0; a < 3; ++a) v[a].assign(n, 0.f);
+  for (size_t i = 0; i < n; ++i) {
+    const double x = nx[i], y = ny[i], z = nz[i];
+    const double len = std::sqrt(x * x + y * y + z * z);
+    if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z) || !(len > 0.0) || !std::isfinite(len)) continue;
+    v[0][i] = float(x / len); v[1][i] = float(y / len); v[2][i] = float(z / len);
+  }
+  if (int32_t rc = alloc_normals(h)) return rc;
+  Scratch S;
+  float* d[3];
+  for (int a = 0; a < 3; ++a) {
+    ICP_HIP(S.alloc((void**)&d[a], n * sizeof(float)));
+    ICP_HIP(hipMemcpyAsync(d[a], v[a].data(), n * sizeof(float), hipMemcpyHostToDevice, h->st));
+  }
+  hipLaunchKernelGGL(k_gather_normals, dim3(blocks_for(h->n_p)), dim3(kBlock), 0, h->st, d[0], d[1], d[2], (const float4*)h->tgt,
+                     uint64_t(n), h->nrm);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipStreamSynchronize(h->st));
+  h->has_normals = true;
+  return S4P_ICP_OK;
+}
+
+// refine's source: as uploaded, or (order_source) in the cell order of its T0-image, so that a wave's lanes read
+// neighbouring cells
+int32_t source_for(s4p_icp_ctx* h, const s4p_icp_params& P, const double* T, const float4** src) {
+  *src = h->src;
+  if (!P.order_source) return S4P_ICP_OK;
+  Scratch S;
+  const uint64_t un = uint64_t(h->n_q);
+  uint32_t *keys, *vals, *keys2, *vals2;
+  ICP_HIP(S.alloc((void**)&keys, un * 4)); ICP_HIP(S.alloc((void**)&vals, un * 4));
+  ICP_HIP(S.alloc((void**)&keys2, un * 4)); ICP_HIP(S.alloc((void**)&vals2, un * 4));
+  const int nb = blocks_for(h->n_q);
+  hipLaunchKernelGGL(k_source_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, un, to_float(T), h->g, keys, vals);
+  ICP_HIP(hipGetLastError());
+  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell)) return rc;
+  hipLaunchKernelGGL(k_gather_source, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, (const uint32_t*)vals2, un, h->src_ord);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipStreamSynchronize(h->st));
+  *src = h->src_ord;
+  return S4P_ICP_OK;
+}
+
 Tf centred_from_float16(const float* T16) {
   Tf f;
   for (int k = 0; k < 12; ++k) f.m[k] = T16[k];
   return f;
+}
+
+}  // namespace
+
+namespace {
+
+// The refine loop of both metrics.  plane: the 31 plane sums (sum d2 at [1]) and s4p_icp_solve_plane, whose degenerate
+// system stops the loop with T_k; otherwise the 17 sums (sum d2 at [16]) and Horn's solve.
+int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result, bool plane) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_inout) return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: null transform");
+  s4p_icp_params P;
+  s4p_icp_default_params(&P);
+  if (params) P = *params;
+  if (P.max_iterations < 0 || P.min_correspondences < 0 || !(P.rel_tol >= 0.0))
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: negative max_iterations / min_correspondences / rel_tol");
+  if (int32_t rc = plane ? plane_ready(h) : ready(h)) return rc;
+  s4p_icp_result R;
+  std::memset(&R, 0, sizeof(R));
+  double T[16], Tn[16], dT[16], sums[kSumsCap];
+  const int i_d2 = plane ? 1 : 16;
+  auto run_pass = [&](const float4* src) { return plane ? plane_pass(h, to_float(T), src, sums) : pass(h, to_float(T), src, nullptr, nullptr, sums); };
+  to_centred(T16_inout, h->c, T);
+  const float4* src = nullptr;
+  if (int32_t rc = source_for(h, P, T, &src)) return rc;
+  double prev = 0.0;
+  R.status = S4P_ICP_MAX_ITERATIONS;
+  for (int k = 0; k < P.max_iterations; ++k) {
+    if (int32_t rc = run_pass(src)) return rc;
+    const double n = sums[0];
+    const double rmse = n > 0.0 ? std::sqrt(sums[i_d2] / n) : 0.0;
+    if (k < S4P_ICP_HISTORY) { R.history_rmse[k] = rmse; R.history_n[k] = int64_t(n); R.history_len = k + 1; }
+    if (n < double(std::max(P.min_correspondences, 1))) { R.status = S4P_ICP_TOO_FEW; break; }
+    if (plane) {
+      if (s4p_icp_solve_plane(sums, dT) != S4P_ICP_OK) { R.status = S4P_ICP_DEGENERATE; break; }
+    } else {
+      s4p_icp_solve(sums, dT);
+    }
+    mat_mul4(dT, T, Tn);
+    std::memcpy(T, Tn, sizeof(T));
+    R.iterations = k + 1;
+    if (k + 1 == P.max_iterations) { R.status = S4P_ICP_MAX_ITERATIONS; break; }
+    if (k > 0 && std::fabs(rmse - prev) <= P.rel_tol * prev) { R.status = S4P_ICP_CONVERGED; break; }
+    prev = rmse;
+  }
+  // final pass: the statistics of the returned transform
+  if (int32_t rc = run_pass(src)) return rc;
+  R.n_corr = int64_t(sums[0]);
+  R.rmse = sums[0] > 0.0 ? std::sqrt(sums[i_d2] / sums[0]) : 0.0;
+  R.fitness = double(R.n_corr) / double(h->n_q);
+  from_centred(T, h->c, T16_inout);
+  if (result) *result = R;
+  return S4P_ICP_OK;
 }
 
 }  // namespace
@@ -566,8 +918,8 @@ int32_t s4p_icp_create(int32_t device, s4p_icp_ctx** out) {
   h->device = device;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess ||
       hipEventCreateWithFlags(&h->ev, hipEventDisableTiming) != hipSuccess ||
-      hipMalloc((void**)&h->dsum, S4P_ICP_NSUMS * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&h->hsum, S4P_ICP_NSUMS * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+      hipMalloc((void**)&h->dsum, kSumsCap * sizeof(double)) != hipSuccess ||
+      hipHostMalloc((void**)&h->hsum, kSumsCap * sizeof(double), hipHostMallocDefault) != hipSuccess) {
     g_create_error = "HIP stream / event / buffer creation failed";
     s4p_icp_destroy(h);
     return S4P_ICP_ERR_HIP;
@@ -580,7 +932,7 @@ void s4p_icp_destroy(s4p_icp_ctx* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->st) (void)hipStreamSynchronize(h->st);
-  dfree(h->tgt); dfree(h->start); dfree(h->src); dfree(h->src_ord); dfree(h->slab); dfree(h->dsum);
+  dfree(h->tgt); dfree(h->start); dfree(h->src); dfree(h->src_ord); dfree(h->slab); dfree(h->dsum); dfree(h->nrm); dfree(h->pslab);
   for (int a = 0; a < 3; ++a) dfree(h->qraw[a]);
   if (h->hsum) (void)hipHostFree(h->hsum);
   if (h->ev) (void)hipEventDestroy(h->ev);
@@ -665,58 +1017,7 @@ int32_t s4p_icp_solve(const double* sums, double* dT16) {
 }
 
 int32_t s4p_icp_refine(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
-  if (!h) return S4P_ICP_ERR_BAD_ARG;
-  if (!T16_inout) return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: null transform");
-  s4p_icp_params P;
-  s4p_icp_default_params(&P);
-  if (params) P = *params;
-  if (P.max_iterations < 0 || P.min_correspondences < 0 || !(P.rel_tol >= 0.0))
-    return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: negative max_iterations / min_correspondences / rel_tol");
-  if (int32_t rc = ready(h)) return rc;
-  s4p_icp_result R;
-  std::memset(&R, 0, sizeof(R));
-  double T[16], Tn[16], dT[16], sums[S4P_ICP_NSUMS];
-  to_centred(T16_inout, h->c, T);
-  const float4* src = h->src;
-  if (P.order_source) {            // visit the source in the cell order of its T0-image: a wave's lanes read neighbouring cells
-    Scratch S;
-    const uint64_t un = uint64_t(h->n_q);
-    uint32_t *keys, *vals, *keys2, *vals2;
-    ICP_HIP(S.alloc((void**)&keys, un * 4)); ICP_HIP(S.alloc((void**)&vals, un * 4));
-    ICP_HIP(S.alloc((void**)&keys2, un * 4)); ICP_HIP(S.alloc((void**)&vals2, un * 4));
-    const int nb = blocks_for(h->n_q);
-    hipLaunchKernelGGL(k_source_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, un, to_float(T), h->g, keys, vals);
-    ICP_HIP(hipGetLastError());
-    if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell)) return rc;
-    hipLaunchKernelGGL(k_gather_source, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, (const uint32_t*)vals2, un, h->src_ord);
-    ICP_HIP(hipGetLastError());
-    ICP_HIP(hipStreamSynchronize(h->st));
-    src = h->src_ord;
-  }
-  double prev = 0.0;
-  R.status = S4P_ICP_MAX_ITERATIONS;
-  for (int k = 0; k < P.max_iterations; ++k) {
-    if (int32_t rc = pass(h, to_float(T), src, nullptr, nullptr, sums)) return rc;
-    const double n = sums[0];
-    const double rmse = n > 0.0 ? std::sqrt(sums[16] / n) : 0.0;
-    if (k < S4P_ICP_HISTORY) { R.history_rmse[k] = rmse; R.history_n[k] = int64_t(n); R.history_len = k + 1; }
-    if (n < double(std::max(P.min_correspondences, 1))) { R.status = S4P_ICP_TOO_FEW; break; }
-    s4p_icp_solve(sums, dT);
-    mat_mul4(dT, T, Tn);
-    std::memcpy(T, Tn, sizeof(T));
-    R.iterations = k + 1;
-    if (k + 1 == P.max_iterations) { R.status = S4P_ICP_MAX_ITERATIONS; break; }
-    if (k > 0 && std::fabs(rmse - prev) <= P.rel_tol * prev) { R.status = S4P_ICP_CONVERGED; break; }
-    prev = rmse;
-  }
-  // final pass: the statistics of the returned transform
-  if (int32_t rc = pass(h, to_float(T), src, nullptr, nullptr, sums)) return rc;
-  R.n_corr = int64_t(sums[0]);
-  R.rmse = sums[0] > 0.0 ? std::sqrt(sums[16] / sums[0]) : 0.0;
-  R.fitness = double(R.n_corr) / double(h->n_q);
-  from_centred(T, h->c, T16_inout);
-  if (result) *result = R;
-  return S4P_ICP_OK;
+  return refine_impl(h, params, T16_inout, result, false);
 }
 
 int32_t s4p_icp_apply(s4p_icp_ctx* h, const double* T16, float* x, float* y, float* z, int64_t n) {
@@ -736,6 +1037,139 @@ int32_t s4p_icp_apply(s4p_icp_ctx* h, const double* T16, float* x, float* y, flo
   for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(io[a], p[a], size_t(n) * sizeof(float), hipMemcpyDeviceToHost, h->st));
   ICP_HIP(hipStreamSynchronize(h->st));
   return S4P_ICP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// point-to-plane (include/s4p_icp_plane.h)
+
+int32_t s4p_icp_set_target_normals(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return fail(h, S4P_ICP_ERR_STATE, "set_target_normals: set_target first");
+  if (!nx || !ny || !nz || n != h->n_p) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target_normals: null or not one per target point");
+  ICP_HIP(hipSetDevice(h->device));
+  return set_normals_host(h, nx, ny, nz);
+}
+
+int32_t s4p_icp_set_target_normals_device(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return fail(h, S4P_ICP_ERR_STATE, "set_target_normals: set_target first");
+  if (!nx || !ny || !nz || n != h->n_p) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target_normals: null or not one per target point");
+  ICP_HIP(hipSetDevice(h->device));
+  // normalised on the host, as for host input: both entry points store the same bits
+  std::vector<float> v[3];
+  const float* in[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a) {
+    v[a].resize(size_t(n));
+    ICP_HIP(hipMemcpy(v[a].data(), in[a], size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return set_normals_host(h, v[0].data(), v[1].data(), v[2].data());
+}
+
+int32_t s4p_icp_estimate_normals(s4p_icp_ctx* h, float radius, int32_t min_neighbours) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return fail(h, S4P_ICP_ERR_STATE, "estimate_normals: set_target first");
+  if (!(radius > 0.f) || !(radius <= h->d))
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "estimate_normals: radius must be in (0, max_distance]");
+  if (min_neighbours < 3) return fail(h, S4P_ICP_ERR_BAD_ARG, "estimate_normals: min_neighbours must be >= 3");
+  ICP_HIP(hipSetDevice(h->device));
+  if (int32_t rc = alloc_normals(h)) return rc;
+  hipLaunchKernelGGL(k_normals, dim3(blocks_for(h->n_p)), dim3(kBlock), 0, h->st, h->g, uint64_t(h->n_p), radius * radius, min_neighbours,
+                     h->nrm);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipStreamSynchronize(h->st));
+  h->has_normals = true;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_target_normals(s4p_icp_ctx* h, float* nx, float* ny, float* nz) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!nx || !ny || !nz) return fail(h, S4P_ICP_ERR_BAD_ARG, "target_normals: null argument");
+  if (!h->has_target || !h->has_normals) return fail(h, S4P_ICP_ERR_STATE, "target_normals: no normals");
+  ICP_HIP(hipSetDevice(h->device));
+  Scratch S;
+  const size_t n = size_t(h->n_p);
+  float* d[3];
+  for (int a = 0; a < 3; ++a) ICP_HIP(S.alloc((void**)&d[a], n * sizeof(float)));
+  hipLaunchKernelGGL(k_scatter_normals, dim3(blocks_for(h->n_p)), dim3(kBlock), 0, h->st, (const float4*)h->nrm, (const float4*)h->tgt,
+                     uint64_t(n), d[0], d[1], d[2]);
+  ICP_HIP(hipGetLastError());
+  float* out[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(out[a], d[a], n * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_plane_sums(s4p_icp_ctx* h, const float* T16_centred, double* sums) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "plane_sums: null argument");
+  if (int32_t rc = plane_ready(h)) return rc;
+  return plane_pass(h, centred_from_float16(T16_centred), h->src, sums);
+}
+
+int32_t s4p_icp_solve_plane(const double* sums, double* dT16) {
+  if (!sums || !dT16) return S4P_ICP_ERR_BAD_ARG;
+  if (!(sums[2] >= 6.0)) return S4P_ICP_ERR_DEGENERATE;
+  double A[6][6], b[6];
+  for (int u = 0, o = 4; u < 6; ++u)
+    for (int v = u; v < 6; ++v, ++o) A[u][v] = A[v][u] = sums[o];
+  for (int u = 0; u < 6; ++u) b[u] = sums[25 + u];
+  // balance the rotation block (length^2) against the translation block (unitless): the test below is unit-free
+  const double tw = A[0][0] + A[1][1] + A[2][2], tt = A[3][3] + A[4][4] + A[5][5];
+  if (!(tw > 0.0) || !(tt > 0.0) || !std::isfinite(tw) || !std::isfinite(tt)) return S4P_ICP_ERR_DEGENERATE;
+  const double sc = std::sqrt(tt / tw);
+  const double D[6] = {sc, sc, sc, 1.0, 1.0, 1.0};
+  double B[6][6], E[6][6], V[6][6], bb[6];
+  for (int u = 0; u < 6; ++u) {
+    bb[u] = D[u] * b[u];
+    for (int v = 0; v < 6; ++v) B[u][v] = E[u][v] = D[u] * A[u][v] * D[v];
+  }
+  jacobi_sym<6>(E, V);
+  double lmin = E[0][0], lmax = E[0][0];
+  for (int u = 1; u < 6; ++u) { lmin = std::min(lmin, E[u][u]); lmax = std::max(lmax, E[u][u]); }
+  if (!(lmin > 1e-10 * lmax)) return S4P_ICP_ERR_DEGENERATE;
+  // Cholesky B = L L^T, then B y = D b, x = D y
+  double L[6][6] = {};
+  for (int u = 0; u < 6; ++u)
+    for (int v = 0; v <= u; ++v) {
+      double acc = B[u][v];
+      for (int k = 0; k < v; ++k) acc -= L[u][k] * L[v][k];
+      if (u == v) {
+        if (!(acc > 0.0)) return S4P_ICP_ERR_DEGENERATE;
+        L[u][u] = std::sqrt(acc);
+      } else {
+        L[u][v] = acc / L[v][v];
+      }
+    }
+  double y[6], x[6];
+  for (int u = 0; u < 6; ++u) {
+    double acc = bb[u];
+    for (int k = 0; k < u; ++k) acc -= L[u][k] * y[k];
+    y[u] = acc / L[u][u];
+  }
+  for (int u = 5; u >= 0; --u) {
+    double acc = y[u];
+    for (int k = u + 1; k < 6; ++k) acc -= L[k][u] * x[k];
+    x[u] = acc / L[u][u];
+  }
+  for (int u = 0; u < 6; ++u) x[u] *= D[u];
+  // exact rotation of omega (Rodrigues): R = I + sin(th)/th K + (1 - cos(th))/th^2 K^2, K = [omega]x, K^2 = w w^T - th^2 I
+  const double w[3] = {x[0], x[1], x[2]};
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(th2);
+  const double c1 = th > 0.0 ? std::sin(th) / th : 1.0;
+  const double sh = th > 0.0 ? std::sin(0.5 * th) / th : 0.5;
+  const double c2 = 2.0 * sh * sh;                                  // (1 - cos th) / th^2 without cancellation
+  const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) dT16[4 * r + c] = (r == c ? 1.0 : 0.0) + c1 * K[r][c] + c2 * (w[r] * w[c] - (r == c ? th2 : 0.0));
+    dT16[4 * r + 3] = x[3 + r];
+  }
+  dT16[12] = dT16[13] = dT16[14] = 0.0;
+  dT16[15] = 1.0;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_refine_plane(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
+  return refine_impl(h, params, T16_inout, result, true);
 }
 
 }  // extern "C"
