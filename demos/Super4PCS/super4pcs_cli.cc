@@ -5,8 +5,12 @@
 //   Super4PCS -i P.obj Q.obj [-o overlap] [-d delta] [-n samples] [-t seconds] [-a normal_deg] [-c colour]
 //             [-r registered_geometry] [-m polyworks_matrix] [--sampled1 file] [--sampled2 file]
 //             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane] [--icp-normal-radius r]
+//             [--estimate-normals k] [--estimate-normals-radius r]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
+// --estimate-normals k gives both inputs k-nearest-neighbour normals (algorithms/normals.h, within r if given) before the
+// matcher runs, replacing the normals read from the files for matching only (-r writes the files' own): -a then filters on
+// them, and --icp-metric plane uses P's when all of them are nonzero.
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
@@ -14,6 +18,7 @@
 #include <vector>
 
 #include "super4pcs/algorithms/icp.h"
+#include "super4pcs/algorithms/normals.h"
 #include "super4pcs/algorithms/super4pcs.h"
 #include "super4pcs/io/io.h"
 #include "super4pcs/utils/geometry.h"
@@ -75,6 +80,14 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
   Match4PCSBase::MatrixType mat = Match4PCSBase::MatrixType::Identity();
   float score = 0.f;
   try {
+    if (opt.normals_k > 0) {
+      NormalEstimationOptions nopt;
+      nopt.k = opt.normals_k;
+      nopt.radius = opt.normals_radius;
+      EstimateNormals(P.points, nopt);
+      EstimateNormals(Q.points, nopt);
+      log.Log<Utils::Verbose>("Estimated normals: k ", opt.normals_k, ", radius ", opt.normals_radius);
+    }
     MatchSuper4PCS matcher(mopt, log);
     log.Log<Utils::Verbose>("Use Super4PCS");
     score = matcher.ComputeTransformation(P.points, &Q.points, mat, Sampling::UniformDistSampler(), Progress());

@@ -26,6 +26,9 @@ struct Options {
   double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
   bool icp_plane = false;                                    // --icp-metric point|plane  (default point)
   double icp_normal_radius = -1;                             // --icp-normal-radius  (default: the ICP max distance)
+  int normals_k = 0;                                         // --estimate-normals k  normals of both inputs on the device (0: off)
+  double normals_radius = -1;                                // --estimate-normals-radius r  (default: unbounded)
+  bool normals_radius_set = false;
   bool bad_value = false;                                    // a flag's value does not parse
 };
 
@@ -72,6 +75,17 @@ inline const Flag* flag_table(size_t* n) {
          const double r = std::strtod(v[0], &end);
          if (end == v[0] || *end != '\0' || !(r > 0) || !std::isfinite(r)) o.bad_value = true; else o.icp_normal_radius = r;
        }},
+      {"--estimate-normals", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long k = std::strtol(v[0], &end, 10);
+         if (end == v[0] || *end != '\0' || k < 3 || k > 32) o.bad_value = true; else o.normals_k = int(k);
+       }},
+      {"--estimate-normals-radius", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double r = std::strtod(v[0], &end);
+         o.normals_radius_set = true;
+         if (end == v[0] || *end != '\0' || !(r > 0) || !(r < 3.0e38)) o.bad_value = true; else o.normals_radius = r;
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -94,6 +108,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
     i += hit->values;
   }
   if (o.bad_value) return Parse::Bad;
+  if (o.normals_radius_set && o.normals_k == 0) return Parse::Bad;    // the radius needs --estimate-normals
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -110,6 +125,9 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
   std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
   std::fprintf(stderr, "\t[ --icp-metric point|plane (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
+  std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
+  std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
+  std::fprintf(stderr, "\t     them and --icp-metric plane uses P's when all are nonzero)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

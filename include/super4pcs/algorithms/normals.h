@@ -1,0 +1,55 @@
+// EstimateNormals: k-nearest-neighbour normals of a whole cloud on the MI355X, through the C ABI of libsuper4pcs_normals.so
+// (include/s4p_normals.h).  The matcher's pair filter (Match4PCSOptions::max_normal_difference, -a) and point-to-plane ICP
+// (ICPMetric::PointToPlane) read Point3D::normal(); this fills it for clouds that carry none.
+// Link with -lsuper4pcs_normals.  Builds with and without Eigen, like the rest of the facade.
+//
+//   NormalEstimationOptions nopt;  nopt.k = 16;
+//   EstimateNormals(P, nopt);  EstimateNormals(Q, nopt);      // then options.max_normal_difference filters on them
+#ifndef S4P_FACADE_NORMALS_H_
+#define S4P_FACADE_NORMALS_H_
+
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "s4p_normals.h"
+#include "super4pcs/shared4pcs.h"
+
+namespace GlobalRegistration {
+
+struct NormalEstimationOptions {
+  int k = 16;                       // neighbours, 3..32 (the point itself included)
+  double radius = -1;               // > 0: only neighbours within radius ("hybrid"); <= 0: unbounded
+  int device = 0;
+};
+
+// Sets every point's normal() (Point3D::set_normal) to its estimated, unoriented normal; (0, 0, 0), "no normal", where
+// fewer than 3 neighbours qualify or they all coincide.  Replaces any normal the points had.  Throws std::runtime_error
+// when there is no device (no CPU fallback) and std::invalid_argument when an option is outside its limits.
+inline void EstimateNormals(std::vector<Point3D>& cloud, const NormalEstimationOptions& options) {
+  if (cloud.empty()) return;
+  if (options.k < S4P_NORMALS_MIN_K || options.k > S4P_NORMALS_MAX_K) throw std::invalid_argument("EstimateNormals: k must be in [3, 32]");
+  if (!(options.radius == options.radius) || options.radius > 3.0e38) throw std::invalid_argument("EstimateNormals: radius must be finite");
+  struct Handle {
+    s4p_normals_ctx* h = nullptr;
+    ~Handle() { s4p_normals_destroy(h); }
+    void check(int32_t rc) const {
+      if (rc != S4P_NORMALS_OK) throw std::runtime_error(std::string("EstimateNormals (MI355X): ") + s4p_normals_last_error(h));
+    }
+  } H;
+  if (s4p_normals_create(options.device, &H.h) != S4P_NORMALS_OK)
+    throw std::runtime_error(std::string("EstimateNormals (MI355X): ") + s4p_normals_last_error(nullptr));
+  std::vector<float> c[3];
+  for (int a = 0; a < 3; ++a) c[a].resize(cloud.size());
+  for (size_t i = 0; i < cloud.size(); ++i) { c[0][i] = cloud[i].x(); c[1][i] = cloud[i].y(); c[2][i] = cloud[i].z(); }
+  H.check(s4p_normals_set_cloud(H.h, c[0].data(), c[1].data(), c[2].data(), int64_t(cloud.size())));
+  std::vector<float> out(3 * cloud.size());
+  H.check(s4p_normals_estimate(H.h, options.k, float(options.radius), out.data()));
+  for (size_t i = 0; i < cloud.size(); ++i) {
+    cloud[i].set_normal(Point3D::VectorType(out[3 * i], out[3 * i + 1], out[3 * i + 2]));
+  }
+}
+
+}  // namespace GlobalRegistration
+#endif

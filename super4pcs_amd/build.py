@@ -128,24 +128,50 @@ def build_icp(force=False, verbose=False):
     return ICP_LIB
 
 
+NORMALS_SRC = os.path.join(_HERE, "normals_src")
+NORMALS_LIB = os.path.join(LIBDIR, "libsuper4pcs_normals.so")
+NORMALS_SOURCES = ["s4p_normals.hip"]
+
+
+def build_normals(force=False, verbose=False, extra_flags=()):
+    """lib/libsuper4pcs_normals.so: k-nearest-neighbour normal estimation (normals_src/, include/s4p_normals.h), a library of
+    its own so that the main and the ICP libraries stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off);
+    it needs only the HIP runtime and the hipCUB headers."""
+    deps = [os.path.join(NORMALS_SRC, f) for f in os.listdir(NORMALS_SRC)] + [os.path.join(ROOT, "include", "s4p_normals.h")]
+    if not force and not extra_flags and os.path.exists(NORMALS_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(NORMALS_LIB)
+                                                                             for d in deps):
+        return NORMALS_LIB
+    os.makedirs(LIBDIR, exist_ok=True)
+    cmd = [_hipcc()] + HIPCC_FLAGS + list(extra_flags) + ["-I" + os.path.join(ROOT, "include"), "-I" + NORMALS_SRC]
+    for s in NORMALS_SOURCES:
+        cmd += ["-x", "hip", os.path.join(NORMALS_SRC, s)]
+    cmd += ["-o", NORMALS_LIB]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.check_call(cmd)
+    return NORMALS_LIB
+
+
 BINDIR = os.path.join(_HERE, "bin")
 CLI = os.path.join(BINDIR, "Super4PCS")
 CLI_SRC = os.path.join(ROOT, "demos", "Super4PCS", "super4pcs_cli.cc")
 
 
 def build_cli(force=False):
-    """The command-line program (demos/Super4PCS) against the facade headers and the library: plain host C++."""
+    """The command-line program (demos/Super4PCS) against the facade headers and the libraries: plain host C++."""
     build()
     build_icp(force=force)
-    deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB, ICP_LIB,
+    build_normals(force=force)
+    deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB, ICP_LIB, NORMALS_LIB,
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp.h"),
+            os.path.join(ROOT, "include", "super4pcs", "algorithms", "normals.h"),
             os.path.join(ROOT, "include", "super4pcs", "io", "io.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "match4pcsBase.h")]
     if not force and os.path.exists(CLI) and all(os.path.getmtime(d) <= os.path.getmtime(CLI) for d in deps):
         return CLI
     os.makedirs(BINDIR, exist_ok=True)
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-I" + os.path.join(ROOT, "include"), CLI_SRC,
-           "-L" + LIBDIR, "-lsuper4pcs_amd", "-lsuper4pcs_icp", "-Wl,-rpath,$ORIGIN/../lib", "-o", CLI]
+           "-L" + LIBDIR, "-lsuper4pcs_amd", "-lsuper4pcs_icp", "-lsuper4pcs_normals", "-Wl,-rpath,$ORIGIN/../lib", "-o", CLI]
     subprocess.check_call(cmd)
     return CLI
 
@@ -153,4 +179,5 @@ def build_cli(force=False):
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_icp(force="--force" in sys.argv, verbose=True))
+    print(build_normals(force="--force" in sys.argv, verbose=True))
     print(build_cli(force="--force" in sys.argv))

@@ -1,0 +1,684 @@
+// s4p_normals.hip -- libsuper4pcs_normals.so: k-nearest-neighbour normal estimation of whole clouds (include/s4p_normals.h,
+// DESIGN.md section "Normal estimation").  One translation unit: device kernels (namespace s4p_nrm) and the C ABI.
+//
+// Device path:
+//   set_cloud   k_pack (SoA -> caller-order float4 x, y, z, index bits) -> k_bounds (per-block float minima / maxima) ->
+//               k_gather_samples + k_spacing_hist (a histogram of d2 around 64 seeded sample points: the cell edge is their
+//               median 16th-neighbour distance) -> k_cell_keys -> radix sort of (cell, index) -> k_cell_ranges + k_gather:
+//               the cloud as cell-ordered float4 and the [begin, end) of every cell.
+//   estimate    queries in cell order (the cloud itself, or k_cell_keys + sort + k_gather of the caller's queries) ->
+//               k_knn_normals<K>: one lane per query, ring search with conservative box pruning, the k best (d2, index)
+//               sorted in registers, covariance in double, 3x3 Jacobi, the normal scattered to the caller's order.
+// No float or double atomics: every sum has a fixed order, so two calls return identical bits.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "s4p_normals.h"
+
+namespace s4p_nrm {
+
+constexpr int kBlock = 256;
+constexpr int kMaxBlocks = 2048;
+constexpr uint64_t kMaxCells = 1ull << 28;
+constexpr int kPlanK = 16;                  // the cell edge follows the distance to the 16th neighbour
+constexpr int kSamples = 64;                // seeded sample points of the spacing estimate
+constexpr int kBinLo = 252;                 // spacing histogram: 4 bins per octave of d2 / L^2 in [2^-64, 2^-10)
+constexpr int kBins = 216;                  //   (bin = (float bits >> 21) - kBinLo; below 2^-64, 0 included, -> bin 0)
+constexpr int kJacobiSweeps = 64;
+
+struct GridDev {
+  double ox, oy, oz, h, inv_h;
+  int32_t nx, ny, nz;
+  const float4* pts;          // cell-ordered cloud: x, y, z, original index (bits)
+  const uint2* range;         // [begin, end) of every cell (0, 0 when empty)
+};
+
+__host__ __device__ inline double cell_coord(float x, double o, double inv_h) { return floor((double(x) - o) * inv_h); }
+
+inline int blocks_for(int64_t n) { return int(std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, kMaxBlocks))); }
+
+// caller SoA -> float4 (x, y, z, index bits)
+__global__ __launch_bounds__(kBlock) void k_pack(const float* x, const float* y, const float* z, uint64_t n, float4* out) {
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock)
+    out[i] = make_float4(x[i], y[i], z[i], __uint_as_float(uint32_t(i)));
+}
+
+// per-block float minima and maxima (rows of 6); NaN propagates through the finiteness check on the host
+__global__ __launch_bounds__(kBlock) void k_bounds(const float4* p, uint64_t n, float* rows) {
+  float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  bool bad = false;
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = p[i];
+    const float c[3] = {q.x, q.y, q.z};
+    for (int a = 0; a < 3; ++a) {
+      bad |= !isfinite(c[a]);
+      v[a] = fminf(v[a], c[a]); v[3 + a] = fmaxf(v[3 + a], c[a]);
+    }
+  }
+  if (bad) v[0] = NAN;
+  __shared__ float sh[kBlock];
+  for (int k = 0; k < 6; ++k) {
+    sh[threadIdx.x] = v[k];
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+      if (threadIdx.x < unsigned(w)) {
+        const float a = sh[threadIdx.x], b = sh[threadIdx.x + w];
+        sh[threadIdx.x] = (a != a || b != b) ? NAN : (k < 3 ? fminf(a, b) : fmaxf(a, b));
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) rows[blockIdx.x * 6 + k] = sh[0];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(64) void k_gather_samples(const float4* p, const uint32_t* idx, int s, float4* out) {
+  if (int(threadIdx.x) < s) out[threadIdx.x] = p[idx[threadIdx.x]];
+}
+
+// hist[s][bin]: points of the cloud whose d2 to sample s, scaled by 1 / L^2, falls in the bin (integer counts: any order of
+// the additions gives the same histogram)
+__global__ __launch_bounds__(kBlock) void k_spacing_hist(const float4* p, uint64_t n, const float4* samples, float inv_l2, uint32_t* hist) {
+  __shared__ uint32_t sh[kSamples * kBins];
+  __shared__ float4 sq[kSamples];
+  for (int t = threadIdx.x; t < kSamples * kBins; t += kBlock) sh[t] = 0u;
+  if (threadIdx.x < kSamples) sq[threadIdx.x] = samples[threadIdx.x];
+  __syncthreads();
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = p[i];
+    for (int s = 0; s < kSamples; ++s) {
+      const float dx = q.x - sq[s].x, dy = q.y - sq[s].y, dz = q.z - sq[s].z;
+      const float d2n = (dx * dx + (dy * dy + dz * dz)) * inv_l2;
+      const int b = int(__float_as_uint(d2n) >> 21) - kBinLo;
+      if (b < kBins) atomicAdd(&sh[s * kBins + max(b, 0)], 1u);
+    }
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < kSamples * kBins; t += kBlock)
+    if (sh[t]) atomicAdd(&hist[t], sh[t]);
+}
+
+// cell key of every point (clamped to the grid; a non-finite point -> ncell, sorted last); value = its position
+__global__ __launch_bounds__(kBlock) void k_cell_keys(const float4* p, uint64_t n, GridDev g, uint32_t* keys, uint32_t* vals) {
+  const uint32_t ncell = uint32_t(g.nx) * uint32_t(g.ny) * uint32_t(g.nz);
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = p[i];
+    uint32_t key = ncell;
+    if (isfinite(q.x) && isfinite(q.y) && isfinite(q.z)) {
+      const int ix = int(fmin(fmax(cell_coord(q.x, g.ox, g.inv_h), 0.0), double(g.nx - 1)));
+      const int iy = int(fmin(fmax(cell_coord(q.y, g.oy, g.inv_h), 0.0), double(g.ny - 1)));
+      const int iz = int(fmin(fmax(cell_coord(q.z, g.oz, g.inv_h), 0.0), double(g.nz - 1)));
+      key = (uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix);
+    }
+    keys[i] = key;
+    vals[i] = uint32_t(i);
+  }
+}
+
+// [begin, end) of every non-empty cell from the sorted keys (the range array is zeroed first)
+__global__ __launch_bounds__(kBlock) void k_cell_ranges(const uint32_t* keys, uint64_t n, uint2* range) {
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t c = keys[i];
+    if (i == 0 || keys[i - 1] != c) range[c].x = uint32_t(i);
+    if (i + 1 == n || keys[i + 1] != c) range[c].y = uint32_t(i + 1);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_gather(const float4* p, const uint32_t* order, uint64_t n, float4* out) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) out[k] = p[order[k]];
+}
+
+// points per non-empty cell, histogram capped at kOccBins - 1 (profiles only)
+constexpr int kOccBins = 4096;
+__global__ __launch_bounds__(kBlock) void k_occupancy(const uint2* range, uint64_t ncell, uint32_t* hist) {
+  for (uint64_t c = blockIdx.x * (uint64_t)kBlock + threadIdx.x; c < ncell; c += (uint64_t)gridDim.x * kBlock) {
+    const uint2 r = range[c];
+    if (r.y > r.x) atomicAdd(&hist[min(r.y - r.x, uint32_t(kOccBins - 1))], 1u);
+  }
+}
+
+// Cyclic Jacobi on a symmetric 3x3: A <- V^T A V (eigenvalues on the diagonal), V orthonormal.  Stop rule and rotation as
+// the ICP library's k_normals; fully unrolled, so A and V stay in registers.
+__device__ inline void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
+    const double diag = (A[0][0] * A[0][0] + A[1][1] * A[1][1]) + A[2][2] * A[2][2];
+    const double off = (A[0][1] * A[0][1] + A[0][2] * A[0][2]) + A[1][2] * A[1][2];
+    if (off == 0.0 || off <= 1e-36 * diag) break;
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = p + 1; q < 3; ++q) {
+        if (A[p][q] == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - s * akq; A[k][q] = s * akp + c * akq;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - s * aqk; A[q][k] = s * apk + c * aqk;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+}
+
+struct KnnArgs {
+  GridDev g;
+  const float4* qs;           // queries in cell order, w = output slot (bits)
+  uint64_t m;
+  const float4* pos;          // the cloud in the caller's order (covariance reads)
+  int32_t k;
+  float r2lim;                // fl(r*r), or +inf (unbounded)
+  float* out;                 // 3 floats per query, caller order
+};
+
+// (d2, index) as one 64-bit key whose unsigned order is the lexicographic order: d2 >= +0, so its float bits are monotone;
+// they are offset by one so that key 0 sorts before every candidate.
+__device__ inline uint64_t knn_key(float d2, uint32_t i) { return (uint64_t(__float_as_uint(d2)) + 1u) << 32 | i; }
+__device__ inline float key_d2(uint64_t key) { return key == ~0ull ? INFINITY : __uint_as_float(uint32_t(key >> 32) - 1u); }
+
+// One lane per query.  The list holds K keys in ascending order: K - k sentinels 0 in front that no candidate passes, then
+// the k best so far, padded with ~0.  Its last entry is the k-th best, the pruning bound.
+// Rings of cells around the query's (clamped) cell are visited in order R = 0, 1, ...; before ring R the search stops
+// when every cell outside the (2R - 1)^3 block already visited is farther than the bound, and inside a ring a cell is
+// skipped when its box is.  Box distances are in double, widened by 1e-6 h for the rounding of the cell location and
+// compared with a (1 - 1e-5) factor that exceeds the rounding of any float d2 (as the ICP library's nearest()): a skipped
+// point can neither enter the list nor tie with its last entry.
+template <int K>
+__global__ __launch_bounds__(kBlock) void k_knn_normals(KnnArgs A) {
+  const GridDev& g = A.g;
+  const double eps = 1e-6 * g.h;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.m; j += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = A.qs[j];
+    uint64_t L[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) L[t] = t < K - A.k ? 0ull : ~0ull;
+    const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+    const double qx = double(q.x), qy = double(q.y), qz = double(q.z);
+    if (finite) {
+      const int cx = int(fmin(fmax(cell_coord(q.x, g.ox, g.inv_h), 0.0), double(g.nx - 1)));
+      const int cy = int(fmin(fmax(cell_coord(q.y, g.oy, g.inv_h), 0.0), double(g.ny - 1)));
+      const int cz = int(fmin(fmax(cell_coord(q.z, g.oz, g.inv_h), 0.0), double(g.nz - 1)));
+      for (int R = 0;; ++R) {
+        if (R > 0) {
+          // the nearest face of the visited block beyond which cells remain
+          double lb = INFINITY;
+          bool more = false;
+          const int c3[3] = {cx, cy, cz}, d3[3] = {g.nx, g.ny, g.nz};
+          const double o3[3] = {g.ox, g.oy, g.oz}, q3[3] = {qx, qy, qz};
+#pragma unroll
+          for (int a = 0; a < 3; ++a) {
+            const int lo = c3[a] - R + 1, hi = c3[a] + R;
+            if (lo > 0) { more = true; lb = fmin(lb, q3[a] - (o3[a] + lo * g.h)); }
+            if (hi < d3[a]) { more = true; lb = fmin(lb, (o3[a] + hi * g.h) - q3[a]); }
+          }
+          if (!more) break;
+          lb -= eps;
+          if (lb > 0.0 && lb * lb * (1.0 - 1e-5) > double(fminf(A.r2lim, key_d2(L[K - 1])))) break;
+        }
+        const int z0 = max(cz - R, 0), z1 = min(cz + R, g.nz - 1), y0 = max(cy - R, 0), y1 = min(cy + R, g.ny - 1);
+        const int x0 = max(cx - R, 0), x1 = min(cx + R, g.nx - 1);
+        for (int iz = z0; iz <= z1; ++iz)
+          for (int iy = y0; iy <= y1; ++iy) {
+            const bool face = iz == cz - R || iz == cz + R || iy == cy - R || iy == cy + R;
+            const int step = face ? 1 : 2 * R;
+            for (int ix = face ? x0 : cx - R; ix <= x1; ix += step) {
+              if (ix < 0) continue;
+              const double bx0 = g.ox + ix * g.h, by0 = g.oy + iy * g.h, bz0 = g.oz + iz * g.h;
+              const double ex = fmax(0.0, fmax(bx0 - qx, qx - (bx0 + g.h)) - eps);
+              const double ey = fmax(0.0, fmax(by0 - qy, qy - (by0 + g.h)) - eps);
+              const double ez = fmax(0.0, fmax(bz0 - qz, qz - (bz0 + g.h)) - eps);
+              if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(fminf(A.r2lim, key_d2(L[K - 1])))) continue;
+              const uint2 rg = g.range[(uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix)];
+              for (uint32_t s = rg.x; s < rg.y; ++s) {
+                const float4 p = g.pts[s];
+                const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
+                const float d2 = dx * dx + (dy * dy + dz * dz);
+                uint64_t c = knn_key(d2, __float_as_uint(p.w));
+                if (!(d2 <= A.r2lim) || !(c < L[K - 1])) continue;
+                // insertion by one min / max pass: the list stays sorted and its largest key drops out
+#pragma unroll
+                for (int t = 0; t < K; ++t) {
+                  const uint64_t lo = c < L[t] ? c : L[t], hi = c < L[t] ? L[t] : c;
+                  L[t] = lo;
+                  c = hi;
+                }
+              }
+            }
+          }
+      }
+    }
+    // covariance in double, neighbours in ascending (d2, index) order
+    double se[3] = {0.0, 0.0, 0.0}, see[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int32_t cnt = 0;
+#pragma unroll
+    for (int t = 0; t < K; ++t) {
+      if (L[t] == 0ull || L[t] == ~0ull) continue;
+      const float4 p = A.pos[uint32_t(L[t])];
+      const double e0 = double(p.x) - qx, e1 = double(p.y) - qy, e2 = double(p.z) - qz;
+      ++cnt;
+      se[0] += e0; se[1] += e1; se[2] += e2;
+      see[0] += e0 * e0; see[1] += e0 * e1; see[2] += e0 * e2; see[3] += e1 * e1; see[4] += e1 * e2; see[5] += e2 * e2;
+    }
+    float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+    if (cnt >= 3) {
+      const double kk = double(cnt);
+      const double m0 = se[0] / kk, m1 = se[1] / kk, m2 = se[2] / kk;
+      double C[3][3], V[3][3];
+      C[0][0] = see[0] / kk - m0 * m0; C[0][1] = see[1] / kk - m0 * m1; C[0][2] = see[2] / kk - m0 * m2;
+      C[1][1] = see[3] / kk - m1 * m1; C[1][2] = see[4] / kk - m1 * m2; C[2][2] = see[5] / kk - m2 * m2;
+      C[1][0] = C[0][1]; C[2][0] = C[0][2]; C[2][1] = C[1][2];
+      const double tr = (C[0][0] + C[1][1]) + C[2][2];
+      if (tr > 0.0) {
+        jacobi3(C, V);
+        int best = 0;
+        if (C[1][1] < C[0][0]) best = 1;
+        if (C[2][2] < (best == 0 ? C[0][0] : C[1][1])) best = 2;
+        double v0 = best == 0 ? V[0][0] : (best == 1 ? V[0][1] : V[0][2]);
+        double v1 = best == 0 ? V[1][0] : (best == 1 ? V[1][1] : V[1][2]);
+        double v2 = best == 0 ? V[2][0] : (best == 1 ? V[2][1] : V[2][2]);
+        const double nv = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
+        v0 /= nv; v1 /= nv; v2 /= nv;
+        const double a0 = fabs(v0), a1 = fabs(v1), a2 = fabs(v2);
+        const double lead = (a0 >= a1 && a0 >= a2) ? v0 : (a1 >= a2 ? v1 : v2);
+        if (lead < 0.0) { v0 = -v0; v1 = -v1; v2 = -v2; }
+        n0 = float(v0); n1 = float(v1); n2 = float(v2);
+      }
+    }
+    const uint64_t o = 3ull * __float_as_uint(q.w);
+    A.out[o] = n0; A.out[o + 1] = n1; A.out[o + 2] = n2;
+  }
+}
+
+uint64_t splitmix64(uint64_t& s) {
+  uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+}  // namespace s4p_nrm
+
+using namespace s4p_nrm;
+
+struct s4p_normals_ctx {
+  int device = 0;
+  hipStream_t st = nullptr;
+  std::string err;
+  bool has_cloud = false;
+  int64_t n = 0;
+  GridDev g{};
+  uint64_t ncell = 0;
+  double spacing = 0.0;
+  float4* pos = nullptr;             // caller order
+  float4* pts = nullptr;             // cell order
+  uint2* range = nullptr;
+};
+
+namespace {
+
+std::string g_create_error;
+
+int32_t fail(s4p_normals_ctx* h, int32_t code, const std::string& msg) {
+  h->err = msg;
+  return code;
+}
+
+#define NRM_HIP(expr)                                                                                                     \
+  do {                                                                                                                    \
+    const hipError_t e_ = (expr);                                                                                         \
+    if (e_ != hipSuccess) return fail(h, e_ == hipErrorOutOfMemory ? S4P_NORMALS_ERR_OOM : S4P_NORMALS_ERR_HIP,          \
+                                      std::string(#expr) + ": " + hipGetErrorString(e_));                                \
+  } while (0)
+
+void dfree(void* p) { if (p) (void)hipFree(p); }
+
+struct Scratch {
+  std::vector<void*> ptrs;
+  ~Scratch() { for (void* p : ptrs) dfree(p); }
+  hipError_t alloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e == hipSuccess) ptrs.push_back(*p); else *p = nullptr;
+    return e;
+  }
+};
+
+int end_bit(uint64_t max_key) {
+  int b = 1;
+  while (b < 32 && (max_key >> b) != 0) ++b;
+  return b;
+}
+
+int32_t sort_pairs(s4p_normals_ctx* h, Scratch& S, const uint32_t* keys, uint32_t* keys_out, const uint32_t* vals, uint32_t* vals_out,
+                   uint64_t n, uint64_t max_key) {
+  size_t bytes = 0;
+  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
+  void* tmp = nullptr;
+  NRM_HIP(S.alloc(&tmp, bytes));
+  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
+  return S4P_NORMALS_OK;
+}
+
+constexpr int64_t kMaxPoints = int64_t(0x7FFFFFFE);
+
+// The cell edge: the median over kSamples seeded sample points of their distance to the kPlanK-th neighbour (the upper
+// edge of the histogram bin where the count, the point itself included, reaches kPlanK; at most L / 32).
+int32_t plan_spacing(s4p_normals_ctx* h, Scratch& S, const float4* pos, uint64_t n, const float lo[3], const float hi[3], double* spacing) {
+  double l2 = 0.0;
+  for (int a = 0; a < 3; ++a) l2 += (double(hi[a]) - double(lo[a])) * (double(hi[a]) - double(lo[a]));
+  const double L = std::sqrt(l2);
+  if (!(L > 0.0)) { *spacing = 0.0; return S4P_NORMALS_OK; }
+  uint32_t idx[kSamples];
+  uint64_t seed = 0x5334504E524D4C31ull;        // fixed: the plan, and so the grid, depend on the cloud alone
+  for (int s = 0; s < kSamples; ++s) idx[s] = uint32_t(splitmix64(seed) % n);
+  uint32_t *didx, *dhist;
+  float4* samp;
+  NRM_HIP(S.alloc((void**)&didx, sizeof(idx)));
+  NRM_HIP(S.alloc((void**)&samp, kSamples * sizeof(float4)));
+  NRM_HIP(S.alloc((void**)&dhist, kSamples * kBins * sizeof(uint32_t)));
+  NRM_HIP(hipMemcpyAsync(didx, idx, sizeof(idx), hipMemcpyHostToDevice, h->st));
+  NRM_HIP(hipMemsetAsync(dhist, 0, kSamples * kBins * sizeof(uint32_t), h->st));
+  hipLaunchKernelGGL(k_gather_samples, dim3(1), dim3(64), 0, h->st, pos, (const uint32_t*)didx, kSamples, samp);
+  NRM_HIP(hipGetLastError());
+  const float inv_l2 = float(1.0 / l2);
+  hipLaunchKernelGGL(k_spacing_hist, dim3(std::min(blocks_for(int64_t(n)), 512)), dim3(kBlock), 0, h->st, pos, n, (const float4*)samp,
+                     inv_l2, dhist);
+  NRM_HIP(hipGetLastError());
+  std::vector<uint32_t> hist(size_t(kSamples) * kBins);
+  NRM_HIP(hipMemcpyAsync(hist.data(), dhist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
+  NRM_HIP(hipStreamSynchronize(h->st));
+  std::vector<double> r(kSamples);
+  for (int s = 0; s < kSamples; ++s) {
+    uint64_t cum = 0;
+    r[s] = L / 32.0;
+    for (int b = 0; b < kBins; ++b) {
+      cum += hist[size_t(s) * kBins + b];
+      if (cum >= uint64_t(kPlanK)) {
+        uint32_t bits = uint32_t(b + kBinLo + 1) << 21;
+        float edge;
+        std::memcpy(&edge, &bits, 4);
+        r[s] = std::min(L / 32.0, std::sqrt(double(edge) / double(inv_l2)));
+        break;
+      }
+    }
+  }
+  std::sort(r.begin(), r.end());
+  *spacing = r[kSamples / 2];
+  return S4P_NORMALS_OK;
+}
+
+int32_t set_cloud_impl(s4p_normals_ctx* h, const float* x, const float* y, const float* z, int64_t n, hipMemcpyKind kind) {
+  if (!h) return S4P_NORMALS_ERR_BAD_ARG;
+  if (!x || !y || !z || n < 1) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: empty or null cloud");
+  if (n > kMaxPoints) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: more than 2^31 - 2 points");
+  NRM_HIP(hipSetDevice(h->device));
+  h->has_cloud = false;
+  dfree(h->pos); dfree(h->pts); dfree(h->range);
+  h->pos = h->pts = nullptr; h->range = nullptr;
+  Scratch S;
+  const uint64_t un = uint64_t(n);
+  float* p[3];
+  const float* in[3] = {x, y, z};
+  for (int a = 0; a < 3; ++a) {
+    NRM_HIP(S.alloc((void**)&p[a], un * sizeof(float)));
+    NRM_HIP(hipMemcpyAsync(p[a], in[a], un * sizeof(float), kind, h->st));
+  }
+  NRM_HIP(hipMalloc((void**)&h->pos, un * sizeof(float4)));
+  const int nb = blocks_for(n);
+  hipLaunchKernelGGL(k_pack, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, h->pos);
+  NRM_HIP(hipGetLastError());
+  float* rows;
+  NRM_HIP(S.alloc((void**)&rows, size_t(nb) * 6 * sizeof(float)));
+  hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->pos, un, rows);
+  NRM_HIP(hipGetLastError());
+  std::vector<float> hr(size_t(nb) * 6);
+  NRM_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  NRM_HIP(hipStreamSynchronize(h->st));
+  float lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) { lo[a] = hr[a]; hi[a] = hr[3 + a]; }
+  for (int b = 0; b < nb; ++b)
+    for (int a = 0; a < 3; ++a) {
+      const float l = hr[size_t(b) * 6 + a], u = hr[size_t(b) * 6 + 3 + a];
+      lo[a] = (l != l || lo[a] != lo[a]) ? NAN : std::min(lo[a], l);
+      hi[a] = std::max(hi[a], u);
+    }
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: non-finite coordinates");
+  double spacing = 0.0;
+  if (int32_t rc = plan_spacing(h, S, h->pos, un, lo, hi, &spacing)) return rc;
+  // grid: edge = the spacing (at least 2^-20 of the extent), enlarged x 1.25 until the dense grid fits the cell cap
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) ext = std::max(ext, double(hi[a]) - double(lo[a]));
+  double hh = ext > 0.0 ? std::max(spacing, ext * 0x1p-20) : 1.0;
+  const uint64_t cap = std::min<uint64_t>(kMaxCells, std::max<uint64_t>(1ull << 20, 4 * un));
+  int dims[3];
+  for (int guard = 0;; ++guard) {
+    const double inv = 1.0 / hh;
+    bool ok = true;
+    uint64_t nc = 1;
+    for (int a = 0; a < 3; ++a) {
+      const double cc = cell_coord(hi[a], double(lo[a]), inv);
+      if (!(cc < 1.0e9)) { ok = false; break; }
+      dims[a] = int(cc) + 1;
+      nc *= uint64_t(dims[a]);
+      if (nc > cap) { ok = false; break; }
+    }
+    if (ok) { h->g.h = hh; h->g.inv_h = inv; h->ncell = nc; break; }
+    if (guard > 400) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: no grid fits the cloud's extent");
+    hh *= 1.25;
+  }
+  h->spacing = spacing;
+  h->g.ox = lo[0]; h->g.oy = lo[1]; h->g.oz = lo[2];
+  h->g.nx = dims[0]; h->g.ny = dims[1]; h->g.nz = dims[2];
+  uint32_t *keys, *vals, *keys2, *vals2;
+  NRM_HIP(S.alloc((void**)&keys, un * 4)); NRM_HIP(S.alloc((void**)&vals, un * 4));
+  NRM_HIP(S.alloc((void**)&keys2, un * 4)); NRM_HIP(S.alloc((void**)&vals2, un * 4));
+  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->pos, un, h->g, keys, vals);
+  NRM_HIP(hipGetLastError());
+  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell - 1)) return rc;
+  NRM_HIP(hipMalloc((void**)&h->range, h->ncell * sizeof(uint2)));
+  NRM_HIP(hipMalloc((void**)&h->pts, un * sizeof(float4)));
+  NRM_HIP(hipMemsetAsync(h->range, 0, h->ncell * sizeof(uint2), h->st));
+  hipLaunchKernelGGL(k_cell_ranges, dim3(nb), dim3(kBlock), 0, h->st, (const uint32_t*)keys2, un, h->range);
+  NRM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->pos, (const uint32_t*)vals2, un, h->pts);
+  NRM_HIP(hipGetLastError());
+  NRM_HIP(hipStreamSynchronize(h->st));          // the scratch is freed on return
+  h->g.pts = h->pts;
+  h->g.range = h->range;
+  h->n = n;
+  h->has_cloud = true;
+  return S4P_NORMALS_OK;
+}
+
+int32_t check_args(s4p_normals_ctx* h, int32_t k, float radius) {
+  if (!h->has_cloud) return fail(h, S4P_NORMALS_ERR_STATE, "estimate: set_cloud first");
+  if (k < S4P_NORMALS_MIN_K || k > S4P_NORMALS_MAX_K) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate: k must be in [3, 32]");
+  if (!std::isfinite(radius)) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate: radius must be finite (<= 0: unbounded)");
+  return S4P_NORMALS_OK;
+}
+
+// queries (cell order, w = output slot) -> out (device, 3 floats per query)
+int32_t run_knn(s4p_normals_ctx* h, const float4* qs, uint64_t m, int32_t k, float radius, float* out) {
+  if (m == 0) return S4P_NORMALS_OK;
+  KnnArgs A;
+  A.g = h->g; A.qs = qs; A.m = m; A.pos = h->pos; A.k = k; A.out = out;
+  A.r2lim = radius > 0.f ? radius * radius : INFINITY;
+  const int nb = blocks_for(int64_t(m));
+  if (k <= 8) hipLaunchKernelGGL(k_knn_normals<8>, dim3(nb), dim3(kBlock), 0, h->st, A);
+  else if (k <= 16) hipLaunchKernelGGL(k_knn_normals<16>, dim3(nb), dim3(kBlock), 0, h->st, A);
+  else hipLaunchKernelGGL(k_knn_normals<32>, dim3(nb), dim3(kBlock), 0, h->st, A);
+  NRM_HIP(hipGetLastError());
+  return S4P_NORMALS_OK;
+}
+
+int32_t estimate_impl(s4p_normals_ctx* h, int32_t k, float radius, float* out, bool device_out) {
+  if (!h) return S4P_NORMALS_ERR_BAD_ARG;
+  if (int32_t rc = check_args(h, k, radius)) return rc;
+  if (!out) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate: null output");
+  NRM_HIP(hipSetDevice(h->device));
+  Scratch S;
+  const uint64_t un = uint64_t(h->n);
+  float* dout = out;
+  if (!device_out) NRM_HIP(S.alloc((void**)&dout, 3 * un * sizeof(float)));
+  if (int32_t rc = run_knn(h, h->pts, un, k, radius, dout)) return rc;
+  if (!device_out) NRM_HIP(hipMemcpyAsync(out, dout, 3 * un * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  NRM_HIP(hipStreamSynchronize(h->st));
+  return S4P_NORMALS_OK;
+}
+
+int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, const float* qz, int64_t m, int32_t k, float radius,
+                         float* out, bool device) {
+  if (!h) return S4P_NORMALS_ERR_BAD_ARG;
+  if (int32_t rc = check_args(h, k, radius)) return rc;
+  if (m < 0 || m > kMaxPoints) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate_at: m must be in [0, 2^31 - 2]");
+  if (m == 0) return S4P_NORMALS_OK;
+  if (!qx || !qy || !qz || !out) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate_at: null argument");
+  NRM_HIP(hipSetDevice(h->device));
+  Scratch S;
+  const uint64_t um = uint64_t(m);
+  const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  float* p[3];
+  const float* in[3] = {qx, qy, qz};
+  for (int a = 0; a < 3; ++a) {
+    NRM_HIP(S.alloc((void**)&p[a], um * sizeof(float)));
+    NRM_HIP(hipMemcpyAsync(p[a], in[a], um * sizeof(float), kind, h->st));
+  }
+  float4 *qp, *qs;
+  uint32_t *keys, *vals, *keys2, *vals2;
+  NRM_HIP(S.alloc((void**)&qp, um * sizeof(float4))); NRM_HIP(S.alloc((void**)&qs, um * sizeof(float4)));
+  NRM_HIP(S.alloc((void**)&keys, um * 4)); NRM_HIP(S.alloc((void**)&vals, um * 4));
+  NRM_HIP(S.alloc((void**)&keys2, um * 4)); NRM_HIP(S.alloc((void**)&vals2, um * 4));
+  const int nb = blocks_for(m);
+  hipLaunchKernelGGL(k_pack, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], um, qp);
+  NRM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, um, h->g, keys, vals);
+  NRM_HIP(hipGetLastError());
+  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, um, h->ncell)) return rc;
+  hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, (const uint32_t*)vals2, um, qs);
+  NRM_HIP(hipGetLastError());
+  float* dout = out;
+  if (!device) NRM_HIP(S.alloc((void**)&dout, 3 * um * sizeof(float)));
+  if (int32_t rc = run_knn(h, qs, um, k, radius, dout)) return rc;
+  if (!device) NRM_HIP(hipMemcpyAsync(out, dout, 3 * um * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  NRM_HIP(hipStreamSynchronize(h->st));
+  return S4P_NORMALS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* s4p_normals_last_error(const s4p_normals_ctx* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int32_t s4p_normals_create(int32_t device, s4p_normals_ctx** out) {
+  if (!out) { g_create_error = "null argument"; return S4P_NORMALS_ERR_BAD_ARG; }
+  *out = nullptr;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    g_create_error = "no HIP device visible: the MI355X path has no CPU fallback";
+    return S4P_NORMALS_ERR_NO_DEVICE;
+  }
+  if (device < 0 || device >= ndev) { g_create_error = "bad device index"; return S4P_NORMALS_ERR_BAD_ARG; }
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) { g_create_error = "hipGetDeviceProperties failed"; return S4P_NORMALS_ERR_HIP; }
+  if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos) {
+    g_create_error = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
+    return S4P_NORMALS_ERR_NO_DEVICE;
+  }
+  s4p_normals_ctx* h = new s4p_normals_ctx();
+  h->device = device;
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking) != hipSuccess) {
+    g_create_error = "HIP stream creation failed";
+    s4p_normals_destroy(h);
+    return S4P_NORMALS_ERR_HIP;
+  }
+  *out = h;
+  return S4P_NORMALS_OK;
+}
+
+void s4p_normals_destroy(s4p_normals_ctx* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->st) (void)hipStreamSynchronize(h->st);
+  dfree(h->pos); dfree(h->pts); dfree(h->range);
+  if (h->st) (void)hipStreamDestroy(h->st);
+  delete h;
+}
+
+int32_t s4p_normals_set_cloud(s4p_normals_ctx* h, const float* x, const float* y, const float* z, int64_t n) {
+  return set_cloud_impl(h, x, y, z, n, hipMemcpyHostToDevice);
+}
+int32_t s4p_normals_set_cloud_device(s4p_normals_ctx* h, const float* x, const float* y, const float* z, int64_t n) {
+  return set_cloud_impl(h, x, y, z, n, hipMemcpyDeviceToDevice);
+}
+
+int32_t s4p_normals_estimate(s4p_normals_ctx* h, int32_t k, float radius, float* out) { return estimate_impl(h, k, radius, out, false); }
+int32_t s4p_normals_estimate_device(s4p_normals_ctx* h, int32_t k, float radius, float* out) {
+  return estimate_impl(h, k, radius, out, true);
+}
+
+int32_t s4p_normals_estimate_at(s4p_normals_ctx* h, const float* qx, const float* qy, const float* qz, int64_t m, int32_t k,
+                                float radius, float* out) {
+  return estimate_at_impl(h, qx, qy, qz, m, k, radius, out, false);
+}
+int32_t s4p_normals_estimate_at_device(s4p_normals_ctx* h, const float* qx, const float* qy, const float* qz, int64_t m, int32_t k,
+                                       float radius, float* out) {
+  return estimate_at_impl(h, qx, qy, qz, m, k, radius, out, true);
+}
+
+int32_t s4p_normals_grid(s4p_normals_ctx* h, s4p_normals_grid_info* info) {
+  if (!h) return S4P_NORMALS_ERR_BAD_ARG;
+  if (!info) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "grid: null argument");
+  if (!h->has_cloud) return fail(h, S4P_NORMALS_ERR_STATE, "grid: set_cloud first");
+  NRM_HIP(hipSetDevice(h->device));
+  Scratch S;
+  uint32_t* dh;
+  NRM_HIP(S.alloc((void**)&dh, kOccBins * sizeof(uint32_t)));
+  NRM_HIP(hipMemsetAsync(dh, 0, kOccBins * sizeof(uint32_t), h->st));
+  hipLaunchKernelGGL(k_occupancy, dim3(blocks_for(int64_t(h->ncell))), dim3(kBlock), 0, h->st, (const uint2*)h->range, h->ncell, dh);
+  NRM_HIP(hipGetLastError());
+  std::vector<uint32_t> hist(kOccBins);
+  NRM_HIP(hipMemcpyAsync(hist.data(), dh, kOccBins * sizeof(uint32_t), hipMemcpyDeviceToHost, h->st));
+  NRM_HIP(hipStreamSynchronize(h->st));
+  std::memset(info, 0, sizeof(*info));
+  info->cell = h->g.h;
+  info->spacing = h->spacing;
+  info->dims[0] = h->g.nx; info->dims[1] = h->g.ny; info->dims[2] = h->g.nz;
+  info->cells = int64_t(h->ncell);
+  int64_t ne = 0;
+  for (int b = 1; b < kOccBins; ++b) ne += hist[b];
+  info->nonempty = ne;
+  info->mean_per_cell = ne > 0 ? double(h->n) / double(ne) : 0.0;
+  int64_t cum = 0;
+  const int64_t want = (99 * ne + 99) / 100;
+  for (int b = 1; b < kOccBins; ++b) {
+    if (hist[b] == 0) continue;
+    info->max_per_cell = b;
+    if (cum < want && cum + int64_t(hist[b]) >= want) info->p99_per_cell = b;
+    cum += hist[b];
+  }
+  return S4P_NORMALS_OK;
+}
+
+}  // extern "C"
