@@ -220,6 +220,14 @@ class Context:
         self._chk(self.L.s4p_device_name(self.h, b, 256))
         return b.value.decode()
 
+    def verify_kernel_info(self):
+        """s4p_verify_kernel_info: which k_verify instantiation the clouds that are set take (see Matcher.verify_kernel_info)."""
+        buf = C.create_string_buffer(1024)
+        self.L.s4p_verify_kernel_info.restype = C.c_int32
+        self.L.s4p_verify_kernel_info.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+        self._chk(self.L.s4p_verify_kernel_info(self.h, buf, 1024))
+        return buf.value.decode()
+
     def set_clouds(self, P, Q, Qn=None, Qrgb=None):
         """P, Q: (n,3) float32 sampled + centred clouds."""
         P = np.ascontiguousarray(P, np.float32); Q = np.ascontiguousarray(Q, np.float32)
