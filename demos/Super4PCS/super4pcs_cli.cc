@@ -5,9 +5,12 @@
 //   Super4PCS -i P.obj Q.obj [-o overlap] [-d delta] [-n samples] [-t seconds] [-a normal_deg] [-c colour]
 //             [-r registered_geometry] [-m polyworks_matrix] [--sampled1 file] [--sampled2 file]
 //             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane] [--icp-normal-radius r]
+//             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
+// --icp-loss refines with a robust loss (include/s4p_icp_robust.h): trimmed keeps the --icp-trim fraction of |Q| (default
+// the overlap -o) with the smallest residuals, huber / tukey reweight with --icp-loss-scale (default estimated on the device).
 // --estimate-normals k gives both inputs k-nearest-neighbour normals (algorithms/normals.h, within r if given) before the
 // matcher runs, replacing the normals read from the files for matching only (-r writes the files' own): -a then filters on
 // them, and --icp-metric plane uses P's when all of them are nonzero.
@@ -103,6 +106,9 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       icp.max_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
       icp.metric = opt.icp_plane ? ICPMetric::PointToPlane : ICPMetric::PointToPoint;
       icp.normal_radius = opt.icp_normal_radius;
+      icp.loss = opt.icp_loss == 1 ? ICPLoss::Trimmed : (opt.icp_loss == 2 ? ICPLoss::Huber : (opt.icp_loss == 3 ? ICPLoss::Tukey : ICPLoss::None));
+      icp.trim_fraction = opt.icp_trim > 0 ? opt.icp_trim : opt.overlap;
+      icp.loss_scale = opt.icp_loss_scale;
       ICPResult res;
       RefineICP(P.points, &Q.points, mat, icp, &res);
       log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);

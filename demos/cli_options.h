@@ -26,6 +26,10 @@ struct Options {
   double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
   bool icp_plane = false;                                    // --icp-metric point|plane  (default point)
   double icp_normal_radius = -1;                             // --icp-normal-radius  (default: the ICP max distance)
+  int icp_loss = 0;                                          // --icp-loss none|trimmed|huber|tukey  (0 1 2 3; default none)
+  double icp_trim = -1;                                      // --icp-trim  (trimmed; default: the overlap -o)
+  double icp_loss_scale = -1;                                // --icp-loss-scale  (huber / tukey; default: estimated)
+  bool icp_trim_set = false, icp_loss_scale_set = false;
   int normals_k = 0;                                         // --estimate-normals k  normals of both inputs on the device (0: off)
   double normals_radius = -1;                                // --estimate-normals-radius r  (default: unbounded)
   bool normals_radius_set = false;
@@ -75,6 +79,24 @@ inline const Flag* flag_table(size_t* n) {
          const double r = std::strtod(v[0], &end);
          if (end == v[0] || *end != '\0' || !(r > 0) || !std::isfinite(r)) o.bad_value = true; else o.icp_normal_radius = r;
        }},
+      {"--icp-loss", 1, [](Options& o, char** v) {
+         static const char* names[] = {"none", "trimmed", "huber", "tukey"};
+         int hit = -1;
+         for (int k = 0; k < 4; ++k) if (!std::strcmp(v[0], names[k])) hit = k;
+         if (hit < 0) o.bad_value = true; else o.icp_loss = hit;
+       }},
+      {"--icp-trim", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double t = std::strtod(v[0], &end);
+         o.icp_trim_set = true;
+         if (end == v[0] || *end != '\0' || !(t > 0) || !(t <= 1)) o.bad_value = true; else o.icp_trim = t;
+       }},
+      {"--icp-loss-scale", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double s = std::strtod(v[0], &end);
+         o.icp_loss_scale_set = true;
+         if (end == v[0] || *end != '\0' || !(s > 0) || !std::isfinite(s)) o.bad_value = true; else o.icp_loss_scale = s;
+       }},
       {"--estimate-normals", 1, [](Options& o, char** v) {
          char* end = nullptr;
          const long k = std::strtol(v[0], &end, 10);
@@ -109,6 +131,8 @@ inline Parse parse(Options& o, int argc, char** argv) {
   }
   if (o.bad_value) return Parse::Bad;
   if (o.normals_radius_set && o.normals_k == 0) return Parse::Bad;    // the radius needs --estimate-normals
+  if (o.icp_trim_set && o.icp_loss != 1) return Parse::Bad;            // --icp-trim needs --icp-loss trimmed
+  if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -125,6 +149,8 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
   std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
   std::fprintf(stderr, "\t[ --icp-metric point|plane (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
+  std::fprintf(stderr, "\t[ --icp-loss none|trimmed|huber|tukey (none) ] [ --icp-trim fraction (trimmed; -o) ]\n");
+  std::fprintf(stderr, "\t[ --icp-loss-scale s (huber, tukey; estimated) ]  (robust ICP)\n");
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
   std::fprintf(stderr, "\t     them and --icp-metric plane uses P's when all are nonzero)\n");

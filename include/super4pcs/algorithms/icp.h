@@ -1,7 +1,7 @@
 // RefineICP: point-to-point or point-to-plane ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
 // documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
 // of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h,
-// include/s4p_icp_plane.h).
+// include/s4p_icp_plane.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
 // Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
 //
 //   MatchSuper4PCS matcher(options, logger);
@@ -19,11 +19,13 @@
 
 #include "s4p_icp.h"
 #include "s4p_icp_plane.h"
+#include "s4p_icp_robust.h"
 #include "super4pcs/algorithms/match4pcsBase.h"
 
 namespace GlobalRegistration {
 
 enum class ICPMetric { PointToPoint, PointToPlane };
+enum class ICPLoss { None, Trimmed, Huber, Tukey };
 
 struct ICPOptions {
   int max_iterations = 30;
@@ -35,6 +37,11 @@ struct ICPOptions {
   // PointToPlane: P's normals when every point of P has a nonzero one, else normals estimated on the device from the
   // neighbours within normal_radius (<= 0: max_distance; at most max_distance) with at least 6 of them
   double normal_radius = -1.0;
+  // None: least squares over every pair within max_distance.  Trimmed keeps the pairs whose residual is at most the
+  // ceil(trim_fraction |Q|)-th smallest; Huber / Tukey reweight with the scale loss_scale (<= 0: estimated on the device)
+  ICPLoss loss = ICPLoss::None;
+  double trim_fraction = 1.0;       // Trimmed: in (0, 1], e.g. the registration's overlap
+  double loss_scale = -1.0;         // Huber / Tukey
 };
 
 struct ICPResult {
@@ -94,7 +101,17 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   prm.rel_tol = options.rel_tol;
   double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   s4p_icp_result r;
-  H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
+  if (options.loss == ICPLoss::None) {
+    H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
+  } else {
+    const int32_t loss = options.loss == ICPLoss::Trimmed ? S4P_ICP_LOSS_TRIMMED
+                         : (options.loss == ICPLoss::Huber ? S4P_ICP_LOSS_HUBER : S4P_ICP_LOSS_TUKEY);
+    s4p_icp_robust rob;
+    s4p_icp_robust_defaults(&rob, loss);
+    rob.trim_fraction = options.trim_fraction;
+    rob.scale = options.loss_scale;
+    H.check(s4p_icp_refine_robust(H.h, &prm, plane ? S4P_ICP_METRIC_PLANE : S4P_ICP_METRIC_POINT, &rob, dT, &r, nullptr));
+  }
   H.check(s4p_icp_apply(H.h, dT, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
   for (size_t i = 0; i < Q->size(); ++i) { (*Q)[i].x() = q[0][i]; (*Q)[i].y() = q[1][i]; (*Q)[i].z() = q[2][i]; }
   double M[16];

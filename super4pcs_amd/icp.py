@@ -1,9 +1,10 @@
-"""ctypes binding of include/s4p_icp.h and include/s4p_icp_plane.h (libsuper4pcs_icp.so): point-to-point and
-point-to-plane ICP refinement on the full-resolution clouds.
+"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h and include/s4p_icp_robust.h (libsuper4pcs_icp.so):
+point-to-point and point-to-plane ICP refinement on the full-resolution clouds, with optional robust losses.
 
     from super4pcs_amd import icp
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="plane")   # target normals estimated on the device
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta, loss="trimmed", trim_fraction=0.6)   # trimmed ICP
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -27,6 +28,9 @@ ERR_DEGENERATE = -8
 ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE", ERR_DEGENERATE: "DEGENERATE"}
 METRICS = ("point", "plane")
 MIN_NEIGHBOURS = 6              # estimate_normals' default
+LOSSES = {"trimmed": 1, "huber": 2, "tukey": 3}             # S4P_ICP_LOSS_*
+LOSS_C = {"huber": 1.345, "tukey": 4.685}                   # default tuning constants
+ROBUST_NINFO = 8
 
 SYMBOLS = [
     "s4p_icp_default_params", "s4p_icp_create", "s4p_icp_destroy", "s4p_icp_last_error", "s4p_icp_set_target",
@@ -36,6 +40,9 @@ SYMBOLS = [
 PLANE_SYMBOLS = [                                          # include/s4p_icp_plane.h
     "s4p_icp_set_target_normals", "s4p_icp_set_target_normals_device", "s4p_icp_estimate_normals", "s4p_icp_target_normals",
     "s4p_icp_plane_sums", "s4p_icp_solve_plane", "s4p_icp_refine_plane",
+]
+ROBUST_SYMBOLS = [                                         # include/s4p_icp_robust.h
+    "s4p_icp_robust_defaults", "s4p_icp_robust_sums", "s4p_icp_refine_robust",
 ]
 
 
@@ -48,6 +55,11 @@ class ICPError(RuntimeError):
 class Params(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("min_correspondences", C.c_int32), ("rel_tol", C.c_double),
                 ("order_source", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Robust(C.Structure):
+    _fields_ = [("loss", C.c_int32), ("reserved0", C.c_int32), ("trim_fraction", C.c_double), ("scale", C.c_double),
+                ("c", C.c_double), ("reserved", C.c_double * 4)]
 
 
 class Result(C.Structure):
@@ -111,6 +123,12 @@ def load_library():
     L.s4p_icp_solve_plane.argtypes = [dp, dp]
     L.s4p_icp_refine_plane.restype = C.c_int32
     L.s4p_icp_refine_plane.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
+    L.s4p_icp_robust_defaults.restype = None
+    L.s4p_icp_robust_defaults.argtypes = [C.POINTER(Robust), C.c_int32]
+    L.s4p_icp_robust_sums.restype = C.c_int32
+    L.s4p_icp_robust_sums.argtypes = [vp, fp, C.c_int32, C.POINTER(Robust), dp, dp]
+    L.s4p_icp_refine_robust.restype = C.c_int32
+    L.s4p_icp_refine_robust.argtypes = [vp, C.POINTER(Params), C.c_int32, C.POINTER(Robust), dp, C.POINTER(Result), dp]
     _LIB = L
     return L
 
@@ -144,6 +162,29 @@ def solve_plane(sums):
     if rc != 0:
         raise ICPError(rc, "solve_plane: degenerate system" if rc == ERR_DEGENERATE else "solve_plane: bad argument")
     return out.reshape(4, 4)
+
+
+def robust_params(loss, trim_fraction=None, scale=None, c=None):
+    """The s4p_icp_robust of a loss name: "trimmed" needs trim_fraction in (0, 1]; "huber" / "tukey" take scale (> 0 fixed,
+    None or <= 0 estimated on the device) and c (None: 1.345 / 4.685).  A parameter the loss does not use is an error."""
+    if loss not in LOSSES:
+        raise ValueError("loss must be one of %s" % (tuple(LOSSES),))
+    r = Robust()
+    load_library().s4p_icp_robust_defaults(C.byref(r), LOSSES[loss])
+    if loss == "trimmed":
+        if scale is not None or c is not None:
+            raise ValueError("the trimmed loss takes no scale or c")
+        if trim_fraction is None:
+            raise ValueError("the trimmed loss needs trim_fraction")
+        r.trim_fraction = float(trim_fraction)
+    else:
+        if trim_fraction is not None:
+            raise ValueError("trim_fraction belongs to the trimmed loss")
+        if scale is not None:
+            r.scale = float(scale)
+        if c is not None:
+            r.c = float(c)
+    return r
 
 
 def compose(A, B):
@@ -268,17 +309,41 @@ class ICP:
         self._chk(self.L.s4p_icp_sums(self.h, _fp(T), _dp(out)))
         return out
 
-    def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True, metric="point"):
-        """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity).  metric "plane"
-        minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals)."""
+    def robust_sums(self, T, metric, loss, trim_fraction=None, scale=None, c=None):
+        """(sums, info) for a float T in the centred frame: the weighted 17 (point) or 31 (plane) sums and the 8 info
+        doubles of include/s4p_icp_robust.h (M, k, threshold key bits, s, count with w > 0, sum w, 0, 0)."""
         if metric not in METRICS:
             raise ValueError("metric must be one of %s" % (METRICS,))
+        r = robust_params(loss, trim_fraction, scale, c)
+        T = self._t32(T)
+        out = np.empty(PLANE_NSUMS if metric == "plane" else NSUMS, np.float64)
+        info = np.empty(ROBUST_NINFO, np.float64)
+        self._chk(self.L.s4p_icp_robust_sums(self.h, _fp(T), METRICS.index(metric), C.byref(r), _dp(out), _dp(info)))
+        return out, info
+
+    def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True, metric="point",
+               loss=None, trim_fraction=None, loss_scale=None, loss_c=None, info=None):
+        """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity).  metric "plane"
+        minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals).  loss
+        "trimmed" / "huber" / "tukey" refines on the weighted sums (include/s4p_icp_robust.h); loss=None is the plain
+        refine.  info: an optional float64 array of 8 that receives the final pass's robust info."""
+        if metric not in METRICS:
+            raise ValueError("metric must be one of %s" % (METRICS,))
+        if loss is None and (trim_fraction is not None or loss_scale is not None or loss_c is not None or info is not None):
+            raise ValueError("trim_fraction / loss_scale / loss_c / info need a loss")
+        rob = None if loss is None else robust_params(loss, trim_fraction, loss_scale, loss_c)
         T = np.ascontiguousarray(np.eye(4) if T0 is None else np.asarray(T0, np.float64).reshape(4, 4), np.float64).reshape(16).copy()
         p = Params()
         self.L.s4p_icp_default_params(C.byref(p))
         p.max_iterations, p.rel_tol, p.min_correspondences = int(max_iterations), float(rel_tol), int(min_correspondences)
         p.order_source = int(bool(order_source))
         r = Result()
+        if rob is not None:
+            inf = np.zeros(ROBUST_NINFO, np.float64)
+            self._chk(self.L.s4p_icp_refine_robust(self.h, C.byref(p), METRICS.index(metric), C.byref(rob), _dp(T), C.byref(r), _dp(inf)))
+            if info is not None:
+                info[:] = inf
+            return T.reshape(4, 4), r
         fn = self.L.s4p_icp_refine_plane if metric == "plane" else self.L.s4p_icp_refine
         self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
         return T.reshape(4, 4), r
@@ -294,7 +359,8 @@ class ICP:
 
 def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None, **params):
     """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane": the
-    target normals are target_normals if given, else estimated within normal_radius (default max_distance)."""
+    target normals are target_normals if given, else estimated within normal_radius (default max_distance).  params go to
+    ICP.refine, the robust ones (loss, trim_fraction, loss_scale, loss_c) included."""
     if max_distance is None:
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
     if metric not in METRICS:

@@ -1,5 +1,6 @@
-// s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point and point-to-plane ICP on the full-resolution clouds (include/s4p_icp.h,
-// include/s4p_icp_plane.h, DESIGN.md sections "ICP refinement" and "Point-to-plane ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
+// s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point and point-to-plane ICP on the full-resolution clouds, with robust
+// losses (include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, DESIGN.md sections "ICP refinement",
+// "Point-to-plane ICP" and "Robust ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
 //
 // Device path:
 //   set_target   k_stats (per-block double sums and float bounds of P) -> host frame c and grid plan ->
@@ -10,7 +11,9 @@
 //                k_final (fixed-order sum of the slab), one pinned read-back, host solve.
 //   plane        (include/s4p_icp_plane.h) target normals, cell-ordered next to tgt: k_normals (estimated) or
 //                k_gather_normals (the caller's); per iteration k_match_plane (31 double sums) + k_final_plane, host solve.
-// No float or double atomics anywhere: every sum has a fixed order, so two calls return identical bits.
+//   robust       (include/s4p_icp_robust.h) per iteration k_search (winner slot + residual key per lane), the radix select of
+//                the keys (k_key_hist + k_key_digit x 4, on the device), k_wsum + k_wfinal (weighted sums), host solve.
+// No float or double atomics anywhere (the selection's histograms use integer atomics): every sum has a fixed order, so two calls return identical bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -24,6 +27,7 @@
 
 #include "s4p_icp.h"
 #include "s4p_icp_plane.h"
+#include "s4p_icp_robust.h"
 
 namespace s4p_icp {
 
@@ -275,6 +279,70 @@ __global__ __launch_bounds__(kBlock) void k_apply_icp(Tf T, float* x, float* y, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// robust ICP (include/s4p_icp_robust.h).  Per iteration: k_search (the one correspondence search: winner slot and residual
+// key per visited lane), the radix select of the keys (k_key_hist + k_key_digit per 8-bit digit, integer atomics only, the
+// digit decisions on the device), k_wsum (weighted sums streamed from the slots, k_match / k_match_plane's lane order and
+// reduction) and k_wfinal (k_final / k_final_plane's fixed order, plus the count with w > 0 and the info).
+
+constexpr uint32_t kNoKey = 0xFFFFFFFFu;    // a miss, or (plane) a zero normal: above every key (keys are non-negative floats)
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+constexpr int kDigits = 4, kBins = 256;     // 4 digits of 8 bits, most significant first
+enum SelMode { kSelNone = 0, kSelTrim = 1, kSelMedian = 2 };
+
+struct SelState {          // zeroed before each pass; written by k_key_digit only
+  uint32_t M, k, rank, prefix;
+  double s, cs, cs2;
+};
+
+// histogram of digit `pass` over the keys whose higher digits equal the selected prefix (LDS, then one add per bin)
+__global__ __launch_bounds__(kBlock) void k_key_hist(const uint32_t* key, uint64_t n, int pass, const SelState* st, uint32_t* hist) {
+  if (pass > 0 && st->k == 0) return;                     // nothing to select (uniform)
+  __shared__ uint32_t h[kBins];
+  h[threadIdx.x] = 0u;
+  __syncthreads();
+  const int shift = 24 - 8 * pass;
+  const uint32_t hi = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+  const uint32_t want = st->prefix & hi;
+  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t u = key[i];
+    if (u != kNoKey && (u & hi) == want) atomicAdd(&h[(u >> shift) & (kBins - 1)], 1u);
+  }
+  __syncthreads();
+  const uint32_t c = h[threadIdx.x];
+  if (c) atomicAdd(&hist[threadIdx.x], c);
+}
+
+// One block: the digit of the rank-k key at `pass` (pass 0 first counts M and sets k); the last pass sets the scale.
+__global__ __launch_bounds__(kBlock) void k_key_digit(const uint32_t* hist, int pass, bool last, int mode, uint64_t kq, double scale,
+                                                      double c, double smin, SelState* st) {
+  __shared__ uint32_t h[kBins];
+  h[threadIdx.x] = hist[threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (pass == 0) {
+    uint32_t M = 0;
+    for (int b = 0; b < kBins; ++b) M += h[b];
+    const uint32_t k = mode == kSelTrim ? uint32_t(min<uint64_t>(uint64_t(M), max<uint64_t>(1, kq)))
+                                        : (mode == kSelMedian ? (M + 1) / 2 : 0u);
+    st->M = M; st->k = k; st->rank = k; st->prefix = 0u;
+  }
+  if (st->k > 0) {
+    uint32_t r = st->rank;
+    int b = 0;
+    while (b < kBins - 1 && r > h[b]) { r -= h[b]; ++b; }
+    st->prefix |= uint32_t(b) << (24 - 8 * pass);
+    st->rank = r;
+  }
+  if (last) {
+    double s = 0.0;
+    if (mode == kSelMedian) s = fmax(1.4826 * sqrt(double(__uint_as_float(st->prefix))), smin);   // M == 0: prefix 0, s_min
+    else if (scale > 0.0) s = scale;
+    const double cs = c * s;
+    st->s = s; st->cs = cs; st->cs2 = cs * cs;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // point-to-plane (include/s4p_icp_plane.h): target normals as a cell-ordered float4 array next to tgt (w unused)
 
 constexpr int kPlanePitch = 32;             // doubles per plane slab row (31 used)
@@ -475,6 +543,187 @@ __global__ __launch_bounds__(kBlock) void k_final_plane(const double* slab, int 
   }
 }
 
+// robust ICP, continued: the correspondence search and the weighted sums (templates on the metric)
+
+struct SearchArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;
+  const float4* nrm;        // plane: cell order, as g.tgt
+  uint64_t n;
+  float d2max;
+  uint32_t* slot;           // per visited lane: the winner's cell-order position, or kNoSlot
+  uint32_t* key;            // per visited lane: the bits of u, or kNoKey
+};
+
+template <bool PLANE>
+__global__ __launch_bounds__(kBlock) void k_search(SearchArgs A) {
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    float best;
+    uint32_t bi, slot;
+    float4 p;
+    nearest_t<true>(A.g, x, y, z, A.d2max, best, bi, p, slot);
+    uint32_t sl = kNoSlot, ky = kNoKey;
+    if (bi != 0xFFFFFFFFu) {
+      sl = slot;
+      if (PLANE) {
+        const float4 nf = A.nrm[slot];
+        if (!(nf.x == 0.f && nf.y == 0.f && nf.z == 0.f)) {
+          const double qd[3] = {double(x), double(y), double(z)}, nd[3] = {double(nf.x), double(nf.y), double(nf.z)};
+          const double r = ((double(p.x) - qd[0]) * nd[0] + (double(p.y) - qd[1]) * nd[1]) + (double(p.z) - qd[2]) * nd[2];
+          ky = __float_as_uint(float(r * r));
+        }
+      } else {
+        ky = __float_as_uint(best);
+      }
+    }
+    A.slot[j] = sl;
+    A.key[j] = ky;
+  }
+}
+
+__device__ inline double robust_weight(int loss, float u, uint32_t thr, double cs, double cs2) {
+  if (loss == S4P_ICP_LOSS_TRIMMED) return __float_as_uint(u) <= thr ? 1.0 : 0.0;
+  const double ud = double(u);
+  if (loss == S4P_ICP_LOSS_HUBER) return ud <= cs2 ? 1.0 : cs / sqrt(ud);
+  if (ud < cs2) {
+    const double t = 1.0 - ud / cs2;
+    return t * t;
+  }
+  return 0.0;
+}
+
+struct WsumArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;
+  const float4* nrm;
+  uint64_t n;
+  const uint32_t* slot;     // k_search's
+  const SelState* st;
+  int32_t loss;
+  double* slab;             // one kPitch (point) / kPlanePitch (plane) row per workgroup
+};
+
+// The weighted sums: k_match / k_match_plane's lanes, terms and reduction with every keyed pair's terms times w (so w == 1
+// gives their bits), plus one column: the count with w > 0.  No search: the winner comes from k_search's slot.
+template <bool PLANE>
+__global__ __launch_bounds__(kBlock) void k_wsum(WsumArgs A) {
+  constexpr int NS = PLANE ? S4P_ICP_PLANE_NSUMS : S4P_ICP_NSUMS;
+  constexpr int NC = NS + 1;
+  constexpr int kRowPitch = PLANE ? kPlanePitch : kPitch;
+  static_assert(NC <= kRowPitch, "slab row");
+  double s[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) s[k] = 0.0;
+  const uint32_t thr = A.st->prefix;
+  const double cs = A.st->cs, cs2 = A.st->cs2;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t sl = A.slot[j];
+    if (sl == kNoSlot) continue;
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    const float4 p = A.g.tgt[sl];
+    const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
+    const float d2 = dx * dx + (dy * dy + dz * dz);           // nearest_t's float d2 of the winner
+    const double qd[3] = {double(x), double(y), double(z)};
+    if (PLANE) {
+      const float4 nf = A.nrm[sl];
+      if (nf.x == 0.f && nf.y == 0.f && nf.z == 0.f) {        // no key: counted as in k_match_plane
+        s[0] += 1.0;
+        s[1] += double(d2);
+        s[NS] += 1.0;
+        continue;
+      }
+      const double nd[3] = {double(nf.x), double(nf.y), double(nf.z)};
+      const double a[6] = {qd[1] * nd[2] - qd[2] * nd[1], qd[2] * nd[0] - qd[0] * nd[2], qd[0] * nd[1] - qd[1] * nd[0], nd[0], nd[1], nd[2]};
+      const double r = ((double(p.x) - qd[0]) * nd[0] + (double(p.y) - qd[1]) * nd[1]) + (double(p.z) - qd[2]) * nd[2];
+      const double w = robust_weight(A.loss, float(r * r), thr, cs, cs2);
+      if (!(w > 0.0)) continue;
+      s[0] += w;
+      s[1] += double(d2) * w;
+      s[2] += 1.0;
+      s[3] += (r * r) * w;
+      int o = 4;
+#pragma unroll
+      for (int u = 0; u < 6; ++u)
+#pragma unroll
+        for (int v = u; v < 6; ++v) s[o++] += (a[u] * a[v]) * w;
+#pragma unroll
+      for (int u = 0; u < 6; ++u) s[25 + u] += (a[u] * r) * w;
+    } else {
+      const double w = robust_weight(A.loss, d2, thr, cs, cs2);
+      if (!(w > 0.0)) continue;
+      const double pd[3] = {double(p.x), double(p.y), double(p.z)};
+      s[0] += w;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) { s[1 + a] += qd[a] * w; s[4 + a] += pd[a] * w; }
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) s[7 + 3 * a + b] += (qd[a] * pd[b]) * w;
+      s[16] += double(d2) * w;
+    }
+    s[NS] += 1.0;
+  }
+  __shared__ double red[kBlock / 64][NC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    double v = s[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NC) {
+    double v = red[0][threadIdx.x];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][threadIdx.x];
+    A.slab[uint64_t(blockIdx.x) * kRowPitch + threadIdx.x] = v;
+  }
+}
+
+// k_final / k_final_plane's order for the NS sums.  The count column (whole numbers: exact in any order) is summed by all
+// threads; the last thread (idle in k_final / k_final_plane's scheme) adds their parts and writes the info.
+template <bool PLANE>
+__global__ __launch_bounds__(kBlock) void k_wfinal(const double* slab, int nb, const SelState* st, double* out) {
+  constexpr int NS = PLANE ? S4P_ICP_PLANE_NSUMS : S4P_ICP_NSUMS;
+  constexpr int kRowPitch = PLANE ? kPlanePitch : kPitch;
+  constexpr int kParts = kBlock / NS;
+  static_assert(kParts * NS < kBlock, "a spare thread");
+  __shared__ double part[kParts][NS];
+  __shared__ double cpart[kBlock];
+  const int col = threadIdx.x % NS, prt = threadIdx.x / NS;
+  if (prt < kParts) {
+    double v = 0.0;
+    for (int r = prt; r < nb; r += kParts) v += slab[uint64_t(r) * kRowPitch + col];
+    part[prt][col] = v;
+  }
+  double c = 0.0;
+  for (int r = threadIdx.x; r < nb; r += kBlock) c += slab[uint64_t(r) * kRowPitch + NS];
+  cpart[threadIdx.x] = c;
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    double v = part[0][threadIdx.x];
+    for (int p = 1; p < kParts; ++p) v += part[p][threadIdx.x];
+    out[threadIdx.x] = v;
+  }
+  if (threadIdx.x == kBlock - 1) {
+    double cnt = 0.0;
+    for (int t = 0; t < kBlock; ++t) cnt += cpart[t];
+    double* info = out + NS;
+    info[0] = double(st->M);
+    info[1] = double(st->k);
+    info[2] = st->k ? double(st->prefix) : 0.0;
+    info[3] = st->s;
+    info[4] = cnt;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host: Horn's closed form.  N (4x4 symmetric) from the centred cross-covariance; its eigenvector of the largest
 // eigenvalue (cyclic Jacobi) is the unit quaternion of the rotation.
@@ -556,6 +805,14 @@ struct s4p_icp_ctx {
   float4* nrm = nullptr;             // target normals, cell order (point-to-plane)
   bool has_normals = false;
   double* pslab = nullptr;           // plane slab: kMaxBlocks rows of kPlanePitch
+  // robust ICP (include/s4p_icp_robust.h), allocated on first use
+  int64_t r_n = 0;                   // entries of rslot / rkey
+  uint32_t* rslot = nullptr;
+  uint32_t* rkey = nullptr;
+  uint32_t* rhist = nullptr;         // kDigits x kBins
+  SelState* rst = nullptr;
+  double* rsum = nullptr;            // sums + info
+  double* rhsum = nullptr;           // pinned
 };
 
 namespace {
@@ -732,6 +989,94 @@ int32_t ready(s4p_icp_ctx* h) {
   return S4P_ICP_OK;
 }
 
+// a validated s4p_icp_robust: the loss, the selection and its inputs
+struct RobustCfg {
+  int32_t loss = 0;
+  int mode = kSelNone;
+  uint64_t kq = 0;          // TRIMMED: ceil(trim_fraction * n_Q)
+  double scale = 0.0, c = 0.0, smin = 0.0;
+};
+
+int32_t robust_cfg(s4p_icp_ctx* h, int32_t metric, const s4p_icp_robust* R, RobustCfg* out) {
+  if (!R) return fail(h, S4P_ICP_ERR_BAD_ARG, "robust: null parameters");
+  if (metric != S4P_ICP_METRIC_POINT && metric != S4P_ICP_METRIC_PLANE) return fail(h, S4P_ICP_ERR_BAD_ARG, "robust: unknown metric");
+  RobustCfg C;
+  C.loss = R->loss;
+  C.smin = 1e-6 * double(h->d);
+  if (R->loss == S4P_ICP_LOSS_TRIMMED) {
+    if (!(R->trim_fraction > 0.0 && R->trim_fraction <= 1.0))
+      return fail(h, S4P_ICP_ERR_BAD_ARG, "robust: trim_fraction must be in (0, 1]");
+    C.mode = kSelTrim;
+    C.kq = uint64_t(std::ceil(R->trim_fraction * double(h->n_q)));
+  } else if (R->loss == S4P_ICP_LOSS_HUBER || R->loss == S4P_ICP_LOSS_TUKEY) {
+    if (!(R->c > 0.0) || !std::isfinite(R->c)) return fail(h, S4P_ICP_ERR_BAD_ARG, "robust: c must be finite and > 0");
+    if (std::isnan(R->scale) || !(R->scale < INFINITY)) return fail(h, S4P_ICP_ERR_BAD_ARG, "robust: scale must be finite");
+    C.c = R->c;
+    C.scale = R->scale > 0.0 ? R->scale : 0.0;
+    C.mode = R->scale > 0.0 ? kSelNone : kSelMedian;
+  } else {
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "robust: unknown loss");
+  }
+  *out = C;
+  return S4P_ICP_OK;
+}
+
+// One robust pass over `src` for T: one search, the selection, the weighted sums; sums and info on the host.
+int32_t robust_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, bool plane, const RobustCfg& C, double* sums, double* info) {
+  const uint64_t un = uint64_t(h->n_q);
+  if (h->r_n != h->n_q) {
+    dfree(h->rslot); dfree(h->rkey); h->rslot = h->rkey = nullptr;
+    h->r_n = 0;
+    ICP_HIP(hipMalloc((void**)&h->rslot, un * sizeof(uint32_t)));
+    ICP_HIP(hipMalloc((void**)&h->rkey, un * sizeof(uint32_t)));
+    h->r_n = h->n_q;
+  }
+  constexpr int kOut = S4P_ICP_PLANE_NSUMS + S4P_ICP_ROBUST_NINFO;
+  if (!h->rhist) ICP_HIP(hipMalloc((void**)&h->rhist, kDigits * kBins * sizeof(uint32_t)));
+  if (!h->rst) ICP_HIP(hipMalloc((void**)&h->rst, sizeof(SelState)));
+  if (!h->rsum) ICP_HIP(hipMalloc((void**)&h->rsum, kOut * sizeof(double)));
+  if (!h->rhsum) ICP_HIP(hipHostMalloc((void**)&h->rhsum, kOut * sizeof(double), hipHostMallocDefault));
+  if (plane && !h->pslab) ICP_HIP(hipMalloc((void**)&h->pslab, size_t(kMaxBlocks) * kPlanePitch * sizeof(double)));
+  const int nb = blocks_for(h->n_q);
+  ICP_HIP(hipMemsetAsync(h->rhist, 0, kDigits * kBins * sizeof(uint32_t), h->st));
+  ICP_HIP(hipMemsetAsync(h->rst, 0, sizeof(SelState), h->st));
+  SearchArgs S;
+  S.T = T; S.g = h->g; S.src = src; S.nrm = h->nrm; S.n = un; S.d2max = h->d2max; S.slot = h->rslot; S.key = h->rkey;
+  if (plane) hipLaunchKernelGGL(k_search<true>, dim3(nb), dim3(kBlock), 0, h->st, S);
+  else hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, S);
+  ICP_HIP(hipGetLastError());
+  const int passes = C.mode == kSelNone ? 1 : kDigits;         // without a selection, pass 0 still counts M
+  for (int p = 0; p < passes; ++p) {
+    hipLaunchKernelGGL(k_key_hist, dim3(nb), dim3(kBlock), 0, h->st, (const uint32_t*)h->rkey, un, p, (const SelState*)h->rst,
+                       h->rhist + p * kBins);
+    ICP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_key_digit, dim3(1), dim3(kBlock), 0, h->st, (const uint32_t*)(h->rhist + p * kBins), p, p == passes - 1, C.mode,
+                       C.kq, C.scale, C.c, C.smin, h->rst);
+    ICP_HIP(hipGetLastError());
+  }
+  WsumArgs W;
+  W.T = T; W.g = h->g; W.src = src; W.nrm = h->nrm; W.n = un; W.slot = h->rslot; W.st = h->rst; W.loss = C.loss;
+  W.slab = plane ? h->pslab : h->slab;
+  const int ns = plane ? S4P_ICP_PLANE_NSUMS : S4P_ICP_NSUMS;
+  if (plane) {
+    hipLaunchKernelGGL(k_wsum<true>, dim3(nb), dim3(kBlock), 0, h->st, W);
+    ICP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_wfinal<true>, dim3(1), dim3(kBlock), 0, h->st, (const double*)h->pslab, nb, (const SelState*)h->rst, h->rsum);
+  } else {
+    hipLaunchKernelGGL(k_wsum<false>, dim3(nb), dim3(kBlock), 0, h->st, W);
+    ICP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_wfinal<false>, dim3(1), dim3(kBlock), 0, h->st, (const double*)h->slab, nb, (const SelState*)h->rst, h->rsum);
+  }
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(h->rhsum, h->rsum, (ns + 5) * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipEventRecord(h->ev, h->st));
+  ICP_HIP(hipEventSynchronize(h->ev));
+  std::memcpy(sums, h->rhsum, ns * sizeof(double));
+  for (int k = 0; k < S4P_ICP_ROBUST_NINFO; ++k) info[k] = k < 5 ? h->rhsum[ns + k] : 0.0;
+  info[5] = sums[0];
+  return S4P_ICP_OK;
+}
+
 // one correspondence pass over `src` for T: the 17 sums (and, if idx, the per-point answers) on the host
 int32_t pass(s4p_icp_ctx* h, const Tf& T, const float4* src, int32_t* idx_dev, float* d2_dev, double* out) {
   MatchArgs A;
@@ -884,6 +1229,58 @@ int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_in
   return S4P_ICP_OK;
 }
 
+// refine_impl's loop on the weighted sums: rmse = sqrt(sum w d2 / sum w), n = the count with w > 0 (info[4])
+int32_t refine_robust_impl(s4p_icp_ctx* h, const s4p_icp_params* params, int32_t metric, const s4p_icp_robust* robust, double* T16_inout,
+                           s4p_icp_result* result, double* info_out) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_inout) return fail(h, S4P_ICP_ERR_BAD_ARG, "refine_robust: null transform");
+  s4p_icp_params P;
+  s4p_icp_default_params(&P);
+  if (params) P = *params;
+  if (P.max_iterations < 0 || P.min_correspondences < 0 || !(P.rel_tol >= 0.0))
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "refine_robust: negative max_iterations / min_correspondences / rel_tol");
+  const bool plane = metric == S4P_ICP_METRIC_PLANE;
+  if (int32_t rc = plane ? plane_ready(h) : ready(h)) return rc;
+  RobustCfg C;
+  if (int32_t rc = robust_cfg(h, metric, robust, &C)) return rc;
+  s4p_icp_result R;
+  std::memset(&R, 0, sizeof(R));
+  double T[16], Tn[16], dT[16], sums[kSumsCap], info[S4P_ICP_ROBUST_NINFO];
+  const int i_d2 = plane ? 1 : 16;
+  to_centred(T16_inout, h->c, T);
+  const float4* src = nullptr;
+  if (int32_t rc = source_for(h, P, T, &src)) return rc;
+  double prev = 0.0;
+  R.status = S4P_ICP_MAX_ITERATIONS;
+  for (int k = 0; k < P.max_iterations; ++k) {
+    if (int32_t rc = robust_pass(h, to_float(T), src, plane, C, sums, info)) return rc;
+    const double n = info[4], sw = sums[0];
+    const double rmse = sw > 0.0 ? std::sqrt(sums[i_d2] / sw) : 0.0;
+    if (k < S4P_ICP_HISTORY) { R.history_rmse[k] = rmse; R.history_n[k] = int64_t(n); R.history_len = k + 1; }
+    if (n < double(std::max(P.min_correspondences, 1)) || (!plane && !(sw >= 1.0))) { R.status = S4P_ICP_TOO_FEW; break; }
+    if (plane) {
+      if (s4p_icp_solve_plane(sums, dT) != S4P_ICP_OK) { R.status = S4P_ICP_DEGENERATE; break; }
+    } else {
+      s4p_icp_solve(sums, dT);
+    }
+    mat_mul4(dT, T, Tn);
+    std::memcpy(T, Tn, sizeof(T));
+    R.iterations = k + 1;
+    if (k + 1 == P.max_iterations) { R.status = S4P_ICP_MAX_ITERATIONS; break; }
+    if (k > 0 && std::fabs(rmse - prev) <= P.rel_tol * prev) { R.status = S4P_ICP_CONVERGED; break; }
+    prev = rmse;
+  }
+  // final pass: the statistics of the returned transform
+  if (int32_t rc = robust_pass(h, to_float(T), src, plane, C, sums, info)) return rc;
+  R.n_corr = int64_t(info[4]);
+  R.rmse = sums[0] > 0.0 ? std::sqrt(sums[i_d2] / sums[0]) : 0.0;
+  R.fitness = double(R.n_corr) / double(h->n_q);
+  from_centred(T, h->c, T16_inout);
+  if (result) *result = R;
+  if (info_out) std::memcpy(info_out, info, sizeof(info));
+  return S4P_ICP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -934,6 +1331,8 @@ void s4p_icp_destroy(s4p_icp_ctx* h) {
   if (h->st) (void)hipStreamSynchronize(h->st);
   dfree(h->tgt); dfree(h->start); dfree(h->src); dfree(h->src_ord); dfree(h->slab); dfree(h->dsum); dfree(h->nrm); dfree(h->pslab);
   for (int a = 0; a < 3; ++a) dfree(h->qraw[a]);
+  dfree(h->rslot); dfree(h->rkey); dfree(h->rhist); dfree(h->rst); dfree(h->rsum);
+  if (h->rhsum) (void)hipHostFree(h->rhsum);
   if (h->hsum) (void)hipHostFree(h->hsum);
   if (h->ev) (void)hipEventDestroy(h->ev);
   if (h->st) (void)hipStreamDestroy(h->st);
@@ -1170,6 +1569,37 @@ int32_t s4p_icp_solve_plane(const double* sums, double* dT16) {
 
 int32_t s4p_icp_refine_plane(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
   return refine_impl(h, params, T16_inout, result, true);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// robust ICP (include/s4p_icp_robust.h)
+
+void s4p_icp_robust_defaults(s4p_icp_robust* r, int32_t loss) {
+  if (!r) return;
+  std::memset(r, 0, sizeof(*r));
+  r->loss = loss;
+  r->trim_fraction = 1.0;
+  r->scale = 0.0;
+  r->c = loss == S4P_ICP_LOSS_HUBER ? S4P_ICP_HUBER_C : (loss == S4P_ICP_LOSS_TUKEY ? S4P_ICP_TUKEY_C : 0.0);
+}
+
+int32_t s4p_icp_robust_sums(s4p_icp_ctx* h, const float* T16_centred, int32_t metric, const s4p_icp_robust* robust, double* sums,
+                            double* info) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "robust_sums: null argument");
+  const bool plane = metric == S4P_ICP_METRIC_PLANE;
+  if (int32_t rc = plane ? plane_ready(h) : ready(h)) return rc;
+  RobustCfg C;
+  if (int32_t rc = robust_cfg(h, metric, robust, &C)) return rc;
+  double inf[S4P_ICP_ROBUST_NINFO];
+  if (int32_t rc = robust_pass(h, centred_from_float16(T16_centred), h->src, plane, C, sums, inf)) return rc;
+  if (info) std::memcpy(info, inf, sizeof(inf));
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_refine_robust(s4p_icp_ctx* h, const s4p_icp_params* params, int32_t metric, const s4p_icp_robust* robust,
+                              double* T16_inout, s4p_icp_result* result, double* info_out) {
+  return refine_robust_impl(h, params, metric, robust, T16_inout, result, info_out);
 }
 
 }  // extern "C"
