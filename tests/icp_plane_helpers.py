@@ -37,6 +37,34 @@ class PlaneCPU:
         return k, c6
 
 
+LITERAL_SRC = os.path.join(ROOT, "tests", "icp_plane_cpu", "icp_normals_literal.cpp")
+
+
+def build_normals_literal(outdir):
+    """tests/icp_plane_cpu/icp_normals_literal.cpp: k_normals restated term by term, for bit-for-bit comparison."""
+    so = os.path.join(str(outdir), "libicp_normals_literal.so")
+    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", LITERAL_SRC, "-o", so])
+    L = C.CDLL(so)
+    vp = C.c_void_p
+    L.icp_normals_literal.restype = C.c_int32
+    L.icp_normals_literal.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_int32, vp, C.c_int64, vp, vp, vp, C.c_int32]
+
+    def normals(Pc, d, r, min_neighbours, which=None, threads=0):
+        """(float32 (m, 3) normals of the target indices `which` (all when None), grid dims, cell edge) for the centred target
+        Pc, set_target's max_distance d and estimate_normals' radius r."""
+        p = [np.ascontiguousarray(Pc[:, a], np.float32) for a in range(3)]
+        n = p[0].shape[0]
+        w = np.arange(n, dtype=np.int64) if which is None else np.ascontiguousarray(which, np.int64)
+        out = np.empty((len(w), 3), np.float32)
+        dims = np.zeros(3, np.int32); h = np.zeros(1, np.float64)
+        rc = L.icp_normals_literal(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, n, float(d), float(r), int(min_neighbours),
+                                   w.ctypes.data, len(w), out.ctypes.data, dims.ctypes.data, h.ctypes.data, int(threads))
+        assert rc == 0
+        return out, dims, float(h[0])
+
+    return normals
+
+
 def numpy_brute_cov(Pc, r):
     """The neighbourhood contract in numpy (float32 d2 in the contract's order): small clouds only."""
     Pc = np.asarray(Pc, np.float32)

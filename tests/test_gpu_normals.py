@@ -1,6 +1,7 @@
 """Normal estimation on the MI355X (include/s4p_normals.h): bit-exact against the CPU restatement (tests/normals_cpu) for
-k in {3, 8, 16, 32} with and without a radius on a bumpy cloud, a small lidar scene and a cloud with duplicated points, and
-through estimate_at; determinism and numpy / torch agreement; planes, spheres and the zero-normal cases; registration
+k in {3, 8, 16, 32} with and without a radius on a bumpy cloud, a small lidar scene and a cloud with duplicated points, at
+524 289 and 1.3 M points (k in {3, 16, 32}: grid-stride lanes take a second and third trip), and through
+estimate_at; determinism and numpy / torch agreement; planes, spheres and the zero-normal cases; registration
 parity of the -a filter with estimated normals; the command line's --estimate-normals."""
 import os
 import subprocess
@@ -80,6 +81,32 @@ def test_normals_equal_the_restatement_bit_for_bit(nrm, cpu, clouds, contexts, n
     # the hybrid radius really bounds: with it, some points lose neighbours at k = 32
     _, cnt = cpu.knn(X, 32, radius, queries=X[sample[:500]], threads=16)
     assert cnt.min() < 32
+
+
+@pytest.mark.parametrize("n", [524_289, 1_300_000])
+def test_normals_at_multi_trip_sizes_equal_the_restatement_bit_for_bit(nrm, cpu, n):
+    """Clouds above 2048 x 256 points, where a lane of every grid-stride kernel takes a second and a third trip: the first such
+    size and 1.3 M.  The sample always holds the last 256 indices (the ragged last trip)."""
+    from super4pcs_amd import datasets as D
+    X = D.bumpy_pair(n, overlap=0.5, delta=0.004, seed=11)[0]
+    assert len(X) == n > 2048 * 256
+    ctx = nrm.Normals(0)
+    ctx.set_cloud(X)
+    g = ctx.grid()
+    rng = np.random.default_rng(7)
+    sample = np.unique(np.concatenate([rng.choice(n - 256, size=3000 - 256, replace=False), np.arange(n - 256, n)]))
+    assert len(sample) == 3000
+    radius = np.float32(0.6 * g["spacing"])
+    print("bumpy %d: grid %s" % (n, g))
+    for k in (3, 16, 32):
+        for r in (None, radius):
+            G = ctx.estimate(k, r)
+            C = cpu.normals(X, k, r, queries=X[sample], threads=16)
+            diff = np.flatnonzero((_bits(G[sample]) != _bits(C)).any(1))
+            assert len(diff) == 0, (n, k, r, diff[:5], G[sample][diff[:3]], C[diff[:3]])
+            zero = ~C.any(1)
+            assert zero.mean() < 0.5
+    ctx.close()
 
 
 def test_estimate_at_equals_the_restatement(nrm, cpu, clouds, contexts):
