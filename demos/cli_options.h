@@ -24,7 +24,10 @@ struct Options {
   bool legacy_4pcs = false;                                  // -x
   int icp_iterations = 0;                                    // --icp  ICP refinement after the registration (0: off)
   double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
-  bool icp_plane = false;                                    // --icp-metric point|plane  (default point)
+  bool icp_plane = false;                                    // --icp-metric point|plane|gicp  (default point)
+  bool icp_gicp = false;                                     //   gicp: generalized ICP, normals of both clouds
+  double icp_gicp_epsilon = 1e-3;                            // --icp-gicp-epsilon e  (gicp; in [1e-6, 1])
+  bool icp_gicp_epsilon_set = false;
   double icp_normal_radius = -1;                             // --icp-normal-radius  (default: the ICP max distance)
   int icp_loss = 0;                                          // --icp-loss none|trimmed|huber|tukey  (0 1 2 3; default none)
   double icp_trim = -1;                                      // --icp-trim  (trimmed; default: the overlap -o)
@@ -70,9 +73,16 @@ inline const Flag* flag_table(size_t* n) {
          if (end == v[0] || *end != '\0' || !(d > 0)) o.bad_value = true; else o.icp_distance = d;
        }},
       {"--icp-metric", 1, [](Options& o, char** v) {
-         if (!std::strcmp(v[0], "point")) o.icp_plane = false;
-         else if (!std::strcmp(v[0], "plane")) o.icp_plane = true;
+         if (!std::strcmp(v[0], "point")) { o.icp_plane = false; o.icp_gicp = false; }
+         else if (!std::strcmp(v[0], "plane")) { o.icp_plane = true; o.icp_gicp = false; }
+         else if (!std::strcmp(v[0], "gicp")) { o.icp_plane = false; o.icp_gicp = true; }
          else o.bad_value = true;
+       }},
+      {"--icp-gicp-epsilon", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double e = std::strtod(v[0], &end);
+         o.icp_gicp_epsilon_set = true;
+         if (end == v[0] || *end != '\0' || !(e >= 1e-6) || !(e <= 1)) o.bad_value = true; else o.icp_gicp_epsilon = e;
        }},
       {"--icp-normal-radius", 1, [](Options& o, char** v) {
          char* end = nullptr;
@@ -133,6 +143,8 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.normals_radius_set && o.normals_k == 0) return Parse::Bad;    // the radius needs --estimate-normals
   if (o.icp_trim_set && o.icp_loss != 1) return Parse::Bad;            // --icp-trim needs --icp-loss trimmed
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
+  if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
+  if (o.icp_gicp_epsilon_set && !o.icp_gicp) return Parse::Bad;        // --icp-gicp-epsilon needs --icp-metric gicp
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -148,12 +160,13 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ -x (legacy 4PCS: not available in this build) ]\n");
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
   std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
-  std::fprintf(stderr, "\t[ --icp-metric point|plane (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
+  std::fprintf(stderr, "\t[ --icp-metric point|plane|gicp (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
+  std::fprintf(stderr, "\t[ --icp-gicp-epsilon e (gicp; 0.001, in [1e-6, 1]; gicp takes no --icp-loss) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss none|trimmed|huber|tukey (none) ] [ --icp-trim fraction (trimmed; -o) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss-scale s (huber, tukey; estimated) ]  (robust ICP)\n");
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
-  std::fprintf(stderr, "\t     them and --icp-metric plane uses P's when all are nonzero)\n");
+  std::fprintf(stderr, "\t     them and --icp-metric plane / gicp use P's (gicp: Q's too) when all are nonzero)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -1,8 +1,15 @@
-// RefineICP: point-to-point or point-to-plane ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
+// RefineICP: point-to-point, point-to-plane or generalized ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
 // documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
 // of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h,
-// include/s4p_icp_plane.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
+// include/s4p_icp_plane.h, include/s4p_icp_gicp.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
 // Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
+//
+// ICPMetric::Generalized needs normals of both clouds.  Q's own are used when every point of Q has a nonzero one.
+// ComputeTransformation moves Q's positions only and leaves its normals in the frame of the file, so RefineICP rotates them
+// by the linear part of `transformation` (in double, row by row as (m0 * x + m1 * y) + m2 * z) before the upload.  Otherwise
+// the normals are estimated on the moved Q as EstimateNormals does with k = 16 (algorithms/normals.h).  That one step binds
+// libsuper4pcs_normals.so at run time (the process's own copy when it is linked, else the library next to
+// libsuper4pcs_icp.so), so that programs which link -lsuper4pcs_icp alone keep building.
 //
 //   MatchSuper4PCS matcher(options, logger);
 //   matcher.ComputeTransformation(P, &Q, mat);           // Q is moved by mat
@@ -10,6 +17,8 @@
 //   RefineICP(P, &Q, mat, icp);                           // Q moved by the refinement too; mat <- dT * mat
 #ifndef S4P_FACADE_ICP_H_
 #define S4P_FACADE_ICP_H_
+
+#include <dlfcn.h>
 
 #include <cstdint>
 #include <memory>
@@ -20,11 +29,13 @@
 #include "s4p_icp.h"
 #include "s4p_icp_plane.h"
 #include "s4p_icp_robust.h"
+#include "s4p_icp_gicp.h"
+#include "s4p_normals.h"
 #include "super4pcs/algorithms/match4pcsBase.h"
 
 namespace GlobalRegistration {
 
-enum class ICPMetric { PointToPoint, PointToPlane };
+enum class ICPMetric { PointToPoint, PointToPlane, Generalized };
 enum class ICPLoss { None, Trimmed, Huber, Tukey };
 
 struct ICPOptions {
@@ -37,6 +48,9 @@ struct ICPOptions {
   // PointToPlane: P's normals when every point of P has a nonzero one, else normals estimated on the device from the
   // neighbours within normal_radius (<= 0: max_distance; at most max_distance) with at least 6 of them
   double normal_radius = -1.0;
+  // Generalized: target normals as for PointToPlane; source normals as described at the top of this header; the covariance
+  // parameter epsilon of include/s4p_icp_gicp.h, in [1e-6, 1].  Takes no loss.
+  double gicp_epsilon = S4P_ICP_GICP_EPSILON;
   // None: least squares over every pair within max_distance.  Trimmed keeps the pairs whose residual is at most the
   // ceil(trim_fraction |Q|)-th smallest; Huber / Tukey reweight with the scale loss_scale (<= 0: estimated on the device)
   ICPLoss loss = ICPLoss::None;
@@ -46,12 +60,45 @@ struct ICPOptions {
 
 struct ICPResult {
   int iterations = 0;
-  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane)
+  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane, generalized)
   int64_t n_corr = 0;
   double rmse = 0.0;
   double fitness = 0.0;             // n_corr / |Q|
   std::vector<double> rmse_history;
 };
+
+namespace detail {
+
+// EstimateNormals' computation (k nearest neighbours, no radius) on SoA positions, with libsuper4pcs_normals.so bound at run
+// time: out = n x 3 floats.
+inline void icp_knn_normals(const std::vector<float> (&c)[3], int k, int device, std::vector<float>* out) {
+  void* lib = nullptr;
+  auto sym = [&lib](const char* name) -> void* {
+    void* f = dlsym(RTLD_DEFAULT, name);
+    if (!f) {
+      if (!lib) lib = dlopen("libsuper4pcs_normals.so", RTLD_NOW | RTLD_GLOBAL);
+      if (lib) f = dlsym(lib, name);
+    }
+    if (!f) throw std::runtime_error(std::string("RefineICP: libsuper4pcs_normals.so is needed to estimate Q's normals (") + name + ")");
+    return f;
+  };
+  const auto create = reinterpret_cast<decltype(&s4p_normals_create)>(sym("s4p_normals_create"));
+  const auto destroy = reinterpret_cast<decltype(&s4p_normals_destroy)>(sym("s4p_normals_destroy"));
+  const auto last_error = reinterpret_cast<decltype(&s4p_normals_last_error)>(sym("s4p_normals_last_error"));
+  const auto set_cloud = reinterpret_cast<decltype(&s4p_normals_set_cloud)>(sym("s4p_normals_set_cloud"));
+  const auto estimate = reinterpret_cast<decltype(&s4p_normals_estimate)>(sym("s4p_normals_estimate"));
+  s4p_normals_ctx* h = nullptr;
+  if (create(device, &h) != S4P_NORMALS_OK) throw std::runtime_error(std::string("RefineICP (MI355X): ") + last_error(nullptr));
+  const int64_t n = int64_t(c[0].size());
+  out->resize(3 * size_t(n));
+  int32_t rc = set_cloud(h, c[0].data(), c[1].data(), c[2].data(), n);
+  if (rc == S4P_NORMALS_OK) rc = estimate(h, k, -1.f, out->data());
+  const std::string err = rc == S4P_NORMALS_OK ? std::string() : std::string(last_error(h));
+  destroy(h);
+  if (rc != S4P_NORMALS_OK) throw std::runtime_error("RefineICP (MI355X): " + err);
+}
+
+}  // namespace detail
 
 // Q as it stands after ComputeTransformation (already moved).  Finds dT, moves Q in place (in k_apply's rounding order)
 // and sets transformation <- dT * transformation.  Returns the fitness of the refined pose.  Throws std::runtime_error
@@ -59,6 +106,8 @@ struct ICPResult {
 inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, Match4PCSBase::MatrixRef transformation,
                        const ICPOptions& options, ICPResult* result = nullptr) {
   if (Q == nullptr || P.empty() || Q->empty()) throw std::invalid_argument("RefineICP: empty cloud");
+  const bool gicp = options.metric == ICPMetric::Generalized;
+  if (gicp && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the generalized metric takes no loss");
   struct Handle {
     s4p_icp_ctx* h = nullptr;
     ~Handle() { s4p_icp_destroy(h); }
@@ -78,7 +127,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
   H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
   const bool plane = options.metric == ICPMetric::PointToPlane;
-  if (plane) {
+  if (plane || gicp) {
     bool all = true;
     for (const Point3D& pt : P) {
       const auto& nv = pt.normal();
@@ -94,6 +143,29 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
       H.check(s4p_icp_estimate_normals(H.h, float(r), 6));
     }
   }
+  if (gicp) {
+    bool all = true;
+    for (const Point3D& pt : *Q) {
+      const auto& nv = pt.normal();
+      if (!(nv(0) != 0 || nv(1) != 0 || nv(2) != 0)) { all = false; break; }
+    }
+    std::vector<float> n[3];
+    for (int k = 0; k < 3; ++k) n[k].resize(Q->size());
+    if (all) {                                     // Q's own, rotated into the frame Q was moved to
+      double m[3][3];
+      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) m[a][b] = double(transformation(a, b));
+      for (size_t i = 0; i < Q->size(); ++i) {
+        const auto& nv = (*Q)[i].normal();
+        const double x = double(nv(0)), y = double(nv(1)), z = double(nv(2));
+        for (int a = 0; a < 3; ++a) n[a][i] = float((m[a][0] * x + m[a][1] * y) + m[a][2] * z);
+      }
+    } else {
+      std::vector<float> est;
+      detail::icp_knn_normals(q, 16, options.device, &est);
+      for (size_t i = 0; i < Q->size(); ++i) for (int k = 0; k < 3; ++k) n[k][i] = est[3 * i + k];
+    }
+    H.check(s4p_icp_set_source_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(Q->size())));
+  }
   s4p_icp_params prm;
   s4p_icp_default_params(&prm);
   prm.max_iterations = options.max_iterations;
@@ -102,7 +174,8 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   s4p_icp_result r;
   if (options.loss == ICPLoss::None) {
-    H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
+    if (gicp) H.check(s4p_icp_refine_gicp(H.h, &prm, options.gicp_epsilon, dT, &r));
+    else H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
   } else {
     const int32_t loss = options.loss == ICPLoss::Trimmed ? S4P_ICP_LOSS_TRIMMED
                          : (options.loss == ICPLoss::Huber ? S4P_ICP_LOSS_HUBER : S4P_ICP_LOSS_TUKEY);

@@ -1,10 +1,12 @@
-"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h and include/s4p_icp_robust.h (libsuper4pcs_icp.so):
-point-to-point and point-to-plane ICP refinement on the full-resolution clouds, with optional robust losses.
+"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h and include/s4p_icp_gicp.h
+(libsuper4pcs_icp.so): point-to-point, point-to-plane and generalized (plane-to-plane) ICP refinement on the full-resolution
+clouds, with optional robust losses for the first two.
 
     from super4pcs_amd import icp
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="plane")   # target normals estimated on the device
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, loss="trimmed", trim_fraction=0.6)   # trimmed ICP
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="gicp")    # normals of both clouds (given or estimated)
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -27,6 +29,9 @@ STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged", TOO_FE
 ERR_DEGENERATE = -8
 ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE", ERR_DEGENERATE: "DEGENERATE"}
 METRICS = ("point", "plane")
+REFINE_METRICS = METRICS + ("gicp",)     # "gicp": include/s4p_icp_gicp.h, no robust losses
+GICP_NSUMS = PLANE_NSUMS
+GICP_EPSILON = 1e-3
 MIN_NEIGHBOURS = 6              # estimate_normals' default
 LOSSES = {"trimmed": 1, "huber": 2, "tukey": 3}             # S4P_ICP_LOSS_*
 LOSS_C = {"huber": 1.345, "tukey": 4.685}                   # default tuning constants
@@ -43,6 +48,10 @@ PLANE_SYMBOLS = [                                          # include/s4p_icp_pla
 ]
 ROBUST_SYMBOLS = [                                         # include/s4p_icp_robust.h
     "s4p_icp_robust_defaults", "s4p_icp_robust_sums", "s4p_icp_refine_robust",
+]
+GICP_SYMBOLS = [                                           # include/s4p_icp_gicp.h
+    "s4p_icp_set_source_normals", "s4p_icp_set_source_normals_device", "s4p_icp_source_normals", "s4p_icp_gicp_sums",
+    "s4p_icp_refine_gicp",
 ]
 
 
@@ -129,6 +138,15 @@ def load_library():
     L.s4p_icp_robust_sums.argtypes = [vp, fp, C.c_int32, C.POINTER(Robust), dp, dp]
     L.s4p_icp_refine_robust.restype = C.c_int32
     L.s4p_icp_refine_robust.argtypes = [vp, C.POINTER(Params), C.c_int32, C.POINTER(Robust), dp, C.POINTER(Result), dp]
+    for name in ("s4p_icp_set_source_normals", "s4p_icp_set_source_normals_device"):
+        getattr(L, name).restype = C.c_int32
+        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.s4p_icp_source_normals.restype = C.c_int32
+    L.s4p_icp_source_normals.argtypes = [vp, fp, fp, fp]
+    L.s4p_icp_gicp_sums.restype = C.c_int32
+    L.s4p_icp_gicp_sums.argtypes = [vp, fp, C.c_double, dp]
+    L.s4p_icp_refine_gicp.restype = C.c_int32
+    L.s4p_icp_refine_gicp.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
     _LIB = L
     return L
 
@@ -203,6 +221,13 @@ def compose(A, B):
 
 def _is_torch(t):
     return type(t).__module__.startswith("torch")
+
+
+def _check_metric(metric, loss):
+    if metric not in REFINE_METRICS:
+        raise ValueError("metric must be one of %s" % (REFINE_METRICS,))
+    if metric == "gicp" and loss is not None:
+        raise ValueError("metric \"gicp\" takes no loss (robust losses cover \"point\" and \"plane\")")
 
 
 class ICP:
@@ -295,6 +320,27 @@ class ICP:
         self._chk(self.L.s4p_icp_plane_sums(self.h, _fp(T), _dp(out)))
         return out
 
+    def set_source_normals(self, N):
+        """One normal per source point (N, 3), in the uploaded order and the frame of the source as uploaded (the library
+        rotates them with T): normalised in double, zero / non-finite -> 0.  set_source invalidates them."""
+        suf, ptr, n, keep = self._cols(N)
+        self._chk(getattr(self.L, "s4p_icp_set_source_normals" + suf)(self.h, ptr[0], ptr[1], ptr[2], n))
+        del keep
+
+    def source_normals(self):
+        """float32 (n_Q, 3): the stored source normals, in the uploaded order."""
+        n = self.n_q
+        cols = [np.empty(n, np.float32) for _ in range(3)]
+        self._chk(self.L.s4p_icp_source_normals(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
+        return np.stack(cols, axis=1)
+
+    def gicp_sums(self, T, epsilon=GICP_EPSILON):
+        """The 31 generalized sums for a float T in the centred frame (layout in include/s4p_icp_gicp.h)."""
+        T = self._t32(T)
+        out = np.empty(GICP_NSUMS, np.float64)
+        self._chk(self.L.s4p_icp_gicp_sums(self.h, _fp(T), float(epsilon), _dp(out)))
+        return out
+
     def correspondences(self, T):
         """(idx int32[n_Q], d2 float32[n_Q]) for a float T in the centred frame; idx -1 where nothing is within d."""
         T = self._t32(T)
@@ -322,13 +368,14 @@ class ICP:
         return out, info
 
     def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True, metric="point",
-               loss=None, trim_fraction=None, loss_scale=None, loss_c=None, info=None):
+               loss=None, trim_fraction=None, loss_scale=None, loss_c=None, info=None, gicp_epsilon=GICP_EPSILON):
         """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity).  metric "plane"
-        minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals).  loss
-        "trimmed" / "huber" / "tukey" refines on the weighted sums (include/s4p_icp_robust.h); loss=None is the plain
-        refine.  info: an optional float64 array of 8 that receives the final pass's robust info."""
-        if metric not in METRICS:
-            raise ValueError("metric must be one of %s" % (METRICS,))
+        minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals); metric
+        "gicp" is generalized ICP (include/s4p_icp_gicp.h) with the covariance parameter gicp_epsilon in [1e-6, 1], needs
+        source normals too (set_source_normals) and takes no loss.  loss "trimmed" / "huber" / "tukey" refines on the
+        weighted sums (include/s4p_icp_robust.h); loss=None is the plain refine.  info: an optional float64 array of 8 that
+        receives the final pass's robust info."""
+        _check_metric(metric, loss)
         if loss is None and (trim_fraction is not None or loss_scale is not None or loss_c is not None or info is not None):
             raise ValueError("trim_fraction / loss_scale / loss_c / info need a loss")
         rob = None if loss is None else robust_params(loss, trim_fraction, loss_scale, loss_c)
@@ -344,6 +391,9 @@ class ICP:
             if info is not None:
                 info[:] = inf
             return T.reshape(4, 4), r
+        if metric == "gicp":
+            self._chk(self.L.s4p_icp_refine_gicp(self.h, C.byref(p), float(gicp_epsilon), _dp(T), C.byref(r)))
+            return T.reshape(4, 4), r
         fn = self.L.s4p_icp_refine_plane if metric == "plane" else self.L.s4p_icp_refine
         self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
         return T.reshape(4, 4), r
@@ -357,23 +407,30 @@ class ICP:
         return np.stack(cols, axis=1)
 
 
-def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None, **params):
-    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane": the
-    target normals are target_normals if given, else estimated within normal_radius (default max_distance).  params go to
-    ICP.refine, the robust ones (loss, trim_fraction, loss_scale, loss_c) included."""
+def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None,
+           source_normals=None, normal_k=16, **params):
+    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane" and "gicp":
+    the target normals are target_normals if given, else estimated within normal_radius (default max_distance).  metric
+    "gicp": the source normals (in Q's frame as given) are source_normals if given, else the normal_k-nearest-neighbour
+    normals of Q (super4pcs_amd.normals.estimate_normals).  params go to ICP.refine, the robust ones (loss, trim_fraction,
+    loss_scale, loss_c) and gicp_epsilon included."""
     if max_distance is None:
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
-    if metric not in METRICS:
-        raise ValueError("metric must be one of %s" % (METRICS,))
+    _check_metric(metric, params.get("loss"))
+    if metric == "gicp" and source_normals is None:
+        from super4pcs_amd import normals
+        source_normals = normals.estimate_normals(Q, k=normal_k)
     ctx = ICP(device)
     try:
         ctx.set_target(P, max_distance)
         ctx.set_source(Q)
-        if metric == "plane":
+        if metric in ("plane", "gicp"):
             if target_normals is not None:
                 ctx.set_target_normals(target_normals)
             else:
                 ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
+        if metric == "gicp":
+            ctx.set_source_normals(source_normals)
         return ctx.refine(T0, metric=metric, **params)
     finally:
         ctx.close()

@@ -1,6 +1,6 @@
 // s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point and point-to-plane ICP on the full-resolution clouds, with robust
-// losses (include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, DESIGN.md sections "ICP refinement",
-// "Point-to-plane ICP" and "Robust ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
+// losses and generalized ICP (include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
+// DESIGN.md sections "ICP refinement", "Point-to-plane ICP", "Robust ICP" and "Generalized ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
 //
 // Device path:
 //   set_target   k_stats (per-block double sums and float bounds of P) -> host frame c and grid plan ->
@@ -13,6 +13,8 @@
 //                k_gather_normals (the caller's); per iteration k_match_plane (31 double sums) + k_final_plane, host solve.
 //   robust       (include/s4p_icp_robust.h) per iteration k_search (winner slot + residual key per lane), the radix select of
 //                the keys (k_key_hist + k_key_digit x 4, on the device), k_wsum + k_wfinal (weighted sums), host solve.
+//   generalized  (include/s4p_icp_gicp.h) source normals in the order of the source (k_gather_source_normals); per iteration
+//                k_search (winner slot per lane), k_gicp_sum (31 double sums streamed from the slots) + k_final_plane, host solve.
 // No float or double atomics anywhere (the selection's histograms use integer atomics): every sum has a fixed order, so two calls return identical bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -28,6 +30,7 @@
 #include "s4p_icp.h"
 #include "s4p_icp_plane.h"
 #include "s4p_icp_robust.h"
+#include "s4p_icp_gicp.h"
 
 namespace s4p_icp {
 
@@ -525,6 +528,112 @@ __global__ __launch_bounds__(kBlock) void k_match_plane(PlaneArgs A) {
   }
 }
 
+// generalized ICP (include/s4p_icp_gicp.h).  Per iteration: k_search<false> (the one correspondence search: the winner's
+// slot per visited lane), k_gicp_sum (the 31 generalized sums streamed from the slots, k_match_plane's reduction) and
+// k_final_plane (the same slab pitch and fixed order).  Defined before k_final_plane, which stays the last non-template
+// kernel of the translation unit (cf. the robust kernels above).
+
+// source normals (uploaded order, already normalised) -> the order of `src` (w = original source index), next to it.
+// The uploaded-order copy stays on the device, so the read-back needs no scatter.
+__global__ __launch_bounds__(kBlock) void k_gather_source_normals(const float* x, const float* y, const float* z, const float4* src,
+                                                                  uint64_t n, float4* snrm) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t j = __float_as_uint(src[k].w);
+    snrm[k] = make_float4(x[j], y[j], z[j], 0.f);
+  }
+}
+
+struct GicpArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;
+  const float4* snrm;       // the order of src
+  const float4* nrm;        // cell order, as g.tgt
+  uint64_t n;
+  const uint32_t* slot;     // k_search's
+  double k;                 // 1 - epsilon
+  double* slab;             // one kPlanePitch row per workgroup
+};
+
+// The generalized sums, term by term as include/s4p_icp_gicp.h states them.  No search: the winner comes from k_search's slot.
+__global__ __launch_bounds__(kBlock) void k_gicp_sum(GicpArgs A) {
+  constexpr int NS = S4P_ICP_PLANE_NSUMS;
+  double s[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = 0.0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t sl = A.slot[j];
+    if (sl == kNoSlot) continue;
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    const float4 p = A.g.tgt[sl];
+    const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
+    const float d2 = dx * dx + (dy * dy + dz * dz);           // nearest_t's float d2 of the winner
+    const float4 nf = A.nrm[sl], mf = A.snrm[j];
+    const double qd[3] = {double(x), double(y), double(z)}, np[3] = {double(nf.x), double(nf.y), double(nf.z)};
+    const double mq[3] = {double(mf.x), double(mf.y), double(mf.z)};
+    double nh[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) nh[a] = (double(A.T.m[4 * a]) * mq[0] + double(A.T.m[4 * a + 1]) * mq[1]) + double(A.T.m[4 * a + 2]) * mq[2];
+    const double S00 = (2.0 - A.k * (np[0] * np[0])) - A.k * (nh[0] * nh[0]);
+    const double S01 = (0.0 - A.k * (np[0] * np[1])) - A.k * (nh[0] * nh[1]);
+    const double S02 = (0.0 - A.k * (np[0] * np[2])) - A.k * (nh[0] * nh[2]);
+    const double S11 = (2.0 - A.k * (np[1] * np[1])) - A.k * (nh[1] * nh[1]);
+    const double S12 = (0.0 - A.k * (np[1] * np[2])) - A.k * (nh[1] * nh[2]);
+    const double S22 = (2.0 - A.k * (np[2] * np[2])) - A.k * (nh[2] * nh[2]);
+    const double c00 = S11 * S22 - S12 * S12, c01 = S02 * S12 - S01 * S22, c02 = S01 * S12 - S02 * S11;
+    const double c11 = S00 * S22 - S02 * S02, c12 = S01 * S02 - S00 * S12, c22 = S00 * S11 - S01 * S01;
+    const double det = (S00 * c00 + S01 * c01) + S02 * c02;
+    double M[3][3];
+    M[0][0] = c00 / det; M[0][1] = c01 / det; M[0][2] = c02 / det; M[1][1] = c11 / det; M[1][2] = c12 / det; M[2][2] = c22 / det;
+    M[1][0] = M[0][1]; M[2][0] = M[0][2]; M[2][1] = M[1][2];
+    const double r[3] = {double(p.x) - qd[0], double(p.y) - qd[1], double(p.z) - qd[2]};
+    double g[3], B[3][3], W[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) g[a] = (M[a][0] * r[0] + M[a][1] * r[1]) + M[a][2] * r[2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      B[0][c] = qd[1] * M[2][c] - qd[2] * M[1][c];
+      B[1][c] = qd[2] * M[0][c] - qd[0] * M[2][c];
+      B[2][c] = qd[0] * M[1][c] - qd[1] * M[0][c];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      W[a][0] = qd[1] * B[a][2] - qd[2] * B[a][1];
+      W[a][1] = qd[2] * B[a][0] - qd[0] * B[a][2];
+      W[a][2] = qd[0] * B[a][1] - qd[1] * B[a][0];
+    }
+    s[0] += 1.0;
+    s[1] += double(d2);
+    s[2] += 1.0;
+    s[3] += (r[0] * g[0] + r[1] * g[1]) + r[2] * g[2];
+    s[4] += W[0][0]; s[5] += W[0][1]; s[6] += W[0][2]; s[7] += B[0][0]; s[8] += B[0][1]; s[9] += B[0][2];
+    s[10] += W[1][1]; s[11] += W[1][2]; s[12] += B[1][0]; s[13] += B[1][1]; s[14] += B[1][2];
+    s[15] += W[2][2]; s[16] += B[2][0]; s[17] += B[2][1]; s[18] += B[2][2];
+    s[19] += M[0][0]; s[20] += M[0][1]; s[21] += M[0][2]; s[22] += M[1][1]; s[23] += M[1][2]; s[24] += M[2][2];
+    s[25] += qd[1] * g[2] - qd[2] * g[1];
+    s[26] += qd[2] * g[0] - qd[0] * g[2];
+    s[27] += qd[0] * g[1] - qd[1] * g[0];
+    s[28] += g[0]; s[29] += g[1]; s[30] += g[2];
+  }
+  __shared__ double red[kBlock / 64][NS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    double v = s[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    double v = red[0][threadIdx.x];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][threadIdx.x];
+    A.slab[uint64_t(blockIdx.x) * kPlanePitch + threadIdx.x] = v;
+  }
+}
+
 // the plane slab's nb rows -> 31 sums, in a fixed order: 8 parts per column (rows part, part + 8, ...), then the parts in order
 __global__ __launch_bounds__(kBlock) void k_final_plane(const double* slab, int nb, double* out) {
   constexpr int kParts = kBlock / S4P_ICP_PLANE_NSUMS;     // 8
@@ -813,6 +922,11 @@ struct s4p_icp_ctx {
   SelState* rst = nullptr;
   double* rsum = nullptr;            // sums + info
   double* rhsum = nullptr;           // pinned
+  // generalized ICP (include/s4p_icp_gicp.h)
+  int64_t sn_n = 0;                  // entries of sn / snrm
+  float* sn[3] = {nullptr, nullptr, nullptr};   // source normals as stored, uploaded order
+  float4* snrm = nullptr;            // the same in the order of the pass's source
+  bool has_src_normals = false;
 };
 
 namespace {
@@ -958,6 +1072,7 @@ int32_t set_source_impl(s4p_icp_ctx* h, const float* x, const float* y, const fl
   if (n >= int64_t(0x7FFFFFFF)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source: more than 2^31 - 1 points");
   ICP_HIP(hipSetDevice(h->device));
   h->has_source = false;
+  h->has_src_normals = false;
   if (n != h->n_q) {
     for (int a = 0; a < 3; ++a) { dfree(h->qraw[a]); h->qraw[a] = nullptr; }
     dfree(h->src); dfree(h->src_ord); h->src = h->src_ord = nullptr;
@@ -1123,10 +1238,8 @@ int32_t alloc_normals(s4p_icp_ctx* h) {
   return S4P_ICP_OK;
 }
 
-// caller normals in the uploaded order (host): normalised in double, rounded to float; zero or non-finite -> (0, 0, 0)
-int32_t set_normals_host(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz) {
-  const size_t n = size_t(h->n_p);
-  std::vector<float> v[3];
+// normalised in double, rounded to float; zero or non-finite -> (0, 0, 0)
+void normalise_host(const float* nx, const float* ny, const float* nz, size_t n, std::vector<float> (&v)[3]) {
   for (int a = 0; a < 3; ++a) v[a].assign(n, 0.f);
   for (size_t i = 0; i < n; ++i) {
     const double x = nx[i], y = ny[i], z = nz[i];
@@ -1134,6 +1247,13 @@ int32_t set_normals_host(s4p_icp_ctx* h, const float* nx, const float* ny, const
     if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(z) || !(len > 0.0) || !std::isfinite(len)) continue;
     v[0][i] = float(x / len); v[1][i] = float(y / len); v[2][i] = float(z / len);
   }
+}
+
+// caller normals in the uploaded order (host)
+int32_t set_normals_host(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz) {
+  const size_t n = size_t(h->n_p);
+  std::vector<float> v[3];
+  normalise_host(nx, ny, nz, n, v);
   if (int32_t rc = alloc_normals(h)) return rc;
   Scratch S;
   float* d[3];
@@ -1146,6 +1266,72 @@ int32_t set_normals_host(s4p_icp_ctx* h, const float* nx, const float* ny, const
   ICP_HIP(hipGetLastError());
   ICP_HIP(hipStreamSynchronize(h->st));
   h->has_normals = true;
+  return S4P_ICP_OK;
+}
+
+// source normals in the uploaded order (host): stored on the device as they are read back
+int32_t set_source_normals_host(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz) {
+  const size_t n = size_t(h->n_q);
+  std::vector<float> v[3];
+  normalise_host(nx, ny, nz, n, v);
+  h->has_src_normals = false;
+  if (h->sn_n != h->n_q) {
+    for (int a = 0; a < 3; ++a) { dfree(h->sn[a]); h->sn[a] = nullptr; }
+    dfree(h->snrm); h->snrm = nullptr;
+    h->sn_n = 0;
+    for (int a = 0; a < 3; ++a) ICP_HIP(hipMalloc((void**)&h->sn[a], n * sizeof(float)));
+    ICP_HIP(hipMalloc((void**)&h->snrm, n * sizeof(float4)));
+    h->sn_n = h->n_q;
+  }
+  for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(h->sn[a], v[a].data(), n * sizeof(float), hipMemcpyHostToDevice, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));          // v is released on return
+  h->has_src_normals = true;
+  return S4P_ICP_OK;
+}
+
+int32_t gicp_ready(s4p_icp_ctx* h, double epsilon) {
+  if (!(epsilon >= S4P_ICP_GICP_EPSILON_MIN && epsilon <= S4P_ICP_GICP_EPSILON_MAX))
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "gicp: epsilon must be in [1e-6, 1]");
+  if (int32_t rc = plane_ready(h)) return rc;
+  if (!h->has_src_normals) return fail(h, S4P_ICP_ERR_STATE, "source normals first (set_source_normals)");
+  return S4P_ICP_OK;
+}
+
+// the buffers of a generalized pass (none is allocated inside the iteration loop) and the source normals in src's order
+int32_t gicp_prepare(s4p_icp_ctx* h, const float4* src) {
+  const uint64_t un = uint64_t(h->n_q);
+  if (h->r_n != h->n_q) {
+    dfree(h->rslot); dfree(h->rkey); h->rslot = h->rkey = nullptr;
+    h->r_n = 0;
+    ICP_HIP(hipMalloc((void**)&h->rslot, un * sizeof(uint32_t)));
+    ICP_HIP(hipMalloc((void**)&h->rkey, un * sizeof(uint32_t)));
+    h->r_n = h->n_q;
+  }
+  if (!h->pslab) ICP_HIP(hipMalloc((void**)&h->pslab, size_t(kMaxBlocks) * kPlanePitch * sizeof(double)));
+  hipLaunchKernelGGL(k_gather_source_normals, dim3(blocks_for(h->n_q)), dim3(kBlock), 0, h->st, (const float*)h->sn[0],
+                     (const float*)h->sn[1], (const float*)h->sn[2], src, un, h->snrm);
+  ICP_HIP(hipGetLastError());
+  return S4P_ICP_OK;
+}
+
+// one generalized pass over `src` for T (after gicp_prepare for this src): the 31 sums on the host
+int32_t gicp_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double epsilon, double* out) {
+  const int nb = blocks_for(h->n_q);
+  SearchArgs S;
+  S.T = T; S.g = h->g; S.src = src; S.nrm = h->nrm; S.n = uint64_t(h->n_q); S.d2max = h->d2max; S.slot = h->rslot; S.key = h->rkey;
+  hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, S);
+  ICP_HIP(hipGetLastError());
+  GicpArgs A;
+  A.T = T; A.g = h->g; A.src = src; A.snrm = h->snrm; A.nrm = h->nrm; A.n = uint64_t(h->n_q); A.slot = h->rslot;
+  A.k = 1.0 - epsilon; A.slab = h->pslab;
+  hipLaunchKernelGGL(k_gicp_sum, dim3(nb), dim3(kBlock), 0, h->st, A);
+  ICP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_final_plane, dim3(1), dim3(kBlock), 0, h->st, (const double*)h->pslab, nb, h->dsum);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(h->hsum, h->dsum, S4P_ICP_GICP_NSUMS * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipEventRecord(h->ev, h->st));
+  ICP_HIP(hipEventSynchronize(h->ev));
+  std::memcpy(out, h->hsum, S4P_ICP_GICP_NSUMS * sizeof(double));
   return S4P_ICP_OK;
 }
 
@@ -1180,9 +1366,13 @@ Tf centred_from_float16(const float* T16) {
 
 namespace {
 
-// The refine loop of both metrics.  plane: the 31 plane sums (sum d2 at [1]) and s4p_icp_solve_plane, whose degenerate
-// system stops the loop with T_k; otherwise the 17 sums (sum d2 at [16]) and Horn's solve.
-int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result, bool plane) {
+enum RefineMetric { kRefinePoint = 0, kRefinePlane = 1, kRefineGicp = 2 };
+
+// The refine loop of the three metrics.  plane / generalized: the 31 sums (sum d2 at [1]) and s4p_icp_solve_plane, whose
+// degenerate system stops the loop with T_k; otherwise the 17 sums (sum d2 at [16]) and Horn's solve.
+int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result, int metric,
+                    double epsilon = 0.0) {
+  const bool gicp = metric == kRefineGicp, plane = metric != kRefinePoint;
   if (!h) return S4P_ICP_ERR_BAD_ARG;
   if (!T16_inout) return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: null transform");
   s4p_icp_params P;
@@ -1190,15 +1380,19 @@ int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_in
   if (params) P = *params;
   if (P.max_iterations < 0 || P.min_correspondences < 0 || !(P.rel_tol >= 0.0))
     return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: negative max_iterations / min_correspondences / rel_tol");
-  if (int32_t rc = plane ? plane_ready(h) : ready(h)) return rc;
+  if (int32_t rc = gicp ? gicp_ready(h, epsilon) : (plane ? plane_ready(h) : ready(h))) return rc;
   s4p_icp_result R;
   std::memset(&R, 0, sizeof(R));
   double T[16], Tn[16], dT[16], sums[kSumsCap];
   const int i_d2 = plane ? 1 : 16;
-  auto run_pass = [&](const float4* src) { return plane ? plane_pass(h, to_float(T), src, sums) : pass(h, to_float(T), src, nullptr, nullptr, sums); };
+  auto run_pass = [&](const float4* src) {
+    if (gicp) return gicp_pass(h, to_float(T), src, epsilon, sums);
+    return plane ? plane_pass(h, to_float(T), src, sums) : pass(h, to_float(T), src, nullptr, nullptr, sums);
+  };
   to_centred(T16_inout, h->c, T);
   const float4* src = nullptr;
   if (int32_t rc = source_for(h, P, T, &src)) return rc;
+  if (gicp) if (int32_t rc = gicp_prepare(h, src)) return rc;      // the normals follow the source's order
   double prev = 0.0;
   R.status = S4P_ICP_MAX_ITERATIONS;
   for (int k = 0; k < P.max_iterations; ++k) {
@@ -1332,6 +1526,8 @@ void s4p_icp_destroy(s4p_icp_ctx* h) {
   dfree(h->tgt); dfree(h->start); dfree(h->src); dfree(h->src_ord); dfree(h->slab); dfree(h->dsum); dfree(h->nrm); dfree(h->pslab);
   for (int a = 0; a < 3; ++a) dfree(h->qraw[a]);
   dfree(h->rslot); dfree(h->rkey); dfree(h->rhist); dfree(h->rst); dfree(h->rsum);
+  for (int a = 0; a < 3; ++a) dfree(h->sn[a]);
+  dfree(h->snrm);
   if (h->rhsum) (void)hipHostFree(h->rhsum);
   if (h->hsum) (void)hipHostFree(h->hsum);
   if (h->ev) (void)hipEventDestroy(h->ev);
@@ -1416,7 +1612,7 @@ int32_t s4p_icp_solve(const double* sums, double* dT16) {
 }
 
 int32_t s4p_icp_refine(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
-  return refine_impl(h, params, T16_inout, result, false);
+  return refine_impl(h, params, T16_inout, result, kRefinePoint);
 }
 
 int32_t s4p_icp_apply(s4p_icp_ctx* h, const double* T16, float* x, float* y, float* z, int64_t n) {
@@ -1568,7 +1764,7 @@ int32_t s4p_icp_solve_plane(const double* sums, double* dT16) {
 }
 
 int32_t s4p_icp_refine_plane(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
-  return refine_impl(h, params, T16_inout, result, true);
+  return refine_impl(h, params, T16_inout, result, kRefinePlane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1600,6 +1796,55 @@ int32_t s4p_icp_robust_sums(s4p_icp_ctx* h, const float* T16_centred, int32_t me
 int32_t s4p_icp_refine_robust(s4p_icp_ctx* h, const s4p_icp_params* params, int32_t metric, const s4p_icp_robust* robust,
                               double* T16_inout, s4p_icp_result* result, double* info_out) {
   return refine_robust_impl(h, params, metric, robust, T16_inout, result, info_out);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// generalized ICP (include/s4p_icp_gicp.h)
+
+int32_t s4p_icp_set_source_normals(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_source) return fail(h, S4P_ICP_ERR_STATE, "set_source_normals: set_source first");
+  if (!nx || !ny || !nz || n != h->n_q) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source_normals: null or not one per source point");
+  ICP_HIP(hipSetDevice(h->device));
+  return set_source_normals_host(h, nx, ny, nz);
+}
+
+int32_t s4p_icp_set_source_normals_device(s4p_icp_ctx* h, const float* nx, const float* ny, const float* nz, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_source) return fail(h, S4P_ICP_ERR_STATE, "set_source_normals: set_source first");
+  if (!nx || !ny || !nz || n != h->n_q) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source_normals: null or not one per source point");
+  ICP_HIP(hipSetDevice(h->device));
+  // normalised on the host, as for host input: both entry points store the same bits
+  std::vector<float> v[3];
+  const float* in[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a) {
+    v[a].resize(size_t(n));
+    ICP_HIP(hipMemcpy(v[a].data(), in[a], size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  return set_source_normals_host(h, v[0].data(), v[1].data(), v[2].data());
+}
+
+int32_t s4p_icp_source_normals(s4p_icp_ctx* h, float* nx, float* ny, float* nz) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!nx || !ny || !nz) return fail(h, S4P_ICP_ERR_BAD_ARG, "source_normals: null argument");
+  if (!h->has_source || !h->has_src_normals) return fail(h, S4P_ICP_ERR_STATE, "source_normals: no normals");
+  ICP_HIP(hipSetDevice(h->device));
+  float* out[3] = {nx, ny, nz};
+  for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(out[a], h->sn[a], size_t(h->n_q) * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_gicp_sums(s4p_icp_ctx* h, const float* T16_centred, double epsilon, double* sums) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "gicp_sums: null argument");
+  if (int32_t rc = gicp_ready(h, epsilon)) return rc;
+  if (int32_t rc = gicp_prepare(h, h->src)) return rc;
+  return gicp_pass(h, centred_from_float16(T16_centred), h->src, epsilon, sums);
+}
+
+int32_t s4p_icp_refine_gicp(s4p_icp_ctx* h, const s4p_icp_params* params, double epsilon, double* T16_inout, s4p_icp_result* result) {
+  return refine_impl(h, params, T16_inout, result, kRefineGicp, epsilon);
 }
 
 }  // extern "C"
