@@ -4,14 +4,16 @@
 // options, 255 (-1) unreadable input.
 //   Super4PCS -i P.obj Q.obj [-o overlap] [-d delta] [-n samples] [-t seconds] [-a normal_deg] [-c colour]
 //             [-r registered_geometry] [-m polyworks_matrix] [--sampled1 file] [--sampled2 file]
-//             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane|gicp] [--icp-normal-radius r]
-//             [--icp-gicp-epsilon e]
+//             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane|gicp|color] [--icp-normal-radius r]
+//             [--icp-gicp-epsilon e] [--icp-color-lambda l]
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
 // normals as for plane, Q's own when all are nonzero (after --estimate-normals they are), else estimated with k = 16; no --icp-loss.
+// With --icp-metric color it is coloured ICP (include/s4p_icp_color.h, weight of the geometric term --icp-color-lambda): P's
+// normals as for plane, the colours of both inputs (a coloured PLY or a PTX), gradients within --icp-normal-radius; no --icp-loss.
 // --icp-loss refines with a robust loss (include/s4p_icp_robust.h): trimmed keeps the --icp-trim fraction of |Q| (default
 // the overlap -o) with the smallest residuals, huber / tukey reweight with --icp-loss-scale (default estimated on the device).
 // --estimate-normals k gives both inputs k-nearest-neighbour normals (algorithms/normals.h, within r if given) before the
@@ -108,6 +110,8 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       icp.max_iterations = opt.icp_iterations;
       icp.max_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
       icp.metric = opt.icp_gicp ? ICPMetric::Generalized : (opt.icp_plane ? ICPMetric::PointToPlane : ICPMetric::PointToPoint);
+      if (opt.icp_color) icp.metric = ICPMetric::Colored;
+      icp.color_lambda = opt.icp_color_lambda;
       icp.gicp_epsilon = opt.icp_gicp_epsilon;
       icp.normal_radius = opt.icp_normal_radius;
       icp.loss = opt.icp_loss == 1 ? ICPLoss::Trimmed : (opt.icp_loss == 2 ? ICPLoss::Huber : (opt.icp_loss == 3 ? ICPLoss::Tukey : ICPLoss::None));

@@ -24,8 +24,11 @@ struct Options {
   bool legacy_4pcs = false;                                  // -x
   int icp_iterations = 0;                                    // --icp  ICP refinement after the registration (0: off)
   double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
-  bool icp_plane = false;                                    // --icp-metric point|plane|gicp  (default point)
+  bool icp_plane = false;                                    // --icp-metric point|plane|gicp|color  (default point)
   bool icp_gicp = false;                                     //   gicp: generalized ICP, normals of both clouds
+  bool icp_color = false;                                    //   color: coloured ICP, the colours of both clouds
+  double icp_color_lambda = 0.968;                           // --icp-color-lambda l  (color; in [0, 1])
+  bool icp_color_lambda_set = false;
   double icp_gicp_epsilon = 1e-3;                            // --icp-gicp-epsilon e  (gicp; in [1e-6, 1])
   bool icp_gicp_epsilon_set = false;
   double icp_normal_radius = -1;                             // --icp-normal-radius  (default: the ICP max distance)
@@ -73,10 +76,18 @@ inline const Flag* flag_table(size_t* n) {
          if (end == v[0] || *end != '\0' || !(d > 0)) o.bad_value = true; else o.icp_distance = d;
        }},
       {"--icp-metric", 1, [](Options& o, char** v) {
-         if (!std::strcmp(v[0], "point")) { o.icp_plane = false; o.icp_gicp = false; }
-         else if (!std::strcmp(v[0], "plane")) { o.icp_plane = true; o.icp_gicp = false; }
-         else if (!std::strcmp(v[0], "gicp")) { o.icp_plane = false; o.icp_gicp = true; }
+         o.icp_plane = o.icp_gicp = o.icp_color = false;
+         if (!std::strcmp(v[0], "point")) {}
+         else if (!std::strcmp(v[0], "plane")) o.icp_plane = true;
+         else if (!std::strcmp(v[0], "gicp")) o.icp_gicp = true;
+         else if (!std::strcmp(v[0], "color")) o.icp_color = true;
          else o.bad_value = true;
+       }},
+      {"--icp-color-lambda", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double l = std::strtod(v[0], &end);
+         o.icp_color_lambda_set = true;
+         if (end == v[0] || *end != '\0' || !(l >= 0) || !(l <= 1)) o.bad_value = true; else o.icp_color_lambda = l;
        }},
       {"--icp-gicp-epsilon", 1, [](Options& o, char** v) {
          char* end = nullptr;
@@ -145,6 +156,8 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
   if (o.icp_gicp_epsilon_set && !o.icp_gicp) return Parse::Bad;        // --icp-gicp-epsilon needs --icp-metric gicp
+  if (o.icp_color && o.icp_loss != 0) return Parse::Bad;               // the coloured metric takes no loss
+  if (o.icp_color_lambda_set && !o.icp_color) return Parse::Bad;       // --icp-color-lambda needs --icp-metric color
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -160,13 +173,15 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ -x (legacy 4PCS: not available in this build) ]\n");
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
   std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
-  std::fprintf(stderr, "\t[ --icp-metric point|plane|gicp (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
+  std::fprintf(stderr, "\t[ --icp-metric point|plane|gicp|color (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
   std::fprintf(stderr, "\t[ --icp-gicp-epsilon e (gicp; 0.001, in [1e-6, 1]; gicp takes no --icp-loss) ]\n");
+  std::fprintf(stderr, "\t[ --icp-color-lambda l (color; 0.968, in [0, 1]: the weight of the geometric term; color needs coloured\n");
+  std::fprintf(stderr, "\t    inputs and takes no --icp-loss) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss none|trimmed|huber|tukey (none) ] [ --icp-trim fraction (trimmed; -o) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss-scale s (huber, tukey; estimated) ]  (robust ICP)\n");
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
-  std::fprintf(stderr, "\t     them and --icp-metric plane / gicp use P's (gicp: Q's too) when all are nonzero)\n");
+  std::fprintf(stderr, "\t     them and --icp-metric plane / gicp / color use P's (gicp: Q's too) when all are nonzero)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -1,7 +1,7 @@
-// RefineICP: point-to-point, point-to-plane or generalized ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
+// RefineICP: point-to-point, point-to-plane, generalized or coloured ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
 // documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
 // of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h,
-// include/s4p_icp_plane.h, include/s4p_icp_gicp.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
+// include/s4p_icp_plane.h, include/s4p_icp_gicp.h, include/s4p_icp_color.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
 // Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
 //
 // ICPMetric::Generalized needs normals of both clouds.  Q's own are used when every point of Q has a nonzero one.
@@ -10,6 +10,10 @@
 // the normals are estimated on the moved Q as EstimateNormals does with k = 16 (algorithms/normals.h).  That one step binds
 // libsuper4pcs_normals.so at run time (the process's own copy when it is linked, else the library next to
 // libsuper4pcs_icp.so), so that programs which link -lsuper4pcs_icp alone keep building.
+//
+// ICPMetric::Colored adds a photometric term (include/s4p_icp_color.h) and needs the colour of both clouds: every point's
+// rgb() (0..255, as io.h reads it) becomes the intensity float(((double r + double g) + double b) / 765).  A point whose
+// rgb()[0] < 0 has no colour (the convention of the reference's pair filter), and RefineICP then throws.
 //
 //   MatchSuper4PCS matcher(options, logger);
 //   matcher.ComputeTransformation(P, &Q, mat);           // Q is moved by mat
@@ -30,12 +34,13 @@
 #include "s4p_icp_plane.h"
 #include "s4p_icp_robust.h"
 #include "s4p_icp_gicp.h"
+#include "s4p_icp_color.h"
 #include "s4p_normals.h"
 #include "super4pcs/algorithms/match4pcsBase.h"
 
 namespace GlobalRegistration {
 
-enum class ICPMetric { PointToPoint, PointToPlane, Generalized };
+enum class ICPMetric { PointToPoint, PointToPlane, Generalized, Colored };
 enum class ICPLoss { None, Trimmed, Huber, Tukey };
 
 struct ICPOptions {
@@ -51,6 +56,10 @@ struct ICPOptions {
   // Generalized: target normals as for PointToPlane; source normals as described at the top of this header; the covariance
   // parameter epsilon of include/s4p_icp_gicp.h, in [1e-6, 1].  Takes no loss.
   double gicp_epsilon = S4P_ICP_GICP_EPSILON;
+  // Colored: target normals as for PointToPlane; intensities from rgb() of both clouds; intensity gradients of P estimated
+  // on the device within normal_radius (<= 0: max_distance) with at least 6 neighbours; the weight color_lambda of the
+  // geometric term (include/s4p_icp_color.h), in [0, 1].  Takes no loss.
+  double color_lambda = S4P_ICP_COLOR_LAMBDA;
   // None: least squares over every pair within max_distance.  Trimmed keeps the pairs whose residual is at most the
   // ceil(trim_fraction |Q|)-th smallest; Huber / Tukey reweight with the scale loss_scale (<= 0: estimated on the device)
   ICPLoss loss = ICPLoss::None;
@@ -60,7 +69,7 @@ struct ICPOptions {
 
 struct ICPResult {
   int iterations = 0;
-  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane, generalized)
+  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane, generalized, coloured)
   int64_t n_corr = 0;
   double rmse = 0.0;
   double fitness = 0.0;             // n_corr / |Q|
@@ -102,12 +111,28 @@ inline void icp_knn_normals(const std::vector<float> (&c)[3], int k, int device,
 
 // Q as it stands after ComputeTransformation (already moved).  Finds dT, moves Q in place (in k_apply's rounding order)
 // and sets transformation <- dT * transformation.  Returns the fitness of the refined pose.  Throws std::runtime_error
-// when there is no device (no CPU fallback) or an argument is invalid.
+// when there is no device (no CPU fallback) or an argument is invalid, std::invalid_argument for an empty cloud, a loss with
+// the generalized or coloured metric, or the coloured metric on a cloud with a point that has no colour.
 inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, Match4PCSBase::MatrixRef transformation,
                        const ICPOptions& options, ICPResult* result = nullptr) {
   if (Q == nullptr || P.empty() || Q->empty()) throw std::invalid_argument("RefineICP: empty cloud");
   const bool gicp = options.metric == ICPMetric::Generalized;
   if (gicp && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the generalized metric takes no loss");
+  const bool colored = options.metric == ICPMetric::Colored;
+  if (colored && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the coloured metric takes no loss");
+  std::vector<float> ip, iq;
+  if (colored) {
+    auto intensity = [](const std::vector<Point3D>& pts, std::vector<float>* out) {
+      out->resize(pts.size());
+      for (size_t i = 0; i < pts.size(); ++i) {
+        const auto& c = pts[i].rgb();
+        if (c(0) < 0) throw std::invalid_argument("RefineICP: the coloured metric needs a colour at every point of P and Q");
+        (*out)[i] = float(((double(c(0)) + double(c(1))) + double(c(2))) / 765.0);
+      }
+    };
+    intensity(P, &ip);
+    intensity(*Q, &iq);
+  }
   struct Handle {
     s4p_icp_ctx* h = nullptr;
     ~Handle() { s4p_icp_destroy(h); }
@@ -127,7 +152,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
   H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
   const bool plane = options.metric == ICPMetric::PointToPlane;
-  if (plane || gicp) {
+  if (plane || gicp || colored) {
     bool all = true;
     for (const Point3D& pt : P) {
       const auto& nv = pt.normal();
@@ -166,6 +191,12 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
     }
     H.check(s4p_icp_set_source_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(Q->size())));
   }
+  if (colored) {
+    H.check(s4p_icp_set_target_intensity(H.h, ip.data(), int64_t(P.size())));
+    H.check(s4p_icp_set_source_intensity(H.h, iq.data(), int64_t(Q->size())));
+    const double r = options.normal_radius > 0 ? options.normal_radius : options.max_distance;
+    H.check(s4p_icp_estimate_color_gradients(H.h, float(r), 6));
+  }
   s4p_icp_params prm;
   s4p_icp_default_params(&prm);
   prm.max_iterations = options.max_iterations;
@@ -175,6 +206,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   s4p_icp_result r;
   if (options.loss == ICPLoss::None) {
     if (gicp) H.check(s4p_icp_refine_gicp(H.h, &prm, options.gicp_epsilon, dT, &r));
+    else if (colored) H.check(s4p_icp_refine_color(H.h, &prm, options.color_lambda, dT, &r));
     else H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
   } else {
     const int32_t loss = options.loss == ICPLoss::Trimmed ? S4P_ICP_LOSS_TRIMMED

@@ -1,12 +1,13 @@
-"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h and include/s4p_icp_gicp.h
-(libsuper4pcs_icp.so): point-to-point, point-to-plane and generalized (plane-to-plane) ICP refinement on the full-resolution
-clouds, with optional robust losses for the first two.
+"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h and
+include/s4p_icp_color.h (libsuper4pcs_icp.so): point-to-point, point-to-plane, generalized (plane-to-plane) and coloured ICP
+refinement on the full-resolution clouds, with optional robust losses for the first two.
 
     from super4pcs_amd import icp
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="plane")   # target normals estimated on the device
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, loss="trimmed", trim_fraction=0.6)   # trimmed ICP
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="gicp")    # normals of both clouds (given or estimated)
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="color", target_intensity=rgbP, source_intensity=rgbQ)
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -29,9 +30,12 @@ STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged", TOO_FE
 ERR_DEGENERATE = -8
 ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE", ERR_DEGENERATE: "DEGENERATE"}
 METRICS = ("point", "plane")
-REFINE_METRICS = METRICS + ("gicp",)     # "gicp": include/s4p_icp_gicp.h, no robust losses
+REFINE_METRICS = METRICS + ("gicp", "color")     # include/s4p_icp_gicp.h, include/s4p_icp_color.h: no robust losses
 GICP_NSUMS = PLANE_NSUMS
 GICP_EPSILON = 1e-3
+COLOR_NSUMS = PLANE_NSUMS
+COLOR_LAMBDA = 0.968            # S4P_ICP_COLOR_LAMBDA: the weight of the geometric term
+COLOR_MIN_NEIGHBOURS = 4        # the smallest min_neighbours of estimate_color_gradients
 MIN_NEIGHBOURS = 6              # estimate_normals' default
 LOSSES = {"trimmed": 1, "huber": 2, "tukey": 3}             # S4P_ICP_LOSS_*
 LOSS_C = {"huber": 1.345, "tukey": 4.685}                   # default tuning constants
@@ -52,6 +56,11 @@ ROBUST_SYMBOLS = [                                         # include/s4p_icp_rob
 GICP_SYMBOLS = [                                           # include/s4p_icp_gicp.h
     "s4p_icp_set_source_normals", "s4p_icp_set_source_normals_device", "s4p_icp_source_normals", "s4p_icp_gicp_sums",
     "s4p_icp_refine_gicp",
+]
+COLOR_SYMBOLS = [                                          # include/s4p_icp_color.h
+    "s4p_icp_set_target_intensity", "s4p_icp_set_target_intensity_device", "s4p_icp_set_source_intensity",
+    "s4p_icp_set_source_intensity_device", "s4p_icp_estimate_color_gradients", "s4p_icp_target_color_gradients",
+    "s4p_icp_color_sums", "s4p_icp_refine_color",
 ]
 
 
@@ -147,6 +156,18 @@ def load_library():
     L.s4p_icp_gicp_sums.argtypes = [vp, fp, C.c_double, dp]
     L.s4p_icp_refine_gicp.restype = C.c_int32
     L.s4p_icp_refine_gicp.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
+    for name in ("s4p_icp_set_target_intensity", "s4p_icp_set_target_intensity_device", "s4p_icp_set_source_intensity",
+                 "s4p_icp_set_source_intensity_device"):
+        getattr(L, name).restype = C.c_int32
+        getattr(L, name).argtypes = [vp, vp, C.c_int64]
+    L.s4p_icp_estimate_color_gradients.restype = C.c_int32
+    L.s4p_icp_estimate_color_gradients.argtypes = [vp, C.c_float, C.c_int32]
+    L.s4p_icp_target_color_gradients.restype = C.c_int32
+    L.s4p_icp_target_color_gradients.argtypes = [vp, fp, fp, fp]
+    L.s4p_icp_color_sums.restype = C.c_int32
+    L.s4p_icp_color_sums.argtypes = [vp, fp, C.c_double, dp]
+    L.s4p_icp_refine_color.restype = C.c_int32
+    L.s4p_icp_refine_color.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
     _LIB = L
     return L
 
@@ -226,8 +247,37 @@ def _is_torch(t):
 def _check_metric(metric, loss):
     if metric not in REFINE_METRICS:
         raise ValueError("metric must be one of %s" % (REFINE_METRICS,))
-    if metric == "gicp" and loss is not None:
-        raise ValueError("metric \"gicp\" takes no loss (robust losses cover \"point\" and \"plane\")")
+    if metric in ("gicp", "color") and loss is not None:
+        raise ValueError("metric \"%s\" takes no loss (robust losses cover \"point\" and \"plane\")" % metric)
+
+
+def rgb_to_intensity(rgb):
+    """float32 (n,): ((double r + double g) + double b) / 765 of an (n, 3) rgb array in 0..255 (numpy, or a torch tensor,
+    which stays on its device) -- the formula of the facade (include/super4pcs/algorithms/icp.h)."""
+    if _is_torch(rgb):
+        import torch
+        if rgb.dim() != 2 or rgb.shape[1] != 3:
+            raise ValueError("rgb is (N, 3)")
+        d = rgb.to(torch.float64)
+        return (((d[:, 0] + d[:, 1]) + d[:, 2]) / 765.0).to(torch.float32)
+    d = np.asarray(rgb, np.float64)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError("rgb is (N, 3)")
+    return (((d[:, 0] + d[:, 1]) + d[:, 2]) / 765.0).astype(np.float32)
+
+
+def _as_intensity(v):
+    """One float per point: an (n, 3) input is rgb and goes through rgb_to_intensity, an (n,) or (n, 1) one is taken as it is."""
+    if not _is_torch(v):
+        v = np.asarray(v)
+    nd = v.dim() if _is_torch(v) else v.ndim
+    if nd == 2 and v.shape[1] == 3:
+        return rgb_to_intensity(v)
+    if nd == 2 and v.shape[1] == 1:
+        return v[:, 0]
+    if nd != 1:
+        raise ValueError("an intensity is (N,) or (N, 1), a colour (N, 3)")
+    return v
 
 
 class ICP:
@@ -341,6 +391,51 @@ class ICP:
         self._chk(self.L.s4p_icp_gicp_sums(self.h, _fp(T), float(epsilon), _dp(out)))
         return out
 
+    def _scalars(self, v):
+        """(entry-point suffix, pointer, n, keep-alive) of one float per point: numpy, or a torch tensor on the GPU."""
+        if _is_torch(v):
+            import torch
+            if not (v.is_cuda and v.dim() == 1):
+                raise ValueError("torch input must be a (N,) tensor on the GPU")
+            c = v.to(torch.float32).contiguous()
+            torch.cuda.synchronize(v.device)
+            return "_device", c.data_ptr(), int(c.shape[0]), c
+        c = np.ascontiguousarray(v, dtype=np.float32)
+        if c.ndim != 1:
+            raise ValueError("an intensity is (N,)")
+        return "", c.ctypes.data, int(c.shape[0]), c
+
+    def set_target_intensity(self, I):
+        """One finite float per target point (N,), in the uploaded order (include/s4p_icp_color.h).  Invalidates the gradients."""
+        suf, ptr, n, keep = self._scalars(I)
+        self._chk(getattr(self.L, "s4p_icp_set_target_intensity" + suf)(self.h, ptr, n))
+        del keep
+
+    def set_source_intensity(self, I):
+        """One finite float per source point (N,), in the uploaded order.  set_source invalidates it."""
+        suf, ptr, n, keep = self._scalars(I)
+        self._chk(getattr(self.L, "s4p_icp_set_source_intensity" + suf)(self.h, ptr, n))
+        del keep
+
+    def estimate_color_gradients(self, radius, min_neighbours=MIN_NEIGHBOURS):
+        """The intensity gradient of every target point in its tangent plane, on the device, from the neighbours within
+        radius (0 < radius <= max_distance, min_neighbours >= 4).  Needs target normals and target intensity."""
+        self._chk(self.L.s4p_icp_estimate_color_gradients(self.h, float(radius), int(min_neighbours)))
+
+    def target_color_gradients(self):
+        """float32 (n_P, 3): the current gradients, in the uploaded order."""
+        n = self.n_p
+        cols = [np.empty(n, np.float32) for _ in range(3)]
+        self._chk(self.L.s4p_icp_target_color_gradients(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
+        return np.stack(cols, axis=1)
+
+    def color_sums(self, T, color_lambda=COLOR_LAMBDA):
+        """The 31 joint sums for a float T in the centred frame (layout in include/s4p_icp_color.h)."""
+        T = self._t32(T)
+        out = np.empty(COLOR_NSUMS, np.float64)
+        self._chk(self.L.s4p_icp_color_sums(self.h, _fp(T), float(color_lambda), _dp(out)))
+        return out
+
     def correspondences(self, T):
         """(idx int32[n_Q], d2 float32[n_Q]) for a float T in the centred frame; idx -1 where nothing is within d."""
         T = self._t32(T)
@@ -368,11 +463,14 @@ class ICP:
         return out, info
 
     def refine(self, T0=None, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True, metric="point",
-               loss=None, trim_fraction=None, loss_scale=None, loss_c=None, info=None, gicp_epsilon=GICP_EPSILON):
+               loss=None, trim_fraction=None, loss_scale=None, loss_c=None, info=None, gicp_epsilon=GICP_EPSILON,
+               color_lambda=COLOR_LAMBDA):
         """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity).  metric "plane"
         minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals); metric
         "gicp" is generalized ICP (include/s4p_icp_gicp.h) with the covariance parameter gicp_epsilon in [1e-6, 1], needs
-        source normals too (set_source_normals) and takes no loss.  loss "trimmed" / "huber" / "tukey" refines on the
+        source normals too (set_source_normals) and takes no loss; metric "color" is coloured ICP
+        (include/s4p_icp_color.h) with the geometric weight color_lambda in [0, 1], needs target normals, both intensities and
+        the gradients (estimate_color_gradients) and takes no loss.  loss "trimmed" / "huber" / "tukey" refines on the
         weighted sums (include/s4p_icp_robust.h); loss=None is the plain refine.  info: an optional float64 array of 8 that
         receives the final pass's robust info."""
         _check_metric(metric, loss)
@@ -394,6 +492,9 @@ class ICP:
         if metric == "gicp":
             self._chk(self.L.s4p_icp_refine_gicp(self.h, C.byref(p), float(gicp_epsilon), _dp(T), C.byref(r)))
             return T.reshape(4, 4), r
+        if metric == "color":
+            self._chk(self.L.s4p_icp_refine_color(self.h, C.byref(p), float(color_lambda), _dp(T), C.byref(r)))
+            return T.reshape(4, 4), r
         fn = self.L.s4p_icp_refine_plane if metric == "plane" else self.L.s4p_icp_refine
         self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
         return T.reshape(4, 4), r
@@ -408,15 +509,23 @@ class ICP:
 
 
 def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None,
-           source_normals=None, normal_k=16, **params):
-    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane" and "gicp":
-    the target normals are target_normals if given, else estimated within normal_radius (default max_distance).  metric
+           source_normals=None, normal_k=16, target_intensity=None, source_intensity=None, color_radius=None, **params):
+    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane", "gicp" and
+    "color": the target normals are target_normals if given, else estimated within normal_radius (default max_distance).  metric
     "gicp": the source normals (in Q's frame as given) are source_normals if given, else the normal_k-nearest-neighbour
-    normals of Q (super4pcs_amd.normals.estimate_normals).  params go to ICP.refine, the robust ones (loss, trim_fraction,
-    loss_scale, loss_c) and gicp_epsilon included."""
+    normals of Q (super4pcs_amd.normals.estimate_normals).  metric "color": target_intensity and source_intensity are
+    required, one value per point as (N,), or rgb in 0..255 as (N, 3), which goes through rgb_to_intensity; the gradients are
+    estimated within color_radius (default: the radius of the normals).  params go to ICP.refine, the robust ones (loss,
+    trim_fraction, loss_scale, loss_c), gicp_epsilon and color_lambda included."""
     if max_distance is None:
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
     _check_metric(metric, params.get("loss"))
+    if metric == "color":
+        if target_intensity is None or source_intensity is None:
+            raise ValueError("metric \"color\" needs target_intensity and source_intensity")
+        target_intensity, source_intensity = _as_intensity(target_intensity), _as_intensity(source_intensity)
+    elif target_intensity is not None or source_intensity is not None or color_radius is not None:
+        raise ValueError("target_intensity / source_intensity / color_radius need metric \"color\"")
     if metric == "gicp" and source_normals is None:
         from super4pcs_amd import normals
         source_normals = normals.estimate_normals(Q, k=normal_k)
@@ -424,13 +533,18 @@ def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_no
     try:
         ctx.set_target(P, max_distance)
         ctx.set_source(Q)
-        if metric in ("plane", "gicp"):
+        if metric in ("plane", "gicp", "color"):
             if target_normals is not None:
                 ctx.set_target_normals(target_normals)
             else:
                 ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
         if metric == "gicp":
             ctx.set_source_normals(source_normals)
+        if metric == "color":
+            ctx.set_target_intensity(target_intensity)
+            ctx.set_source_intensity(source_intensity)
+            r_n = max_distance if normal_radius is None else normal_radius
+            ctx.estimate_color_gradients(r_n if color_radius is None else color_radius)
         return ctx.refine(T0, metric=metric, **params)
     finally:
         ctx.close()

@@ -1,6 +1,6 @@
 // s4p_icp.hip -- libsuper4pcs_icp.so: point-to-point and point-to-plane ICP on the full-resolution clouds, with robust
-// losses and generalized ICP (include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
-// DESIGN.md sections "ICP refinement", "Point-to-plane ICP", "Robust ICP" and "Generalized ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
+// losses, generalized and coloured ICP (include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
+// include/s4p_icp_color.h, DESIGN.md sections "ICP refinement", "Point-to-plane ICP", "Robust ICP", "Generalized ICP" and "Coloured ICP").  One translation unit: device kernels (namespace s4p_icp), the host solve and the C ABI.
 //
 // Device path:
 //   set_target   k_stats (per-block double sums and float bounds of P) -> host frame c and grid plan ->
@@ -15,6 +15,9 @@
 //                the keys (k_key_hist + k_key_digit x 4, on the device), k_wsum + k_wfinal (weighted sums), host solve.
 //   generalized  (include/s4p_icp_gicp.h) source normals in the order of the source (k_gather_source_normals); per iteration
 //                k_search (winner slot per lane), k_gicp_sum (31 double sums streamed from the slots) + k_final_plane, host solve.
+//   coloured     (include/s4p_icp_color.h) target intensities in cell order (k_gather_target_intensity), their tangent-plane
+//                gradients (k_color_gradient, k_normals' walk), source intensities in the order of the source
+//                (k_gather_source_intensity); per iteration k_search, k_color_sum (31 joint sums) + k_final_plane, host solve.
 // No float or double atomics anywhere (the selection's histograms use integer atomics): every sum has a fixed order, so two calls return identical bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -31,6 +34,7 @@
 #include "s4p_icp_plane.h"
 #include "s4p_icp_robust.h"
 #include "s4p_icp_gicp.h"
+#include "s4p_icp_color.h"
 
 namespace s4p_icp {
 
@@ -634,6 +638,155 @@ __global__ __launch_bounds__(kBlock) void k_gicp_sum(GicpArgs A) {
   }
 }
 
+// coloured ICP (include/s4p_icp_color.h).  Once per target: the intensities in cell order (k_gather_target_intensity) and
+// the intensity gradient of every target point in its tangent plane (k_color_gradient).  Per iteration: k_search<false>,
+// k_color_sum (the 31 joint sums streamed from the slots, k_match_plane's reduction) and k_final_plane.  Defined before
+// k_final_plane, as the generalized kernels above.
+
+// target intensities (uploaded order) -> cell order, through the index bits of tgt[k].w
+__global__ __launch_bounds__(kBlock) void k_gather_target_intensity(const float* in, const float4* tgt, uint64_t n, float* out) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock)
+    out[k] = in[__float_as_uint(tgt[k].w)];
+}
+
+// Intensity gradient of every target point, one lane per point in cell order: k_normals' walk (the same neighbourhood, the
+// same conservative cell skip), 9 double sums of the neighbours' tangent-plane offsets u and intensity differences,
+// A = S + tr(S) n n^T, the Jacobi gate on A's spectrum and a cofactor solve, term by term as include/s4p_icp_color.h
+// states them.  Writes (g, I_p): the sum pass reads gradient and intensity of a winner in one 16-byte load.
+__global__ __launch_bounds__(kBlock) void k_color_gradient(GridDev g, const float4* nrm, const float* tint, uint64_t n, float r2,
+                                                           int32_t min_nb, float4* grad) {
+  const double eps = 1e-6 * g.h;
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock) {
+    const float4 p = g.tgt[k];
+    const float4 nf = nrm[k];
+    const float ip = tint[k];
+    float4 out = make_float4(0.f, 0.f, 0.f, ip);
+    if (nf.x == 0.f && nf.y == 0.f && nf.z == 0.f) { grad[k] = out; continue; }
+    const int cx = int(cell_coord(p.x, g.ox, g.inv_h)), cy = int(cell_coord(p.y, g.oy, g.inv_h)), cz = int(cell_coord(p.z, g.oz, g.inv_h));
+    const double qx = double(p.x), qy = double(p.y), qz = double(p.z), qi = double(ip);
+    const double n0 = double(nf.x), n1 = double(nf.y), n2 = double(nf.z);
+    double S[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, b[3] = {0.0, 0.0, 0.0};    // sum u u^T (xx xy xz yy yz zz); sum u dI
+    int32_t cnt = 0;
+    for (int t = 0; t < 27; ++t) {
+      const int ix = cx + t % 3 - 1, iy = cy + (t / 3) % 3 - 1, iz = cz + t / 9 - 1;
+      if (ix < 0 || ix >= g.nx || iy < 0 || iy >= g.ny || iz < 0 || iz >= g.nz) continue;
+      const double bx0 = g.ox + ix * g.h, by0 = g.oy + iy * g.h, bz0 = g.oz + iz * g.h;
+      const double ex = fmax(0.0, fmax(bx0 - qx, qx - (bx0 + g.h)) - eps);
+      const double ey = fmax(0.0, fmax(by0 - qy, qy - (by0 + g.h)) - eps);
+      const double ez = fmax(0.0, fmax(bz0 - qz, qz - (bz0 + g.h)) - eps);
+      if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(r2)) continue;
+      const uint32_t c = (uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix);
+      const uint32_t cb = g.start[c], ce = g.start[c + 1];
+      for (uint32_t j = cb; j < ce; ++j) {
+        const float4 o = g.tgt[j];
+        const float dx = p.x - o.x, dy = p.y - o.y, dz = p.z - o.z;
+        if (dx * dx + (dy * dy + dz * dz) > r2) continue;
+        const double e0 = double(o.x) - qx, e1 = double(o.y) - qy, e2 = double(o.z) - qz;
+        const double en = (e0 * n0 + e1 * n1) + e2 * n2;
+        const double u0 = e0 - en * n0, u1 = e1 - en * n1, u2 = e2 - en * n2;
+        const double dI = double(tint[j]) - qi;
+        ++cnt;
+        S[0] += u0 * u0; S[1] += u0 * u1; S[2] += u0 * u2; S[3] += u1 * u1; S[4] += u1 * u2; S[5] += u2 * u2;
+        b[0] += u0 * dI; b[1] += u1 * dI; b[2] += u2 * dI;
+      }
+    }
+    if (cnt >= min_nb) {
+      const double tr = (S[0] + S[3]) + S[5];
+      const double A00 = S[0] + tr * (n0 * n0), A01 = S[1] + tr * (n0 * n1), A02 = S[2] + tr * (n0 * n2);
+      const double A11 = S[3] + tr * (n1 * n1), A12 = S[4] + tr * (n1 * n2), A22 = S[5] + tr * (n2 * n2);
+      double C[3][3], V[3][3];
+      C[0][0] = A00; C[0][1] = A01; C[0][2] = A02; C[1][1] = A11; C[1][2] = A12; C[2][2] = A22;
+      C[1][0] = A01; C[2][0] = A02; C[2][1] = A12;
+      jacobi_sym<3>(C, V);
+      const double lmin = fmin(fmin(C[0][0], C[1][1]), C[2][2]), lmax = fmax(fmax(C[0][0], C[1][1]), C[2][2]);
+      if (lmin > S4P_ICP_COLOR_GATE * lmax) {
+        const double c00 = A11 * A22 - A12 * A12, c01 = A02 * A12 - A01 * A22, c02 = A01 * A12 - A02 * A11;
+        const double c11 = A00 * A22 - A02 * A02, c12 = A01 * A02 - A00 * A12, c22 = A00 * A11 - A01 * A01;
+        const double det = (A00 * c00 + A01 * c01) + A02 * c02;
+        out.x = float(((c00 * b[0] + c01 * b[1]) + c02 * b[2]) / det);
+        out.y = float(((c01 * b[0] + c11 * b[1]) + c12 * b[2]) / det);
+        out.z = float(((c02 * b[0] + c12 * b[1]) + c22 * b[2]) / det);
+      }
+    }
+    grad[k] = out;
+  }
+}
+
+// source intensities (uploaded order) -> the order of `src` (w = original source index), next to it
+__global__ __launch_bounds__(kBlock) void k_gather_source_intensity(const float* in, const float4* src, uint64_t n, float* out) {
+  for (uint64_t k = blockIdx.x * (uint64_t)kBlock + threadIdx.x; k < n; k += (uint64_t)gridDim.x * kBlock)
+    out[k] = in[__float_as_uint(src[k].w)];
+}
+
+struct ColorArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;
+  const float* sint;        // source intensities, the order of src
+  const float4* nrm;        // cell order, as g.tgt
+  const float4* grad;       // cell order: gradient, target intensity
+  uint64_t n;
+  const uint32_t* slot;     // k_search's
+  double wg, wc;            // lambda, 1 - lambda
+  double* slab;             // one kPlanePitch row per workgroup
+};
+
+// The joint sums, term by term as include/s4p_icp_color.h states them.  No search: the winner comes from k_search's slot.
+__global__ __launch_bounds__(kBlock) void k_color_sum(ColorArgs A) {
+  constexpr int NS = S4P_ICP_PLANE_NSUMS;
+  double s[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = 0.0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t sl = A.slot[j];
+    if (sl == kNoSlot) continue;
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    const float4 p = A.g.tgt[sl];
+    const float dx = x - p.x, dy = y - p.y, dz = z - p.z;
+    const float d2 = dx * dx + (dy * dy + dz * dz);           // nearest_t's float d2 of the winner
+    s[0] += 1.0;
+    s[1] += double(d2);
+    const float4 nf = A.nrm[sl];
+    if (nf.x == 0.f && nf.y == 0.f && nf.z == 0.f) continue;
+    const float4 gf = A.grad[sl];
+    const double qd[3] = {double(x), double(y), double(z)}, nd[3] = {double(nf.x), double(nf.y), double(nf.z)};
+    const double gd[3] = {double(gf.x), double(gf.y), double(gf.z)};
+    const double r[3] = {double(p.x) - qd[0], double(p.y) - qd[1], double(p.z) - qd[2]};
+    const double sg = (r[0] * nd[0] + r[1] * nd[1]) + r[2] * nd[2];
+    const double gn = (gd[0] * nd[0] + gd[1] * nd[1]) + gd[2] * nd[2];
+    const double gp[3] = {gd[0] - gn * nd[0], gd[1] - gn * nd[1], gd[2] - gn * nd[2]};
+    const double rc = ((double(A.sint[j]) - double(gf.w)) + ((gd[0] * r[0] + gd[1] * r[1]) + gd[2] * r[2])) - sg * gn;
+    const double aG[6] = {qd[1] * nd[2] - qd[2] * nd[1], qd[2] * nd[0] - qd[0] * nd[2], qd[0] * nd[1] - qd[1] * nd[0], nd[0], nd[1], nd[2]};
+    const double aC[6] = {qd[1] * gp[2] - qd[2] * gp[1], qd[2] * gp[0] - qd[0] * gp[2], qd[0] * gp[1] - qd[1] * gp[0], gp[0], gp[1], gp[2]};
+    s[2] += 1.0;
+    s[3] += A.wg * (sg * sg) + A.wc * (rc * rc);
+    int o = 4;
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+      for (int v = u; v < 6; ++v) s[o++] += A.wg * (aG[u] * aG[v]) + A.wc * (aC[u] * aC[v]);
+#pragma unroll
+    for (int u = 0; u < 6; ++u) s[25 + u] += A.wg * (aG[u] * sg) + A.wc * (aC[u] * rc);
+  }
+  __shared__ double red[kBlock / 64][NS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    double v = s[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    double v = red[0][threadIdx.x];
+    for (int w = 1; w < kBlock / 64; ++w) v += red[w][threadIdx.x];
+    A.slab[uint64_t(blockIdx.x) * kPlanePitch + threadIdx.x] = v;
+  }
+}
+
 // the plane slab's nb rows -> 31 sums, in a fixed order: 8 parts per column (rows part, part + 8, ...), then the parts in order
 __global__ __launch_bounds__(kBlock) void k_final_plane(const double* slab, int nb, double* out) {
   constexpr int kParts = kBlock / S4P_ICP_PLANE_NSUMS;     // 8
@@ -927,6 +1080,14 @@ struct s4p_icp_ctx {
   float* sn[3] = {nullptr, nullptr, nullptr};   // source normals as stored, uploaded order
   float4* snrm = nullptr;            // the same in the order of the pass's source
   bool has_src_normals = false;
+  // coloured ICP (include/s4p_icp_color.h)
+  float* tint = nullptr;             // target intensities, cell order
+  float4* grad = nullptr;            // target gradients and intensities, cell order
+  bool has_tint = false, has_grad = false;
+  int64_t si_n = 0;                  // entries of si / sint
+  float* si = nullptr;               // source intensities, uploaded order
+  float* sint = nullptr;             // the same in the order of the pass's source
+  bool has_sint = false;
 };
 
 namespace {
@@ -986,6 +1147,8 @@ int32_t set_target_impl(s4p_icp_ctx* h, const float* x, const float* y, const fl
   h->has_target = false;
   h->has_normals = false;
   dfree(h->nrm); h->nrm = nullptr;
+  h->has_tint = h->has_grad = false;
+  dfree(h->tint); dfree(h->grad); h->tint = nullptr; h->grad = nullptr;
   dfree(h->tgt); h->tgt = nullptr;
   dfree(h->start); h->start = nullptr;
   Scratch S;
@@ -1073,6 +1236,7 @@ int32_t set_source_impl(s4p_icp_ctx* h, const float* x, const float* y, const fl
   ICP_HIP(hipSetDevice(h->device));
   h->has_source = false;
   h->has_src_normals = false;
+  h->has_sint = false;
   if (n != h->n_q) {
     for (int a = 0; a < 3; ++a) { dfree(h->qraw[a]); h->qraw[a] = nullptr; }
     dfree(h->src); dfree(h->src_ord); h->src = h->src_ord = nullptr;
@@ -1234,6 +1398,7 @@ int32_t plane_ready(s4p_icp_ctx* h) {
 
 int32_t alloc_normals(s4p_icp_ctx* h) {
   h->has_normals = false;
+  h->has_grad = false;                           // the gradients lie in the tangent planes of the normals they were made with
   if (!h->nrm) ICP_HIP(hipMalloc((void**)&h->nrm, size_t(h->n_p) * sizeof(float4)));
   return S4P_ICP_OK;
 }
@@ -1297,8 +1462,8 @@ int32_t gicp_ready(s4p_icp_ctx* h, double epsilon) {
   return S4P_ICP_OK;
 }
 
-// the buffers of a generalized pass (none is allocated inside the iteration loop) and the source normals in src's order
-int32_t gicp_prepare(s4p_icp_ctx* h, const float4* src) {
+// the buffers of a split pass (k_search's slots and keys, the plane slab): none is allocated inside the iteration loop
+int32_t split_buffers(s4p_icp_ctx* h) {
   const uint64_t un = uint64_t(h->n_q);
   if (h->r_n != h->n_q) {
     dfree(h->rslot); dfree(h->rkey); h->rslot = h->rkey = nullptr;
@@ -1308,6 +1473,13 @@ int32_t gicp_prepare(s4p_icp_ctx* h, const float4* src) {
     h->r_n = h->n_q;
   }
   if (!h->pslab) ICP_HIP(hipMalloc((void**)&h->pslab, size_t(kMaxBlocks) * kPlanePitch * sizeof(double)));
+  return S4P_ICP_OK;
+}
+
+// the buffers of a generalized pass and the source normals in src's order
+int32_t gicp_prepare(s4p_icp_ctx* h, const float4* src) {
+  if (int32_t rc = split_buffers(h)) return rc;
+  const uint64_t un = uint64_t(h->n_q);
   hipLaunchKernelGGL(k_gather_source_normals, dim3(blocks_for(h->n_q)), dim3(kBlock), 0, h->st, (const float*)h->sn[0],
                      (const float*)h->sn[1], (const float*)h->sn[2], src, un, h->snrm);
   ICP_HIP(hipGetLastError());
@@ -1332,6 +1504,88 @@ int32_t gicp_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double epsilon
   ICP_HIP(hipEventRecord(h->ev, h->st));
   ICP_HIP(hipEventSynchronize(h->ev));
   std::memcpy(out, h->hsum, S4P_ICP_GICP_NSUMS * sizeof(double));
+  return S4P_ICP_OK;
+}
+
+// intensities: every value finite
+int32_t check_intensity(s4p_icp_ctx* h, const float* v, size_t n, const char* who) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return fail(h, S4P_ICP_ERR_BAD_ARG, std::string(who) + ": non-finite intensity");
+  return S4P_ICP_OK;
+}
+
+// target intensities in the uploaded order (host) -> cell order
+int32_t set_target_intensity_host(s4p_icp_ctx* h, const float* v) {
+  const size_t n = size_t(h->n_p);
+  if (int32_t rc = check_intensity(h, v, n, "set_target_intensity")) return rc;
+  h->has_tint = h->has_grad = false;
+  if (!h->tint) ICP_HIP(hipMalloc((void**)&h->tint, n * sizeof(float)));
+  Scratch S;
+  float* d = nullptr;
+  ICP_HIP(S.alloc((void**)&d, n * sizeof(float)));
+  ICP_HIP(hipMemcpyAsync(d, v, n * sizeof(float), hipMemcpyHostToDevice, h->st));
+  hipLaunchKernelGGL(k_gather_target_intensity, dim3(blocks_for(h->n_p)), dim3(kBlock), 0, h->st, (const float*)d, (const float4*)h->tgt,
+                     uint64_t(n), h->tint);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipStreamSynchronize(h->st));          // v may be released on return; the scratch is
+  h->has_tint = true;
+  return S4P_ICP_OK;
+}
+
+// source intensities in the uploaded order (host): kept on the device in that order
+int32_t set_source_intensity_host(s4p_icp_ctx* h, const float* v) {
+  const size_t n = size_t(h->n_q);
+  if (int32_t rc = check_intensity(h, v, n, "set_source_intensity")) return rc;
+  h->has_sint = false;
+  if (h->si_n != h->n_q) {
+    dfree(h->si); dfree(h->sint); h->si = h->sint = nullptr;
+    h->si_n = 0;
+    ICP_HIP(hipMalloc((void**)&h->si, n * sizeof(float)));
+    ICP_HIP(hipMalloc((void**)&h->sint, n * sizeof(float)));
+    h->si_n = h->n_q;
+  }
+  ICP_HIP(hipMemcpyAsync(h->si, v, n * sizeof(float), hipMemcpyHostToDevice, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));          // v may be released on return
+  h->has_sint = true;
+  return S4P_ICP_OK;
+}
+
+int32_t color_ready(s4p_icp_ctx* h, double lambda) {
+  if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(h, S4P_ICP_ERR_BAD_ARG, "color: lambda must be in [0, 1]");
+  if (int32_t rc = plane_ready(h)) return rc;
+  if (!h->has_tint) return fail(h, S4P_ICP_ERR_STATE, "target intensity first (set_target_intensity)");
+  if (!h->has_grad) return fail(h, S4P_ICP_ERR_STATE, "colour gradients first (estimate_color_gradients)");
+  if (!h->has_sint) return fail(h, S4P_ICP_ERR_STATE, "source intensity first (set_source_intensity)");
+  return S4P_ICP_OK;
+}
+
+// the buffers of a colour pass and the source intensities in src's order
+int32_t color_prepare(s4p_icp_ctx* h, const float4* src) {
+  if (int32_t rc = split_buffers(h)) return rc;
+  const uint64_t un = uint64_t(h->n_q);
+  hipLaunchKernelGGL(k_gather_source_intensity, dim3(blocks_for(h->n_q)), dim3(kBlock), 0, h->st, (const float*)h->si, src, un, h->sint);
+  ICP_HIP(hipGetLastError());
+  return S4P_ICP_OK;
+}
+
+// one colour pass over `src` for T (after color_prepare for this src): the 31 sums on the host
+int32_t color_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double lambda, double* out) {
+  const int nb = blocks_for(h->n_q);
+  SearchArgs S;
+  S.T = T; S.g = h->g; S.src = src; S.nrm = h->nrm; S.n = uint64_t(h->n_q); S.d2max = h->d2max; S.slot = h->rslot; S.key = h->rkey;
+  hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, S);
+  ICP_HIP(hipGetLastError());
+  ColorArgs A;
+  A.T = T; A.g = h->g; A.src = src; A.sint = h->sint; A.nrm = h->nrm; A.grad = h->grad; A.n = uint64_t(h->n_q); A.slot = h->rslot;
+  A.wg = lambda; A.wc = 1.0 - lambda; A.slab = h->pslab;
+  hipLaunchKernelGGL(k_color_sum, dim3(nb), dim3(kBlock), 0, h->st, A);
+  ICP_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_final_plane, dim3(1), dim3(kBlock), 0, h->st, (const double*)h->pslab, nb, h->dsum);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(h->hsum, h->dsum, S4P_ICP_COLOR_NSUMS * sizeof(double), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipEventRecord(h->ev, h->st));
+  ICP_HIP(hipEventSynchronize(h->ev));
+  std::memcpy(out, h->hsum, S4P_ICP_COLOR_NSUMS * sizeof(double));
   return S4P_ICP_OK;
 }
 
@@ -1366,13 +1620,14 @@ Tf centred_from_float16(const float* T16) {
 
 namespace {
 
-enum RefineMetric { kRefinePoint = 0, kRefinePlane = 1, kRefineGicp = 2 };
+enum RefineMetric { kRefinePoint = 0, kRefinePlane = 1, kRefineGicp = 2, kRefineColor = 3 };
 
-// The refine loop of the three metrics.  plane / generalized: the 31 sums (sum d2 at [1]) and s4p_icp_solve_plane, whose
+// The refine loop of the four metrics (epsilon: the generalized metric's, or the coloured metric's lambda).  plane /
+// generalized / coloured: the 31 sums (sum d2 at [1]) and s4p_icp_solve_plane, whose
 // degenerate system stops the loop with T_k; otherwise the 17 sums (sum d2 at [16]) and Horn's solve.
 int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result, int metric,
                     double epsilon = 0.0) {
-  const bool gicp = metric == kRefineGicp, plane = metric != kRefinePoint;
+  const bool gicp = metric == kRefineGicp, color = metric == kRefineColor, plane = metric != kRefinePoint;
   if (!h) return S4P_ICP_ERR_BAD_ARG;
   if (!T16_inout) return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: null transform");
   s4p_icp_params P;
@@ -1380,19 +1635,21 @@ int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_in
   if (params) P = *params;
   if (P.max_iterations < 0 || P.min_correspondences < 0 || !(P.rel_tol >= 0.0))
     return fail(h, S4P_ICP_ERR_BAD_ARG, "refine: negative max_iterations / min_correspondences / rel_tol");
-  if (int32_t rc = gicp ? gicp_ready(h, epsilon) : (plane ? plane_ready(h) : ready(h))) return rc;
+  if (int32_t rc = gicp ? gicp_ready(h, epsilon) : (color ? color_ready(h, epsilon) : (plane ? plane_ready(h) : ready(h)))) return rc;
   s4p_icp_result R;
   std::memset(&R, 0, sizeof(R));
   double T[16], Tn[16], dT[16], sums[kSumsCap];
   const int i_d2 = plane ? 1 : 16;
   auto run_pass = [&](const float4* src) {
     if (gicp) return gicp_pass(h, to_float(T), src, epsilon, sums);
+    if (color) return color_pass(h, to_float(T), src, epsilon, sums);
     return plane ? plane_pass(h, to_float(T), src, sums) : pass(h, to_float(T), src, nullptr, nullptr, sums);
   };
   to_centred(T16_inout, h->c, T);
   const float4* src = nullptr;
   if (int32_t rc = source_for(h, P, T, &src)) return rc;
   if (gicp) if (int32_t rc = gicp_prepare(h, src)) return rc;      // the normals follow the source's order
+  if (color) if (int32_t rc = color_prepare(h, src)) return rc;    // and so do the intensities
   double prev = 0.0;
   R.status = S4P_ICP_MAX_ITERATIONS;
   for (int k = 0; k < P.max_iterations; ++k) {
@@ -1528,6 +1785,7 @@ void s4p_icp_destroy(s4p_icp_ctx* h) {
   dfree(h->rslot); dfree(h->rkey); dfree(h->rhist); dfree(h->rst); dfree(h->rsum);
   for (int a = 0; a < 3; ++a) dfree(h->sn[a]);
   dfree(h->snrm);
+  dfree(h->tint); dfree(h->grad); dfree(h->si); dfree(h->sint);
   if (h->rhsum) (void)hipHostFree(h->rhsum);
   if (h->hsum) (void)hipHostFree(h->hsum);
   if (h->ev) (void)hipEventDestroy(h->ev);
@@ -1845,6 +2103,96 @@ int32_t s4p_icp_gicp_sums(s4p_icp_ctx* h, const float* T16_centred, double epsil
 
 int32_t s4p_icp_refine_gicp(s4p_icp_ctx* h, const s4p_icp_params* params, double epsilon, double* T16_inout, s4p_icp_result* result) {
   return refine_impl(h, params, T16_inout, result, kRefineGicp, epsilon);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// coloured ICP (include/s4p_icp_color.h)
+
+int32_t s4p_icp_set_target_intensity(s4p_icp_ctx* h, const float* intensity, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return fail(h, S4P_ICP_ERR_STATE, "set_target_intensity: set_target first");
+  if (!intensity || n != h->n_p) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target_intensity: null or not one per target point");
+  ICP_HIP(hipSetDevice(h->device));
+  return set_target_intensity_host(h, intensity);
+}
+
+int32_t s4p_icp_set_target_intensity_device(s4p_icp_ctx* h, const float* intensity, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return fail(h, S4P_ICP_ERR_STATE, "set_target_intensity: set_target first");
+  if (!intensity || n != h->n_p) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target_intensity: null or not one per target point");
+  ICP_HIP(hipSetDevice(h->device));
+  // checked on the host, as for host input: both entry points store the same bits
+  std::vector<float> v(static_cast<size_t>(n));
+  ICP_HIP(hipMemcpy(v.data(), intensity, size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+  return set_target_intensity_host(h, v.data());
+}
+
+int32_t s4p_icp_set_source_intensity(s4p_icp_ctx* h, const float* intensity, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_source) return fail(h, S4P_ICP_ERR_STATE, "set_source_intensity: set_source first");
+  if (!intensity || n != h->n_q) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source_intensity: null or not one per source point");
+  ICP_HIP(hipSetDevice(h->device));
+  return set_source_intensity_host(h, intensity);
+}
+
+int32_t s4p_icp_set_source_intensity_device(s4p_icp_ctx* h, const float* intensity, int64_t n) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_source) return fail(h, S4P_ICP_ERR_STATE, "set_source_intensity: set_source first");
+  if (!intensity || n != h->n_q) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_source_intensity: null or not one per source point");
+  ICP_HIP(hipSetDevice(h->device));
+  std::vector<float> v(static_cast<size_t>(n));
+  ICP_HIP(hipMemcpy(v.data(), intensity, size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+  return set_source_intensity_host(h, v.data());
+}
+
+int32_t s4p_icp_estimate_color_gradients(s4p_icp_ctx* h, float radius, int32_t min_neighbours) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!h->has_target) return fail(h, S4P_ICP_ERR_STATE, "estimate_color_gradients: set_target first");
+  if (!h->has_normals) return fail(h, S4P_ICP_ERR_STATE, "estimate_color_gradients: target normals first");
+  if (!h->has_tint) return fail(h, S4P_ICP_ERR_STATE, "estimate_color_gradients: target intensity first");
+  if (!(radius > 0.f) || !(radius <= h->d))
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "estimate_color_gradients: radius must be in (0, max_distance]");
+  if (min_neighbours < S4P_ICP_COLOR_MIN_NEIGHBOURS)
+    return fail(h, S4P_ICP_ERR_BAD_ARG, "estimate_color_gradients: min_neighbours must be >= 4");
+  ICP_HIP(hipSetDevice(h->device));
+  h->has_grad = false;
+  if (!h->grad) ICP_HIP(hipMalloc((void**)&h->grad, size_t(h->n_p) * sizeof(float4)));
+  hipLaunchKernelGGL(k_color_gradient, dim3(blocks_for(h->n_p)), dim3(kBlock), 0, h->st, h->g, (const float4*)h->nrm, (const float*)h->tint,
+                     uint64_t(h->n_p), radius * radius, min_neighbours, h->grad);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipStreamSynchronize(h->st));
+  h->has_grad = true;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_target_color_gradients(s4p_icp_ctx* h, float* gx, float* gy, float* gz) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!gx || !gy || !gz) return fail(h, S4P_ICP_ERR_BAD_ARG, "target_color_gradients: null argument");
+  if (!h->has_target || !h->has_grad) return fail(h, S4P_ICP_ERR_STATE, "target_color_gradients: no gradients");
+  ICP_HIP(hipSetDevice(h->device));
+  Scratch S;
+  const size_t n = size_t(h->n_p);
+  float* d[3];
+  for (int a = 0; a < 3; ++a) ICP_HIP(S.alloc((void**)&d[a], n * sizeof(float)));
+  hipLaunchKernelGGL(k_scatter_normals, dim3(blocks_for(h->n_p)), dim3(kBlock), 0, h->st, (const float4*)h->grad, (const float4*)h->tgt,
+                     uint64_t(n), d[0], d[1], d[2]);
+  ICP_HIP(hipGetLastError());
+  float* out[3] = {gx, gy, gz};
+  for (int a = 0; a < 3; ++a) ICP_HIP(hipMemcpyAsync(out[a], d[a], n * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_color_sums(s4p_icp_ctx* h, const float* T16_centred, double lambda, double* sums) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "color_sums: null argument");
+  if (int32_t rc = color_ready(h, lambda)) return rc;
+  if (int32_t rc = color_prepare(h, h->src)) return rc;
+  return color_pass(h, centred_from_float16(T16_centred), h->src, lambda, sums);
+}
+
+int32_t s4p_icp_refine_color(s4p_icp_ctx* h, const s4p_icp_params* params, double lambda, double* T16_inout, s4p_icp_result* result) {
+  return refine_impl(h, params, T16_inout, result, kRefineColor, lambda);
 }
 
 }  // extern "C"
