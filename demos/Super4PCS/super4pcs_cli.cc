@@ -8,6 +8,7 @@
 //             [--icp-gicp-epsilon e] [--icp-color-lambda l]
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
+//             [--remove-outliers k] [--remove-outliers-std ratio]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -19,6 +20,10 @@
 // --estimate-normals k gives both inputs k-nearest-neighbour normals (algorithms/normals.h, within r if given) before the
 // matcher runs, replacing the normals read from the files for matching only (-r writes the files' own): -a then filters on
 // them, and --icp-metric plane uses P's when all of them are nonzero.
+// --remove-outliers k removes the statistical outliers of both inputs (algorithms/outliers.h: mean distance to the k nearest
+// other points above mean + ratio * stddev, ratio --remove-outliers-std, default 2) right after loading, before
+// --estimate-normals, the matcher and ICP; -r then writes the filtered, registered second input.  Faces index the vertex
+// list, so an input with faces is refused (exit status 254).
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
@@ -27,6 +32,7 @@
 
 #include "super4pcs/algorithms/icp.h"
 #include "super4pcs/algorithms/normals.h"
+#include "super4pcs/algorithms/outliers.h"
 #include "super4pcs/algorithms/super4pcs.h"
 #include "super4pcs/io/io.h"
 #include "super4pcs/utils/geometry.h"
@@ -48,6 +54,22 @@ struct Mesh {                                    // everything IOManager returns
     if (!io.ReadObject(path.c_str(), points, tex, normals, faces, materials)) return false;
     if (faces.empty()) Utils::CleanInvalidNormals(points, normals);   // point sets only: faces index the vertex list
     return true;
+  }
+  // statistical outlier removal of the points; per-vertex normal and texture lists follow the vertices
+  size_t remove_outliers(const OutlierRemovalOptions& oopt) {
+    const size_t before = points.size();
+    std::vector<uint8_t> kept;
+    const size_t removed = RemoveOutliers(points, oopt, &kept);
+    auto compact = [&](auto& list) {
+      if (list.size() != before) return;
+      size_t w = 0;
+      for (size_t i = 0; i < before; ++i)
+        if (kept[i]) list[w++] = list[i];
+      list.resize(w);
+    };
+    compact(normals);
+    compact(tex);
+    return removed;
   }
   bool save(IOManager& io, const std::string& path) const {
     return io.WriteObject(path.c_str(), points, tex, normals, faces, materials);
@@ -87,7 +109,18 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
 
   Match4PCSBase::MatrixType mat = Match4PCSBase::MatrixType::Identity();
   float score = 0.f;
+  if (opt.outliers_k > 0 && (!P.faces.empty() || !Q.faces.empty())) {
+    log.Log<Utils::ErrorReport>("--remove-outliers: an input has faces; faces index the vertex list, so only point sets can be filtered");
+    return -2;
+  }
   try {
+    if (opt.outliers_k > 0) {
+      OutlierRemovalOptions oopt;
+      oopt.k = opt.outliers_k;
+      oopt.std_ratio = opt.outliers_std;
+      const size_t rp = P.remove_outliers(oopt), rq = Q.remove_outliers(oopt);
+      log.Log<Utils::Verbose>("Removed outliers: k ", opt.outliers_k, ", ratio ", opt.outliers_std, ": ", rp, " of input1, ", rq, " of input2");
+    }
     if (opt.normals_k > 0) {
       NormalEstimationOptions nopt;
       nopt.k = opt.normals_k;

@@ -39,6 +39,9 @@ struct Options {
   int normals_k = 0;                                         // --estimate-normals k  normals of both inputs on the device (0: off)
   double normals_radius = -1;                                // --estimate-normals-radius r  (default: unbounded)
   bool normals_radius_set = false;
+  int outliers_k = 0;                                        // --remove-outliers k  statistical outlier removal of both inputs (0: off)
+  double outliers_std = 2.0;                                 // --remove-outliers-std ratio  (needs k)
+  bool outliers_std_set = false;
   bool bad_value = false;                                    // a flag's value does not parse
 };
 
@@ -129,6 +132,17 @@ inline const Flag* flag_table(size_t* n) {
          o.normals_radius_set = true;
          if (end == v[0] || *end != '\0' || !(r > 0) || !(r < 3.0e38)) o.bad_value = true; else o.normals_radius = r;
        }},
+      {"--remove-outliers", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long k = std::strtol(v[0], &end, 10);
+         if (end == v[0] || *end != '\0' || k < 1 || k > 32) o.bad_value = true; else o.outliers_k = int(k);
+       }},
+      {"--remove-outliers-std", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double s = std::strtod(v[0], &end);
+         o.outliers_std_set = true;
+         if (end == v[0] || *end != '\0' || !(s >= 0) || !std::isfinite(s)) o.bad_value = true; else o.outliers_std = s;
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -152,6 +166,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
   }
   if (o.bad_value) return Parse::Bad;
   if (o.normals_radius_set && o.normals_k == 0) return Parse::Bad;    // the radius needs --estimate-normals
+  if (o.outliers_std_set && o.outliers_k == 0) return Parse::Bad;      // the ratio needs --remove-outliers
   if (o.icp_trim_set && o.icp_loss != 1) return Parse::Bad;            // --icp-trim needs --icp-loss trimmed
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
@@ -182,6 +197,10 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
   std::fprintf(stderr, "\t     them and --icp-metric plane / gicp / color use P's (gicp: Q's too) when all are nonzero)\n");
+  std::fprintf(stderr, "\t[ --remove-outliers k (1..32; off) ] [ --remove-outliers-std ratio (needs k; 2.0, >= 0) ]\n");
+  std::fprintf(stderr, "\t    (statistical outlier removal of both inputs on the device, right after loading: a point is kept when the mean\n");
+  std::fprintf(stderr, "\t     distance to its k nearest others is at most mean + ratio * stddev over the cloud; point sets only, -r writes\n");
+  std::fprintf(stderr, "\t     the filtered input2)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -6,6 +6,7 @@
 //               k_gather_samples + k_spacing_hist (a histogram of d2 around 64 seeded sample points: the cell edge is their
 //               median 16th-neighbour distance) -> k_cell_keys -> radix sort of (cell, index) -> k_cell_ranges + k_gather:
 //               the cloud as cell-ordered float4 and the [begin, end) of every cell.
+//   lists and outlier removal (include/s4p_knn.h): s4p_knn.inc, on the same cloud and grid.
 //   estimate    queries in cell order (the cloud itself, or k_cell_keys + sort + k_gather of the caller's queries) ->
 //               k_knn_normals<K>: one lane per query, ring search with conservative box pruning, the k best (d2, index)
 //               sorted in registers, covariance in double, 3x3 Jacobi, the normal scattered to the caller's order.
@@ -20,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "s4p_knn.h"
 #include "s4p_normals.h"
 
 namespace s4p_nrm {
@@ -333,6 +335,8 @@ struct s4p_normals_ctx {
   float4* pos = nullptr;             // caller order
   float4* pts = nullptr;             // cell order
   uint2* range = nullptr;
+  void* arena = nullptr;             // work memory of the s4p_knn.h calls: grows, never shrinks
+  size_t arena_bytes = 0;
 };
 
 namespace {
@@ -587,6 +591,8 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
 
 }  // namespace
 
+#include "s4p_knn.inc"                   // include/s4p_knn.h: neighbour lists and outlier removal on the same context
+
 extern "C" {
 
 const char* s4p_normals_last_error(const s4p_normals_ctx* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -621,7 +627,7 @@ void s4p_normals_destroy(s4p_normals_ctx* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->st) (void)hipStreamSynchronize(h->st);
-  dfree(h->pos); dfree(h->pts); dfree(h->range);
+  dfree(h->pos); dfree(h->pts); dfree(h->range); dfree(h->arena);
   if (h->st) (void)hipStreamDestroy(h->st);
   delete h;
 }

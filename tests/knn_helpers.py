@@ -1,0 +1,144 @@
+"""Test-side restatement of the neighbour-list and outlier-removal contract (include/s4p_knn.h) on top of the normals
+restatement (tests/normals_helpers.py): lists from the numpy lexsort brute force or from tests/normals_cpu, d2 recomputed in
+numpy float32 in the contract's order, lists without self as the first k of (the k + 1 list minus the own index), the mean
+neighbour distances in double in ascending order, and the clouds the tests share."""
+import math
+import os
+import subprocess
+
+import numpy as np
+
+from tests import normals_helpers as NH
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 2.0 ** -52
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def d2_of(X, Q, idx):
+    """float32 d2 of every listed neighbour, dx*dx + (dy*dy + dz*dz) with dx = fl(x_j - q_x); +inf where idx is -1."""
+    X = np.asarray(X, np.float32); Q = np.asarray(Q, np.float32)
+    j = np.where(idx < 0, 0, idx)
+    dx = X[j, 0] - Q[:, None, 0]; dy = X[j, 1] - Q[:, None, 1]; dz = X[j, 2] - Q[:, None, 2]
+    d2 = (dx * dx + (dy * dy + dz * dz)).astype(np.float32)
+    d2[idx < 0] = np.float32(np.inf)
+    return d2
+
+
+def _without_self(idx1, own, k):
+    """First k of (each row of the k + 1 list minus the row's own index), -1 padded; and the counts."""
+    m = idx1.shape[0]
+    out = np.full((m, k), -1, np.int32)
+    cnt = np.zeros(m, np.int32)
+    for i in range(m):
+        row = idx1[i]
+        row = row[(row >= 0) & (row != own[i])][:k]
+        out[i, :len(row)] = row
+        cnt[i] = len(row)
+    return out, cnt
+
+
+def lists(knn_fn, X, k, radius=None, queries=None, exclude_self=False, own=None):
+    """(idx, d2, cnt) of the contract from a neighbour-set function knn_fn(X, k, radius, queries=) -> (idx, cnt) that includes
+    the point itself.  own: the cloud index of every query (exclude_self with sampled queries)."""
+    X = np.asarray(X, np.float32)
+    Q = X if queries is None else np.asarray(queries, np.float32)
+    if exclude_self:
+        own = np.arange(len(X)) if own is None else own
+        idx1, _ = knn_fn(X, k + 1, radius, queries=Q)
+        idx, cnt = _without_self(idx1, own, k)
+    else:
+        idx, cnt = knn_fn(X, k, radius, queries=Q)
+    finite = np.isfinite(Q).all(1)
+    idx[~finite] = -1
+    cnt[~finite] = 0
+    return idx, d2_of(X, Q, idx), cnt
+
+
+def numpy_lists(X, k, radius=None, queries=None, exclude_self=False):
+    with np.errstate(invalid="ignore"):
+        return lists(NH.numpy_knn, X, k, radius, queries, exclude_self)
+
+
+def cpu_lists(cpu, X, k, radius=None, sample=None, exclude_self=False, queries=None):
+    """The restatement's lists of the cloud's points X[sample] (or of free queries)."""
+    fn = lambda X_, k_, r_, queries: cpu.knn(X_, k_, r_, queries=queries, threads=16)      # noqa: E731
+    if queries is not None:
+        return lists(fn, X, k, radius, queries, False)
+    sample = np.arange(len(X)) if sample is None else sample
+    return lists(fn, X, k, radius, np.asarray(X, np.float32)[sample], exclude_self, own=sample)
+
+
+def mean_dist(d2, cnt):
+    """m_j: sqrt((double)d2) summed over the list in ascending order, in double, over cnt_j; 0 for an empty list."""
+    m = np.zeros(d2.shape[0], np.float64)
+    for t in range(d2.shape[1]):
+        on = cnt > t
+        m[on] = m[on] + np.sqrt(d2[on, t].astype(np.float64))
+    nz = cnt > 0
+    m[nz] = m[nz] / cnt[nz].astype(np.float64)
+    return m
+
+
+def sor_reference(m, std_ratio):
+    """(mu, sigma, t) of the contract from the m_j with correctly rounded sums (math.fsum)."""
+    n = len(m)
+    mu = math.fsum(m.tolist()) / n
+    var = math.fsum(((m - mu) ** 2).tolist()) / (n - 1) if n > 1 else 0.0
+    sigma = math.sqrt(var)
+    return mu, sigma, mu + std_ratio * sigma
+
+
+def plant(X, count):
+    """X plus `count` points uniform in X's bounding box scaled 1.5x about its centre (default_rng(5)), the whole permuted.
+    Returns (cloud float32, planted bool mask)."""
+    X = np.asarray(X, np.float32)
+    rng = np.random.default_rng(5)
+    lo, hi = X.min(0).astype(np.float64), X.max(0).astype(np.float64)
+    c, half = 0.5 * (lo + hi), 0.75 * (hi - lo)
+    extra = rng.uniform(c - half, c + half, size=(count, 3)).astype(np.float32)
+    whole = np.concatenate([X, extra])
+    planted = np.concatenate([np.zeros(len(X), bool), np.ones(count, bool)])
+    perm = rng.permutation(len(whole))
+    return np.ascontiguousarray(whole[perm]), planted[perm]
+
+
+def tiny_cloud(n, dup):
+    """n random points; with dup a third of them repeat earlier ones (ties at d2 = 0, broken by index)."""
+    rng = np.random.default_rng(1000 + n)
+    P = rng.uniform(0, 1, size=(n, 3)).astype(np.float32)
+    if dup and n >= 2:
+        c = max(1, n // 3)
+        P[n - c:] = P[rng.integers(0, n - c, c)]
+    return P
+
+
+TINY_N = (1, 2, 3, 8, 9, 33, 255, 256, 257)
+
+
+def tiny_radius(n):
+    """About half a neighbour expected within it: most lists come out short, some hold a few."""
+    return np.float32(0.5 * n ** (-1.0 / 3.0))
+
+
+def write_obj(path, pts, faces=()):
+    with open(path, "w") as f:
+        f.write("# points\n")
+        for p in pts:
+            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
+        for t in faces:
+            f.write("f %d %d %d\n" % tuple(t))
+        f.write("# End of File\n")
+
+
+def build_app(outdir, extra=()):
+    """tests/knn_app/main.cpp against the facade header and libsuper4pcs_normals.so."""
+    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
+    exe = os.path.join(str(outdir), "knn_app")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + list(extra) +
+                          [os.path.join(ROOT, "tests", "knn_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_normals",
+                           "-Wl,-rpath," + libdir, "-o", exe])
+    return exe

@@ -1,0 +1,248 @@
+"""Outlier removal on the MI355X (include/s4p_knn.h): the statistical filter's mean distances, mu, sigma, t and mask against
+the CPU restatement with correctly rounded sums, its edge cases, the radius filter's mask against numpy, determinism,
+numpy against torch, the facade application and the command line's --remove-outliers."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import helpers as H
+from tests import knn_helpers as KH
+from tests import normals_helpers as NH
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.gpu
+EPS = KH.EPS
+
+
+@pytest.fixture(scope="module")
+def knn():
+    from super4pcs_amd import build as B
+    B.build_normals()
+    from super4pcs_amd import knn
+    return knn
+
+
+@pytest.fixture(scope="module")
+def cpu(tmp_path_factory):
+    return NH.build_cpu(tmp_path_factory.mktemp("knn_cpu"))
+
+
+@pytest.fixture(scope="module")
+def planted():
+    from super4pcs_amd import datasets as D
+    return {"bumpy": KH.plant(D.bumpy_pair(6000, overlap=0.5, delta=0.004, seed=12)[0], 60),
+            "lidar": KH.plant(D.lidar_pair_scaled(0.004, delta=0.05)[0], 200)}
+
+
+@pytest.fixture(scope="module")
+def contexts(knn, planted):
+    out = {}
+    for name, (X, _) in planted.items():
+        ctx = knn.Knn(0)
+        ctx.set_cloud(X)
+        out[name] = ctx
+    yield out
+    for ctx in out.values():
+        ctx.close()
+
+
+@pytest.fixture(scope="module")
+def reference_lists(cpu, planted):
+    """The restatement's 33 nearest of every point (itself included), once per cloud: every k's list without self is the
+    first k of (these minus the own index)."""
+    return {name: cpu.knn(X, 33, None, threads=16)[0] for name, (X, _) in planted.items()}
+
+
+def _reference_m(X, idx33, k):
+    fn = lambda X_, k_, r_, queries: (idx33[:, :k_].copy(), (idx33[:, :k_] >= 0).sum(1).astype(np.int32))      # noqa: E731
+    _, d2, cnt = KH.lists(fn, X, k, None, None, True)
+    assert (cnt == min(k, len(X) - 1)).all()
+    return KH.mean_dist(d2, cnt)
+
+
+def _check_against_reference(n, k, ratio, md, stats, keep, m_ref, what):
+    """The bounds, with eps = 2^-52 (twice the unit roundoff, so every "one rounding" below is covered with room):
+    - m_j: k sqrt roundings, k - 1 additions and one division of non-negative terms: relative (k + 2) eps.
+    - mu, t: any summation order of n non-negative terms is within relative (n - 1) eps / 2 of the exact sum; with the
+      division, relative n eps.  t = mu + ratio sigma inherits it (sigma's bound below is no larger for n >= 8).
+    - sigma: S = sum (m_j - mu')^2 with the device's mu' = mu (1 + theta), |theta| <= n eps.  Since sum (m_j - mu) = 0,
+      sum (m_j - mu')^2 = S + n (mu - mu')^2: the error of mu enters at second order, n (n eps mu)^2.  Each term carries
+      the rounding of the difference (twice, squared) and of the square, 3 eps / 2, and the sum of n non-negative terms
+      (n - 1) eps / 2; the division by n - 1 and the square root add 3 eps / 2 and the root halves what came before.  In
+      all |sigma' - sigma| / sigma <= (n / 4 + 4) eps + n (n eps mu)^2 / (2 S), and the same 4 eps again for the
+      reference's own (m - mu)^2 terms: (n / 4 + 8) eps + (n eps mu / sigma)^2 / 2 is asserted."""
+    mu, sigma, t = KH.sor_reference(m_ref, ratio)
+    rel_m = np.max(np.abs(md - m_ref) / np.where(m_ref > 0, m_ref, 1.0))
+    gap = np.min(np.abs(m_ref - t)) / t if t > 0 else np.inf
+    keep_ref = m_ref <= t
+    print("%s: n %d k %d ratio %g: mu %.17g (ref %.17g) sigma %.17g (ref %.17g) t %.17g (ref %.17g) max rel m %.3g "
+          "(equal %s) gap %.3g kept %d (ref %d)" % (what, n, k, ratio, stats["mean"], mu, stats["stddev"], sigma, stats["threshold"], t,
+                                                     rel_m, np.array_equal(md, m_ref), gap, stats["kept"], keep_ref.sum()))
+    assert stats["n"] == n
+    assert rel_m <= (k + 2) * EPS
+    assert abs(stats["mean"] - mu) <= n * EPS * mu
+    assert abs(stats["threshold"] - t) <= n * EPS * t
+    if sigma > 0:
+        assert abs(stats["stddev"] - sigma) <= ((n / 4 + 8) * EPS + 0.5 * (n * EPS * mu / sigma) ** 2) * sigma
+    else:
+        assert stats["stddev"] == 0.0
+    # the mask is the device's own comparison, exactly, and the reference's
+    assert np.array_equal(keep, md <= stats["threshold"]) and stats["kept"] == int(keep.sum())
+    assert gap > 1e-9                                    # no reference m_j so near the reference t that rounding could flip it
+    assert np.array_equal(keep, keep_ref)
+    return keep_ref
+
+
+@pytest.mark.parametrize("name,k,ratio", [("bumpy", 1, 2.0), ("bumpy", 8, 2.0), ("bumpy", 16, 2.0), ("bumpy", 32, 2.0),
+                                          ("lidar", 16, 2.0), ("lidar", 8, 1.0)])
+def test_statistical_removal_equals_the_reference(knn, planted, contexts, reference_lists, name, k, ratio):
+    X, is_planted = planted[name]
+    keep, stats, md = contexts[name].statistical_outliers(k, ratio)
+    assert keep.dtype == bool and md.dtype == np.float64 and keep.shape == (len(X),) and md.shape == (len(X),)
+    m_ref = _reference_m(X, reference_lists[name], k)
+    _check_against_reference(len(X), k, ratio, md, stats, keep, m_ref, name)
+    if name == "bumpy":                                  # the filter does its job: the surface stays, the strays go
+        assert keep[~is_planted].all() and (~keep[is_planted]).sum() >= 51, (~keep[is_planted]).sum()
+
+
+def test_statistical_removal_edge_cases(knn, cpu):
+    ctx = knn.Knn(0)
+    # n = 1: no neighbour, m = 0, sigma = 0, kept
+    ctx.set_cloud(np.array([[1, 2, 3]], np.float32))
+    keep, st, md = ctx.statistical_outliers(16, 2.0)
+    assert keep.tolist() == [True] and md.tolist() == [0.0]
+    assert st == {"n": 1, "mean": 0.0, "stddev": 0.0, "threshold": 0.0, "kept": 1}
+    # n = 2: each is the other's only neighbour
+    X = np.array([[0, 0, 0], [3, 4, 0]], np.float32)
+    ctx.set_cloud(X)
+    keep, st, md = ctx.statistical_outliers(16, 2.0)
+    assert keep.tolist() == [True, True] and md.tolist() == [5.0, 5.0]
+    assert st == {"n": 2, "mean": 5.0, "stddev": 0.0, "threshold": 5.0, "kept": 2}
+    # 300 identical points: every m = 0, t = 0, all kept because 0 <= 0
+    ctx.set_cloud(np.tile(np.array([[0.5, -0.25, 2.0]], np.float32), (300, 1)))
+    keep, st, md = ctx.statistical_outliers(8, 2.0)
+    assert keep.all() and not md.any() and st == {"n": 300, "mean": 0.0, "stddev": 0.0, "threshold": 0.0, "kept": 300}
+    # k = 32 on 20 points: every list holds the 19 others
+    X = np.random.default_rng(4).uniform(size=(20, 3)).astype(np.float32)
+    ctx.set_cloud(X)
+    for ratio in (0.0, 1.0):
+        keep, st, md = ctx.statistical_outliers(32, ratio)
+        _, d2, cnt = KH.numpy_lists(X, 32, exclude_self=True)
+        assert (cnt == 19).all()
+        _check_against_reference(20, 32, ratio, md, st, keep, KH.mean_dist(d2, cnt), "20 points")
+    ctx.close()
+
+
+def _numpy_radius_mask(X, r, mn):
+    """At least mn other points with d2 <= fl(r * r): a count over the whole float32 distance matrix, in row blocks."""
+    X = np.asarray(X, np.float32)
+    r2 = np.float32(r) * np.float32(r)
+    out = np.empty(len(X), bool)
+    for lo in range(0, len(X), 1000):
+        Q = X[lo:lo + 1000]
+        dx = X[None, :, 0] - Q[:, None, 0]; dy = X[None, :, 1] - Q[:, None, 1]; dz = X[None, :, 2] - Q[:, None, 2]
+        out[lo:lo + 1000] = ((dx * dx + (dy * dy + dz * dz)) <= r2).sum(1) - 1 >= mn
+    return out
+
+
+def test_radius_removal_equals_numpy(knn, planted, contexts):
+    X, is_planted = planted["bumpy"]
+    for r, mn in ((0.01, 1), (0.02, 8), (0.05, 32)):
+        want = _numpy_radius_mask(X, r, mn)
+        keep = contexts["bumpy"].radius_outliers(r, mn)
+        assert keep.dtype == bool and np.array_equal(keep, want), (r, mn, np.flatnonzero(keep != want)[:5])
+        print("radius %g, min %d: kept %d of %d, planted kept %d" % (r, mn, keep.sum(), len(X), keep[is_planted].sum()))
+        assert 0 < keep.sum() < len(X)
+    for n in KH.TINY_N:
+        for dup in (False, True):
+            Xs = KH.tiny_cloud(n, dup)
+            ctx = knn.Knn(0)
+            ctx.set_cloud(Xs)
+            for mn in (1, 2, 8, 32):
+                r = float(KH.tiny_radius(n)) * (1.0 if mn == 1 else 2.5)
+                assert np.array_equal(ctx.radius_outliers(r, mn), _numpy_radius_mask(Xs, r, mn)), (n, dup, mn)
+            ctx.close()
+
+
+def test_two_calls_and_numpy_torch_agree(knn, planted, contexts):
+    import torch
+    X, _ = planted["lidar"]
+    ctx = contexts["lidar"]
+    k1, s1, m1 = ctx.statistical_outliers(16, 2.0)
+    k2, s2, m2 = ctx.statistical_outliers(16, 2.0)
+    assert np.array_equal(k1, k2) and np.array_equal(m1.view(np.uint64), m2.view(np.uint64))
+    assert all(np.float64(s1[f]).view(np.uint64) == np.float64(s2[f]).view(np.uint64) for f in ("mean", "stddev", "threshold")) and s1 == s2
+    r1 = ctx.radius_outliers(0.05, 8)
+    assert np.array_equal(r1, ctx.radius_outliers(0.05, 8))
+    # the one-shot functions, numpy and torch
+    kept, mask, stats = knn.remove_statistical_outliers(X, k=16, std_ratio=2.0)
+    assert isinstance(kept, np.ndarray) and np.array_equal(mask, k1) and stats == s1 and np.array_equal(kept, X[k1])
+    Xt = torch.from_numpy(X).cuda()
+    kept_t, mask_t, stats_t = knn.remove_statistical_outliers(Xt, k=16, std_ratio=2.0)
+    assert kept_t.is_cuda and mask_t.is_cuda and mask_t.dtype == torch.bool and stats_t == s1
+    assert np.array_equal(mask_t.cpu().numpy(), k1) and np.array_equal(kept_t.cpu().numpy(), X[k1])
+    tctx = knn.Knn(0)
+    tctx.set_cloud(Xt)
+    _, _, md_t = tctx.statistical_outliers(16, 2.0)
+    assert md_t.is_cuda and md_t.dtype == torch.float64 and np.array_equal(md_t.cpu().numpy().view(np.uint64), m1.view(np.uint64))
+    tctx.close()
+    kept, mask = knn.remove_radius_outliers(X, 0.05, 8)
+    kept_t, mask_t = knn.remove_radius_outliers(Xt, 0.05, 8)
+    assert np.array_equal(mask, r1) and np.array_equal(mask_t.cpu().numpy(), r1) and np.array_equal(kept_t.cpu().numpy(), kept)
+    assert np.array_equal(kept, X[r1])
+
+
+def test_facade_application_gives_the_same_mask(knn, planted, contexts, tmp_path):
+    X, _ = planted["bumpy"]
+    exe = KH.build_app(tmp_path)
+    np.savetxt(tmp_path / "P.xyz", X, fmt="%.9g")
+    Xr = np.loadtxt(tmp_path / "P.xyz", dtype=np.float32)
+    assert np.array_equal(Xr, X)
+    for args, want in ((["stat", "16", "2.0"], contexts["bumpy"].statistical_outliers(16, 2.0)[0]),
+                       (["radius", "0.02", "8"], contexts["bumpy"].radius_outliers(0.02, 8))):
+        r = subprocess.run([exe, str(tmp_path / "P.xyz")] + args, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        lines = r.stdout.splitlines()
+        n = len(X)
+        assert lines[0] == "removed %d" % (~want).sum()
+        mask = np.array([int(v) for v in lines[1:1 + n]], bool)
+        assert np.array_equal(mask, want)
+        rest = np.array([[float(v) for v in ln.split()] for ln in lines[1 + n:]])
+        # erased in place, order kept, normals and colours moved with their points
+        assert np.array_equal(rest[:, :3].astype(np.float32), X[want]) and (rest[:, 3] == 1.0).all()
+        assert np.array_equal(rest[:, 4].astype(np.int64), np.flatnonzero(want))
+
+
+def test_cli_remove_outliers_matches_the_python_path(knn, s4p_lib_built, tmp_path):
+    from super4pcs_amd import build as B, capi
+    delta, overlap, n_s = 0.01, 0.6, 200
+    P, Q, _ = H.small_pair(8000, delta=delta, seed=33)
+    P, _ = KH.plant(P, 40)
+    Q, _ = KH.plant(Q, 40)
+    KH.write_obj(tmp_path / "P.obj", P); KH.write_obj(tmp_path / "Q.obj", Q)
+    cli = B.build_cli()
+    common = [cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-n", str(n_s), "-t", "1000"]
+    r = subprocess.run(common + ["--remove-outliers", "16", "-m", str(tmp_path / "mat.txt"), "-r", str(tmp_path / "reg.obj")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    got = np.array([[float(v) for v in ln.split()] for ln in (tmp_path / "mat.txt").read_text().splitlines()[2:6]])
+    # the Python path: filter both clouds, then register with the same options
+    Pk, pm, _ = knn.remove_statistical_outliers(P, k=16, std_ratio=2.0)
+    Qk, qm, _ = knn.remove_statistical_outliers(Q, k=16, std_ratio=2.0)
+    assert 0 < (~pm).sum() < 400 and 0 < (~qm).sum() < 400
+    gm = capi.Matcher(capi.make_options(delta, overlap, n_s))
+    _, M, gQ = gm.compute_transformation(Pk, Qk)
+    print("removed %d / %d\ncli:\n%s\npython:\n%s" % ((~pm).sum(), (~qm).sum(), got, M))
+    assert np.max(np.abs(got - np.asarray(M, np.float64))) <= 1e-5
+    assert "Removed outliers: k 16" in r.stdout + r.stderr
+    # -r: the filtered Q, registered
+    head, body = (tmp_path / "reg.ply").read_bytes().split(b"end_header\n", 1)
+    assert b"element vertex %d\n" % len(Qk) in head
+    assert np.array_equal(np.frombuffer(body, "<f4").reshape(-1, 3), gQ)
+    # an input with faces is refused
+    KH.write_obj(tmp_path / "F.obj", Q[:100], faces=[(1, 2, 3)])
+    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "F.obj"), "--remove-outliers", "16"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 254 and "faces" in r.stdout + r.stderr
