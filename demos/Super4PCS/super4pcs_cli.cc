@@ -9,6 +9,7 @@
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
 //             [--remove-outliers k] [--remove-outliers-std ratio]
+//             [--voxel-size v] [--icp-scales v1,v2,...]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -24,6 +25,12 @@
 // other points above mean + ratio * stddev, ratio --remove-outliers-std, default 2) right after loading, before
 // --estimate-normals, the matcher and ICP; -r then writes the filtered, registered second input.  Faces index the vertex
 // list, so an input with faces is refused (exit status 254).
+// --voxel-size v replaces both inputs by the means of their occupied voxels of edge v (algorithms/voxelgrid.h) after
+// --remove-outliers and before --estimate-normals, the matcher and ICP; normals and colours are averaged when every point
+// has one; -r then writes the downsampled, registered second input.  An input with faces is refused (exit status 254).
+// --icp-scales v1,v2,... (needs --icp) refines coarse to fine (algorithms/icp_multiscale.h): one level per voxel size, both
+// inputs downsampled at it (the second in its own frame; 0, allowed last, takes them as they are), the level's distance
+// max(--icp-dist, 3 v) and --icp iterations per level; every --icp-metric and --icp-loss applies to every level.
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
@@ -31,9 +38,11 @@
 #include <vector>
 
 #include "super4pcs/algorithms/icp.h"
+#include "super4pcs/algorithms/icp_multiscale.h"
 #include "super4pcs/algorithms/normals.h"
 #include "super4pcs/algorithms/outliers.h"
 #include "super4pcs/algorithms/super4pcs.h"
+#include "super4pcs/algorithms/voxelgrid.h"
 #include "super4pcs/io/io.h"
 #include "super4pcs/utils/geometry.h"
 
@@ -70,6 +79,17 @@ struct Mesh {                                    // everything IOManager returns
     compact(normals);
     compact(tex);
     return removed;
+  }
+  // voxel-grid downsampling of the points; the per-vertex normal list is rebuilt from the averaged normals when they were
+  // carried (every point had one), the texture list does not survive
+  size_t voxel_downsample(const VoxelGridOptions& vopt) {
+    const size_t m = VoxelDownsample(points, vopt);
+    bool carried = !points.empty() && normals.size() != 0;
+    for (const Point3D& pt : points) carried = carried && (pt.normal()(0) != 0 || pt.normal()(1) != 0 || pt.normal()(2) != 0);
+    normals.clear();
+    if (carried) for (const Point3D& pt : points) normals.push_back(pt.normal());
+    tex.clear();
+    return m;
   }
   bool save(IOManager& io, const std::string& path) const {
     return io.WriteObject(path.c_str(), points, tex, normals, faces, materials);
@@ -113,6 +133,10 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
     log.Log<Utils::ErrorReport>("--remove-outliers: an input has faces; faces index the vertex list, so only point sets can be filtered");
     return -2;
   }
+  if (opt.voxel_size > 0 && (!P.faces.empty() || !Q.faces.empty())) {
+    log.Log<Utils::ErrorReport>("--voxel-size: an input has faces; faces index the vertex list, so only point sets can be downsampled");
+    return -2;
+  }
   try {
     if (opt.outliers_k > 0) {
       OutlierRemovalOptions oopt;
@@ -120,6 +144,13 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       oopt.std_ratio = opt.outliers_std;
       const size_t rp = P.remove_outliers(oopt), rq = Q.remove_outliers(oopt);
       log.Log<Utils::Verbose>("Removed outliers: k ", opt.outliers_k, ", ratio ", opt.outliers_std, ": ", rp, " of input1, ", rq, " of input2");
+    }
+    if (opt.voxel_size > 0) {
+      VoxelGridOptions vopt;
+      vopt.voxel_size = opt.voxel_size;
+      const size_t np = P.points.size(), nq = Q.points.size();
+      const size_t mp = P.voxel_downsample(vopt), mq = Q.voxel_downsample(vopt);
+      log.Log<Utils::Verbose>("Voxel grid: edge ", opt.voxel_size, ": ", mp, " of ", np, " points of input1, ", mq, " of ", nq, " of input2");
     }
     if (opt.normals_k > 0) {
       NormalEstimationOptions nopt;
@@ -129,6 +160,8 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       EstimateNormals(Q.points, nopt);
       log.Log<Utils::Verbose>("Estimated normals: k ", opt.normals_k, ", radius ", opt.normals_radius);
     }
+    std::vector<Point3D> Q0;                                // the second input in its own frame: the matcher moves Q.points
+    if (opt.icp_iterations > 0 && !opt.icp_scales.empty()) Q0 = Q.points;
     MatchSuper4PCS matcher(mopt, log);
     log.Log<Utils::Verbose>("Use Super4PCS");
     score = matcher.ComputeTransformation(P.points, &Q.points, mat, Sampling::UniformDistSampler(), Progress());
@@ -150,9 +183,26 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       icp.loss = opt.icp_loss == 1 ? ICPLoss::Trimmed : (opt.icp_loss == 2 ? ICPLoss::Huber : (opt.icp_loss == 3 ? ICPLoss::Tukey : ICPLoss::None));
       icp.trim_fraction = opt.icp_trim > 0 ? opt.icp_trim : opt.overlap;
       icp.loss_scale = opt.icp_loss_scale;
-      ICPResult res;
-      RefineICP(P.points, &Q.points, mat, icp, &res);
-      log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);
+      if (!opt.icp_scales.empty()) {
+        std::vector<ICPLevel> levels;
+        for (double v : opt.icp_scales) {
+          ICPLevel level;
+          level.voxel_size = v;
+          level.max_distance = icp.max_distance > 3.0 * v ? icp.max_distance : 3.0 * v;
+          level.max_iterations = opt.icp_iterations;
+          levels.push_back(level);
+        }
+        std::vector<ICPResult> res;
+        RefineICPMultiScale(P.points, &Q0, mat, icp, levels, &res);
+        for (size_t i = 0; i < Q0.size(); ++i) Q.points[i].pos() = Q0[i].pos();
+        for (size_t l = 0; l < res.size(); ++l)
+          log.Log<Utils::Verbose>("ICP level ", l, " (voxel ", levels[l].voxel_size, ", distance ", levels[l].max_distance, "): ",
+                                  res[l].iterations, " iterations, rmse ", res[l].rmse, ", fitness ", res[l].fitness);
+      } else {
+        ICPResult res;
+        RefineICP(P.points, &Q.points, mat, icp, &res);
+        log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);
+      }
     }
   } catch (const std::exception& e) {
     log.Log<Utils::ErrorReport>("[Error]: ", e.what());

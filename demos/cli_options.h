@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include <super4pcs/shared4pcs.h>
 
@@ -42,6 +43,9 @@ struct Options {
   int outliers_k = 0;                                        // --remove-outliers k  statistical outlier removal of both inputs (0: off)
   double outliers_std = 2.0;                                 // --remove-outliers-std ratio  (needs k)
   bool outliers_std_set = false;
+  double voxel_size = -1;                                    // --voxel-size v  voxel-grid downsampling of both inputs (off)
+  std::vector<double> icp_scales;                            // --icp-scales v1,v2,...  multi-scale ICP levels, coarse to fine (needs --icp)
+  bool icp_scales_set = false;
   bool bad_value = false;                                    // a flag's value does not parse
 };
 
@@ -143,6 +147,30 @@ inline const Flag* flag_table(size_t* n) {
          o.outliers_std_set = true;
          if (end == v[0] || *end != '\0' || !(s >= 0) || !std::isfinite(s)) o.bad_value = true; else o.outliers_std = s;
        }},
+      {"--voxel-size", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double s = std::strtod(v[0], &end);
+         if (end == v[0] || *end != '\0' || !(s > 0) || !(s < 3.0e38) || !(float(s) > 0.f)) o.bad_value = true; else o.voxel_size = s;
+       }},
+      {"--icp-scales", 1, [](Options& o, char** v) {
+         // v1,v2,...: at most 16 sizes, each > 0 and representable as a float, non-increasing; only the last may be 0
+         o.icp_scales_set = true;
+         o.icp_scales.clear();
+         const char* p = v[0];
+         for (;;) {
+           char* end = nullptr;
+           const double s = std::strtod(p, &end);
+           const bool last = *end == '\0';
+           if (end == p || (*end != ',' && !last) || !(s >= 0) || !(s < 3.0e38) || (s > 0 && !(float(s) > 0.f)) || (s == 0 && !last) ||
+               (!o.icp_scales.empty() && s > o.icp_scales.back()) || o.icp_scales.size() >= 16) {
+             o.bad_value = true;
+             return;
+           }
+           o.icp_scales.push_back(s);
+           if (last) return;
+           p = end + 1;
+         }
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -173,6 +201,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.icp_gicp_epsilon_set && !o.icp_gicp) return Parse::Bad;        // --icp-gicp-epsilon needs --icp-metric gicp
   if (o.icp_color && o.icp_loss != 0) return Parse::Bad;               // the coloured metric takes no loss
   if (o.icp_color_lambda_set && !o.icp_color) return Parse::Bad;       // --icp-color-lambda needs --icp-metric color
+  if (o.icp_scales_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-scales needs --icp
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -201,6 +230,13 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t    (statistical outlier removal of both inputs on the device, right after loading: a point is kept when the mean\n");
   std::fprintf(stderr, "\t     distance to its k nearest others is at most mean + ratio * stddev over the cloud; point sets only, -r writes\n");
   std::fprintf(stderr, "\t     the filtered input2)\n");
+  std::fprintf(stderr, "\t[ --voxel-size v (> 0; off) ]\n");
+  std::fprintf(stderr, "\t    (voxel-grid downsampling of both inputs on the device, after --remove-outliers and before --estimate-normals:\n");
+  std::fprintf(stderr, "\t     one point per occupied voxel of edge v, the mean of its members; point sets only, -r writes the\n");
+  std::fprintf(stderr, "\t     downsampled input2)\n");
+  std::fprintf(stderr, "\t[ --icp-scales v1,v2,... (needs --icp; off) ]\n");
+  std::fprintf(stderr, "\t    (multi-scale ICP: one level per voxel size, coarse to fine, non-increasing, the last may be 0 = the inputs as\n");
+  std::fprintf(stderr, "\t     they are; level distance max(--icp-dist, 3 v), --icp iterations per level)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -7,6 +7,7 @@
 //               median 16th-neighbour distance) -> k_cell_keys -> radix sort of (cell, index) -> k_cell_ranges + k_gather:
 //               the cloud as cell-ordered float4 and the [begin, end) of every cell.
 //   lists and outlier removal (include/s4p_knn.h): s4p_knn.inc, on the same cloud and grid.
+//   voxel-grid downsampling (include/s4p_voxel.h): s4p_voxel.inc, of a cloud passed per call, on the context's stream.
 //   estimate    queries in cell order (the cloud itself, or k_cell_keys + sort + k_gather of the caller's queries) ->
 //               k_knn_normals<K>: one lane per query, ring search with conservative box pruning, the k best (d2, index)
 //               sorted in registers, covariance in double, 3x3 Jacobi, the normal scattered to the caller's order.
@@ -592,6 +593,7 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
 }  // namespace
 
 #include "s4p_knn.inc"                   // include/s4p_knn.h: neighbour lists and outlier removal on the same context
+#include "s4p_voxel.inc"                 // include/s4p_voxel.h: voxel-grid downsampling on the context's stream and arena
 
 extern "C" {
 
