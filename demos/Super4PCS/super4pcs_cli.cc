@@ -183,6 +183,8 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       icp.loss = opt.icp_loss == 1 ? ICPLoss::Trimmed : (opt.icp_loss == 2 ? ICPLoss::Huber : (opt.icp_loss == 3 ? ICPLoss::Tukey : ICPLoss::None));
       icp.trim_fraction = opt.icp_trim > 0 ? opt.icp_trim : opt.overlap;
       icp.loss_scale = opt.icp_loss_scale;
+      icp.reciprocal = opt.icp_reciprocal;
+      icp.normal_angle_deg = opt.icp_normal_angle;
       if (!opt.icp_scales.empty()) {
         std::vector<ICPLevel> levels;
         for (double v : opt.icp_scales) {

@@ -37,6 +37,9 @@ struct Options {
   double icp_trim = -1;                                      // --icp-trim  (trimmed; default: the overlap -o)
   double icp_loss_scale = -1;                                // --icp-loss-scale  (huber / tukey; default: estimated)
   bool icp_trim_set = false, icp_loss_scale_set = false;
+  bool icp_reciprocal = false;                               // --icp-reciprocal  keep reciprocal pairs only (needs --icp)
+  double icp_normal_angle = -1;                              // --icp-normal-angle deg  reject pairs whose normals differ by more (needs --icp)
+  bool icp_normal_angle_set = false;
   int normals_k = 0;                                         // --estimate-normals k  normals of both inputs on the device (0: off)
   double normals_radius = -1;                                // --estimate-normals-radius r  (default: unbounded)
   bool normals_radius_set = false;
@@ -125,6 +128,13 @@ inline const Flag* flag_table(size_t* n) {
          o.icp_loss_scale_set = true;
          if (end == v[0] || *end != '\0' || !(s > 0) || !std::isfinite(s)) o.bad_value = true; else o.icp_loss_scale = s;
        }},
+      {"--icp-reciprocal", 0, [](Options& o, char**) { o.icp_reciprocal = true; }},
+      {"--icp-normal-angle", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const double a = std::strtod(v[0], &end);
+         o.icp_normal_angle_set = true;
+         if (end == v[0] || *end != '\0' || !(a >= 0) || !(a <= 90)) o.bad_value = true; else o.icp_normal_angle = a;
+       }},
       {"--estimate-normals", 1, [](Options& o, char** v) {
          char* end = nullptr;
          const long k = std::strtol(v[0], &end, 10);
@@ -202,6 +212,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.icp_color && o.icp_loss != 0) return Parse::Bad;               // the coloured metric takes no loss
   if (o.icp_color_lambda_set && !o.icp_color) return Parse::Bad;       // --icp-color-lambda needs --icp-metric color
   if (o.icp_scales_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-scales needs --icp
+  if ((o.icp_reciprocal || o.icp_normal_angle_set) && o.icp_iterations == 0) return Parse::Bad;    // pair rejection needs --icp
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -223,6 +234,8 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t    inputs and takes no --icp-loss) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss none|trimmed|huber|tukey (none) ] [ --icp-trim fraction (trimmed; -o) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss-scale s (huber, tukey; estimated) ]  (robust ICP)\n");
+  std::fprintf(stderr, "\t[ --icp-reciprocal ] [ --icp-normal-angle deg (in [0, 90]; off) ]  (pair rejection, needs --icp, any metric and loss:\n");
+  std::fprintf(stderr, "\t    keep a pair only when it is nearest in both directions / when its normals, up to sign, differ by at most deg)\n");
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
   std::fprintf(stderr, "\t     them and --icp-metric plane / gicp / color use P's (gicp: Q's too) when all are nonzero)\n");

@@ -2,6 +2,7 @@
 // documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
 // of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h,
 // include/s4p_icp_plane.h, include/s4p_icp_gicp.h, include/s4p_icp_color.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
+// Pair rejection (include/s4p_icp_reject.h: reciprocal pairs, normal angle) applies to every metric and loss.
 // Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
 //
 // ICPMetric::Generalized needs normals of both clouds.  Q's own are used when every point of Q has a nonzero one.
@@ -24,6 +25,7 @@
 
 #include <dlfcn.h>
 
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <stdexcept>
@@ -35,6 +37,7 @@
 #include "s4p_icp_robust.h"
 #include "s4p_icp_gicp.h"
 #include "s4p_icp_color.h"
+#include "s4p_icp_reject.h"
 #include "s4p_normals.h"
 #include "super4pcs/algorithms/match4pcsBase.h"
 
@@ -65,6 +68,13 @@ struct ICPOptions {
   ICPLoss loss = ICPLoss::None;
   double trim_fraction = 1.0;       // Trimmed: in (0, 1], e.g. the registration's overlap
   double loss_scale = -1.0;         // Huber / Tukey
+  // Pair rejection (include/s4p_icp_reject.h), for every metric and loss.  reciprocal: a pair is kept only when the source
+  // point is the nearest one of its target point too.  normal_angle_deg >= 0: a pair is kept only when the target normal and
+  // the (rotated) source normal are at most that far apart, up to sign unless normals_oriented ([0, 90] degrees, oriented
+  // [0, 180]); the normals of both clouds are obtained as ICPMetric::Generalized obtains them.  < 0: off.
+  bool reciprocal = false;
+  double normal_angle_deg = -1;
+  bool normals_oriented = false;
 };
 
 struct ICPResult {
@@ -152,7 +162,10 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
   H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
   const bool plane = options.metric == ICPMetric::PointToPlane;
-  if (plane || gicp || colored) {
+  const bool by_normals = options.normal_angle_deg >= 0;
+  if (by_normals && !(options.normal_angle_deg <= (options.normals_oriented ? 180.0 : 90.0)))
+    throw std::invalid_argument("RefineICP: normal_angle_deg must be at most 90 (oriented normals: 180)");
+  if (plane || gicp || colored || by_normals) {
     bool all = true;
     for (const Point3D& pt : P) {
       const auto& nv = pt.normal();
@@ -168,7 +181,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
       H.check(s4p_icp_estimate_normals(H.h, float(r), 6));
     }
   }
-  if (gicp) {
+  if (gicp || by_normals) {
     bool all = true;
     for (const Point3D& pt : *Q) {
       const auto& nv = pt.normal();
@@ -196,6 +209,18 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
     H.check(s4p_icp_set_source_intensity(H.h, iq.data(), int64_t(Q->size())));
     const double r = options.normal_radius > 0 ? options.normal_radius : options.max_distance;
     H.check(s4p_icp_estimate_color_gradients(H.h, float(r), 6));
+  }
+  if (options.reciprocal || by_normals) {
+    s4p_icp_reject rej;
+    s4p_icp_reject_defaults(&rej);
+    rej.reciprocal = options.reciprocal ? 1 : 0;
+    if (by_normals) {
+      rej.normal_mode = options.normals_oriented ? S4P_ICP_REJECT_NORMALS_ORIENTED : S4P_ICP_REJECT_NORMALS_UNORIENTED;
+      const double c = std::cos(options.normal_angle_deg * (3.14159265358979323846 / 180.0));
+      const double lo = options.normals_oriented ? -1.0 : 0.0;
+      rej.normal_cos = c < lo ? lo : (c > 1.0 ? 1.0 : c);
+    }
+    H.check(s4p_icp_set_rejection(H.h, &rej));
   }
   s4p_icp_params prm;
   s4p_icp_default_params(&prm);

@@ -1,6 +1,7 @@
-"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h and
-include/s4p_icp_color.h (libsuper4pcs_icp.so): point-to-point, point-to-plane, generalized (plane-to-plane) and coloured ICP
-refinement on the full-resolution clouds, with optional robust losses for the first two.
+"""ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
+include/s4p_icp_color.h and include/s4p_icp_reject.h (libsuper4pcs_icp.so): point-to-point, point-to-plane, generalized
+(plane-to-plane) and coloured ICP refinement on the full-resolution clouds, with optional robust losses for the first two and
+optional correspondence rejection (reciprocal pairs, normal angle) for all of them.
 
     from super4pcs_amd import icp
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
@@ -8,6 +9,7 @@ refinement on the full-resolution clouds, with optional robust losses for the fi
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, loss="trimmed", trim_fraction=0.6)   # trimmed ICP
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="gicp")    # normals of both clouds (given or estimated)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="color", target_intensity=rgbP, source_intensity=rgbQ)
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta, reciprocal=True, normal_angle=60)   # pair rejection, any metric / loss
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -62,6 +64,11 @@ COLOR_SYMBOLS = [                                          # include/s4p_icp_col
     "s4p_icp_set_source_intensity_device", "s4p_icp_estimate_color_gradients", "s4p_icp_target_color_gradients",
     "s4p_icp_color_sums", "s4p_icp_refine_color",
 ]
+REJECT_SYMBOLS = [                                         # include/s4p_icp_reject.h
+    "s4p_icp_reject_defaults", "s4p_icp_set_rejection", "s4p_icp_rejection", "s4p_icp_rejection_counts",
+]
+NORMALS_OFF, NORMALS_UNORIENTED, NORMALS_ORIENTED = 0, 1, 2         # S4P_ICP_REJECT_NORMALS_*
+WHY_KEPT, WHY_UNMATCHED, WHY_NORMALS, WHY_RECIPROCITY = 0, 1, 2, 3  # S4P_ICP_WHY_*
 
 
 class ICPError(RuntimeError):
@@ -78,6 +85,10 @@ class Params(C.Structure):
 class Robust(C.Structure):
     _fields_ = [("loss", C.c_int32), ("reserved0", C.c_int32), ("trim_fraction", C.c_double), ("scale", C.c_double),
                 ("c", C.c_double), ("reserved", C.c_double * 4)]
+
+
+class Reject(C.Structure):
+    _fields_ = [("reciprocal", C.c_int32), ("normal_mode", C.c_int32), ("normal_cos", C.c_double), ("reserved", C.c_double * 4)]
 
 
 class Result(C.Structure):
@@ -168,6 +179,14 @@ def load_library():
     L.s4p_icp_color_sums.argtypes = [vp, fp, C.c_double, dp]
     L.s4p_icp_refine_color.restype = C.c_int32
     L.s4p_icp_refine_color.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
+    L.s4p_icp_reject_defaults.restype = None
+    L.s4p_icp_reject_defaults.argtypes = [C.POINTER(Reject)]
+    L.s4p_icp_set_rejection.restype = C.c_int32
+    L.s4p_icp_set_rejection.argtypes = [vp, C.POINTER(Reject)]
+    L.s4p_icp_rejection.restype = C.c_int32
+    L.s4p_icp_rejection.argtypes = [vp, fp, ip, fp, ip]
+    L.s4p_icp_rejection_counts.restype = C.c_int32
+    L.s4p_icp_rejection_counts.argtypes = [vp, C.POINTER(C.c_int64)]
     _LIB = L
     return L
 
@@ -223,6 +242,25 @@ def robust_params(loss, trim_fraction=None, scale=None, c=None):
             r.scale = float(scale)
         if c is not None:
             r.c = float(c)
+    return r
+
+
+def reject_params(reciprocal=False, normal_angle=None, oriented=False):
+    """The s4p_icp_reject of (reciprocal, normal_angle in degrees or None, oriented): the cosine is math.cos of the angle in
+    double.  The angle must be in [0, 90] for unoriented normals and in [0, 180] for oriented ones."""
+    import math
+    r = Reject()
+    load_library().s4p_icp_reject_defaults(C.byref(r))
+    r.reciprocal = int(bool(reciprocal))
+    if normal_angle is None:
+        if oriented:
+            raise ValueError("oriented needs normal_angle")
+        return r
+    a = float(normal_angle)
+    if not (0.0 <= a <= (180.0 if oriented else 90.0)):
+        raise ValueError("normal_angle must be in [0, %d] degrees" % (180 if oriented else 90))
+    r.normal_mode = NORMALS_ORIENTED if oriented else NORMALS_UNORIENTED
+    r.normal_cos = min(1.0, max(-1.0 if oriented else 0.0, math.cos(math.radians(a))))
     return r
 
 
@@ -436,6 +474,36 @@ class ICP:
         self._chk(self.L.s4p_icp_color_sums(self.h, _fp(T), float(color_lambda), _dp(out)))
         return out
 
+    def set_rejection(self, reciprocal=False, normal_angle=None, oriented=False, normal_cos=None):
+        """The context's pair rejection (include/s4p_icp_reject.h): reciprocal keeps a pair only if the source point is the
+        nearest one of its target point too; normal_angle (degrees) keeps a pair only if the target normal and the rotated
+        source normal are at most that far apart (oriented=False: up to sign).  normal_cos gives the cosine itself instead
+        of the angle.  Everything False / None turns it off.  Every sums call and every refine honours it."""
+        if normal_cos is not None:
+            if normal_angle is not None:
+                raise ValueError("normal_angle or normal_cos, not both")
+            r = reject_params(reciprocal)
+            r.normal_mode = NORMALS_ORIENTED if oriented else NORMALS_UNORIENTED
+            r.normal_cos = float(normal_cos)
+        else:
+            r = reject_params(reciprocal, normal_angle, oriented)
+        self._chk(self.L.s4p_icp_set_rejection(self.h, C.byref(r)))
+
+    def rejection(self, T):
+        """(idx int32[n_Q], d2 float32[n_Q], why int32[n_Q]) for a float T in the centred frame under the context's
+        rejection: why 0 kept, 1 unmatched, 2 rejected by normals, 3 by reciprocity; idx -1 and d2 0 unless kept."""
+        T = self._t32(T)
+        idx = np.empty(self.n_q, np.int32); d2 = np.empty(self.n_q, np.float32); why = np.empty(self.n_q, np.int32)
+        ip = C.POINTER(C.c_int32)
+        self._chk(self.L.s4p_icp_rejection(self.h, _fp(T), idx.ctypes.data_as(ip), _fp(d2), why.ctypes.data_as(ip)))
+        return idx, d2, why
+
+    def rejection_counts(self):
+        """int64[4] of the last pass under rejection: matched one-way, rejected by normals, by reciprocity, kept."""
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.s4p_icp_rejection_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
     def correspondences(self, T):
         """(idx int32[n_Q], d2 float32[n_Q]) for a float T in the centred frame; idx -1 where nothing is within d."""
         T = self._t32(T)
@@ -509,13 +577,16 @@ class ICP:
 
 
 def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None,
-           source_normals=None, normal_k=16, target_intensity=None, source_intensity=None, color_radius=None, **params):
+           source_normals=None, normal_k=16, target_intensity=None, source_intensity=None, color_radius=None,
+           reciprocal=False, normal_angle=None, normals_oriented=False, **params):
     """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane", "gicp" and
     "color": the target normals are target_normals if given, else estimated within normal_radius (default max_distance).  metric
     "gicp": the source normals (in Q's frame as given) are source_normals if given, else the normal_k-nearest-neighbour
     normals of Q (super4pcs_amd.normals.estimate_normals).  metric "color": target_intensity and source_intensity are
     required, one value per point as (N,), or rgb in 0..255 as (N, 3), which goes through rgb_to_intensity; the gradients are
-    estimated within color_radius (default: the radius of the normals).  params go to ICP.refine, the robust ones (loss,
+    estimated within color_radius (default: the radius of the normals).  reciprocal / normal_angle (degrees) /
+    normals_oriented set the pair rejection (ICP.set_rejection) for any metric and loss; with normal_angle, a metric that does
+    not already set them gets target normals by the plane rule and source normals by the gicp rule.  params go to ICP.refine, the robust ones (loss,
     trim_fraction, loss_scale, loss_c), gicp_epsilon and color_lambda included."""
     if max_distance is None:
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
@@ -526,20 +597,24 @@ def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_no
         target_intensity, source_intensity = _as_intensity(target_intensity), _as_intensity(source_intensity)
     elif target_intensity is not None or source_intensity is not None or color_radius is not None:
         raise ValueError("target_intensity / source_intensity / color_radius need metric \"color\"")
-    if metric == "gicp" and source_normals is None:
+    rej = reject_params(reciprocal, normal_angle, normals_oriented)       # validates before any device work
+    by_normals = rej.normal_mode != NORMALS_OFF
+    if (metric == "gicp" or by_normals) and source_normals is None:
         from super4pcs_amd import normals
         source_normals = normals.estimate_normals(Q, k=normal_k)
     ctx = ICP(device)
     try:
         ctx.set_target(P, max_distance)
         ctx.set_source(Q)
-        if metric in ("plane", "gicp", "color"):
+        if metric in ("plane", "gicp", "color") or by_normals:
             if target_normals is not None:
                 ctx.set_target_normals(target_normals)
             else:
                 ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
-        if metric == "gicp":
+        if metric == "gicp" or by_normals:
             ctx.set_source_normals(source_normals)
+        if rej.reciprocal or by_normals:
+            ctx._chk(ctx.L.s4p_icp_set_rejection(ctx.h, C.byref(rej)))
         if metric == "color":
             ctx.set_target_intensity(target_intensity)
             ctx.set_source_intensity(source_intensity)

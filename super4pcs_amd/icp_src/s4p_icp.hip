@@ -18,6 +18,9 @@
 //   coloured     (include/s4p_icp_color.h) target intensities in cell order (k_gather_target_intensity), their tangent-plane
 //                gradients (k_color_gradient, k_normals' walk), source intensities in the order of the source
 //                (k_gather_source_intensity); per iteration k_search, k_color_sum (31 joint sums) + k_final_plane, host solve.
+//   rejection    (include/s4p_icp_reject.h) a state of the context: a second grid over the source (set_target's plan and
+//                build), and k_reject between k_search and the sum kernel of every split pass: it clears the slot and key of
+//                a pair that fails the normal test or the reverse search.  Off: nothing of it is launched.
 // No float or double atomics anywhere (the selection's histograms use integer atomics): every sum has a fixed order, so two calls return identical bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -35,6 +38,7 @@
 #include "s4p_icp_robust.h"
 #include "s4p_icp_gicp.h"
 #include "s4p_icp_color.h"
+#include "s4p_icp_reject.h"
 
 namespace s4p_icp {
 
@@ -638,6 +642,19 @@ __global__ __launch_bounds__(kBlock) void k_gicp_sum(GicpArgs A) {
   }
 }
 
+// correspondence rejection (include/s4p_icp_reject.h): the per-point answers of s4p_icp_rejection, from the lanes of a
+// k_search<false> + k_reject pass (the key of a surviving lane is its forward float d2) to the uploaded source order
+__global__ __launch_bounds__(kBlock) void k_reject_out(const float4* src, const float4* tgt, const uint32_t* slot, const uint32_t* key,
+                                                       const uint8_t* code, uint64_t n, int32_t* idx, float* d2, int32_t* why) {
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t o = __float_as_uint(src[j].w), sl = slot[j];
+    const bool hit = sl != kNoSlot;
+    idx[o] = hit ? int32_t(__float_as_uint(tgt[sl].w)) : -1;
+    d2[o] = hit ? __uint_as_float(key[j]) : 0.f;
+    why[o] = int32_t(code[j]);
+  }
+}
+
 // coloured ICP (include/s4p_icp_color.h).  Once per target: the intensities in cell order (k_gather_target_intensity) and
 // the intensity gradient of every target point in its tangent plane (k_color_gradient).  Per iteration: k_search<false>,
 // k_color_sum (the 31 joint sums streamed from the slots, k_match_plane's reduction) and k_final_plane.  Defined before
@@ -847,7 +864,82 @@ __global__ __launch_bounds__(kBlock) void k_search(SearchArgs A) {
   }
 }
 
+// correspondence rejection (include/s4p_icp_reject.h), between k_search and the sum kernel of a split pass
+struct RejectArgs {
+  Tf T;                     // the pass's T: its linear part rotates the source normals
+  Tf Ti;                    // the reverse map T- (host)
+  GridDev g;                // the target grid
+  GridDev gs;               // the source grid: tgt = Q' in cell order, w = the uploaded source index
+  const float4* src;
+  const float4* snrm;       // source normals, the order of src
+  const float4* nrm;        // target normals, cell order, as g.tgt
+  uint64_t n;
+  float d2max;
+  int32_t oriented;         // normal test: c >= ncos (else |c| >= ncos)
+  double ncos;
+  uint32_t* slot;           // k_search's; a rejected lane gets kNoSlot / kNoKey
+  uint32_t* key;
+  uint8_t* code;            // optional: S4P_ICP_WHY_* per visited lane
+  unsigned long long* counts;   // matched, by normals, by reciprocity, kept
+};
+
+// One lane per visited source lane, in src's order (the order of the T0-image cells: neighbouring lanes search
+// neighbouring source cells backwards).  The normal test first; a pair that fails it is not searched backwards.  Every
+// lane of a wave runs the same number of rounds, so each ballot sees the whole wave: the four counters are wave-uniform
+// integers, added once per wave at the end (integer atomics only).
+template <bool RECIP, bool NORMAL>
+__global__ __launch_bounds__(kBlock) void k_reject(RejectArgs A) {
+  uint32_t c_matched = 0, c_normal = 0, c_recip = 0, c_kept = 0;
+  for (uint64_t base = blockIdx.x * (uint64_t)kBlock; base < A.n; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t j = base + threadIdx.x;
+    const bool in = j < A.n;
+    const uint32_t sl = in ? A.slot[j] : kNoSlot;
+    const bool matched = sl != kNoSlot;
+    bool by_normal = false, by_recip = false;
+    if (NORMAL && matched) {
+      const float4 nf = A.nrm[sl], mf = A.snrm[j];
+      const bool info = !(nf.x == 0.f && nf.y == 0.f && nf.z == 0.f) && !(mf.x == 0.f && mf.y == 0.f && mf.z == 0.f);
+      if (info) {
+        const double mq[3] = {double(mf.x), double(mf.y), double(mf.z)};
+        double nh[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) nh[a] = (double(A.T.m[4 * a]) * mq[0] + double(A.T.m[4 * a + 1]) * mq[1]) + double(A.T.m[4 * a + 2]) * mq[2];
+        const double c = (double(nf.x) * nh[0] + double(nf.y) * nh[1]) + double(nf.z) * nh[2];
+        by_normal = !((A.oriented ? c : fabs(c)) >= A.ncos);
+      }
+    }
+    if (RECIP && matched && !by_normal) {
+      const float4 p = A.g.tgt[sl];
+      float x, y, z;
+      apply_t(A.Ti, p.x, p.y, p.z, x, y, z);
+      float best;
+      uint32_t bi;
+      float4 bq;
+      nearest(A.gs, x, y, z, A.d2max, best, bi, bq);
+      by_recip = bi != __float_as_uint(A.src[j].w);
+    }
+    const bool rejected = by_normal || by_recip;
+    if (rejected) { A.slot[j] = kNoSlot; A.key[j] = kNoKey; }
+    if (A.code && in)
+      A.code[j] = uint8_t(!matched ? S4P_ICP_WHY_UNMATCHED
+                                   : (by_normal ? S4P_ICP_WHY_NORMALS : (by_recip ? S4P_ICP_WHY_RECIPROCITY : S4P_ICP_WHY_KEPT)));
+    c_matched += uint32_t(__popcll(__ballot(matched)));
+    c_normal += uint32_t(__popcll(__ballot(by_normal)));
+    c_recip += uint32_t(__popcll(__ballot(by_recip)));
+    c_kept += uint32_t(__popcll(__ballot(matched && !rejected)));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (c_matched) atomicAdd(&A.counts[0], (unsigned long long)c_matched);
+    if (c_normal) atomicAdd(&A.counts[1], (unsigned long long)c_normal);
+    if (c_recip) atomicAdd(&A.counts[2], (unsigned long long)c_recip);
+    if (c_kept) atomicAdd(&A.counts[3], (unsigned long long)c_kept);
+  }
+}
+
+constexpr int32_t kLossOnes = 0;            // every weight 1: the plain point / plane sums under rejection
+
 __device__ inline double robust_weight(int loss, float u, uint32_t thr, double cs, double cs2) {
+  if (loss == kLossOnes) return 1.0;
   if (loss == S4P_ICP_LOSS_TRIMMED) return __float_as_uint(u) <= thr ? 1.0 : 0.0;
   const double ud = double(u);
   if (loss == S4P_ICP_LOSS_HUBER) return ud <= cs2 ? 1.0 : cs / sqrt(ud);
@@ -1088,6 +1180,16 @@ struct s4p_icp_ctx {
   float* si = nullptr;               // source intensities, uploaded order
   float* sint = nullptr;             // the same in the order of the pass's source
   bool has_sint = false;
+  // correspondence rejection (include/s4p_icp_reject.h)
+  s4p_icp_reject rej{};              // validated; everything off by default
+  bool rej_on = false;
+  GridDev gs{};                      // the source grid (reverse search), built when a pass first needs it
+  float4* sgrid = nullptr;           // Q' in its cell order, w = the uploaded source index
+  uint32_t* sstart = nullptr;
+  bool sgrid_valid = false;
+  unsigned long long* rcnt = nullptr;    // the four counters of a pass
+  unsigned long long* rhcnt = nullptr;   // pinned
+  int64_t rej_counts[4] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -1138,53 +1240,30 @@ int32_t sort_pairs(s4p_icp_ctx* h, Scratch& S, const uint32_t* keys, uint32_t* k
   return S4P_ICP_OK;
 }
 
-int32_t set_target_impl(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n, float d, hipMemcpyKind kind) {
-  if (!h) return S4P_ICP_ERR_BAD_ARG;
-  if (!x || !y || !z || n < 1) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: empty or null cloud");
-  if (n >= int64_t(0x7FFFFFFF)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: more than 2^31 - 1 points");
-  if (!(d > 0.f) || !std::isfinite(d)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: max_distance must be finite and > 0");
-  ICP_HIP(hipSetDevice(h->device));
-  h->has_target = false;
-  h->has_normals = false;
-  dfree(h->nrm); h->nrm = nullptr;
-  h->has_tint = h->has_grad = false;
-  dfree(h->tint); dfree(h->grad); h->tint = nullptr; h->grad = nullptr;
-  dfree(h->tgt); h->tgt = nullptr;
-  dfree(h->start); h->start = nullptr;
-  Scratch S;
-  const uint64_t un = uint64_t(n);
-  float* p[3];
-  const float* in[3] = {x, y, z};
-  for (int a = 0; a < 3; ++a) {
-    ICP_HIP(S.alloc((void**)&p[a], un * sizeof(float)));
-    ICP_HIP(hipMemcpyAsync(p[a], in[a], un * sizeof(float), kind, h->st));
-  }
-  // frame and bounds
+// coordinate sums and float bounds of a cloud on the device: k_stats' per-block partials, combined on the host in row order
+int32_t cloud_stats(s4p_icp_ctx* h, Scratch& S, float* const p[3], int64_t n, double sum[3], float lo[3], float hi[3]) {
   const int nb = blocks_for(n);
   double* rows = nullptr;
   ICP_HIP(S.alloc((void**)&rows, size_t(nb) * kStatsPitch * sizeof(double)));
-  hipLaunchKernelGGL(k_stats, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, rows);
+  hipLaunchKernelGGL(k_stats, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], uint64_t(n), rows);
   ICP_HIP(hipGetLastError());
   std::vector<double> hr(size_t(nb) * kStatsPitch);
   ICP_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(double), hipMemcpyDeviceToHost, h->st));
   ICP_HIP(hipStreamSynchronize(h->st));
-  double sum[3] = {0.0, 0.0, 0.0};
-  float lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) { lo[a] = float(hr[3 + a]); hi[a] = float(hr[6 + a]); }
+  for (int a = 0; a < 3; ++a) { sum[a] = 0.0; lo[a] = float(hr[3 + a]); hi[a] = float(hr[6 + a]); }
   for (int b = 0; b < nb; ++b)
     for (int a = 0; a < 3; ++a) {
       sum[a] += hr[size_t(b) * kStatsPitch + a];
       lo[a] = std::min(lo[a], float(hr[size_t(b) * kStatsPitch + 3 + a]));
       hi[a] = std::max(hi[a], float(hr[size_t(b) * kStatsPitch + 6 + a]));
     }
-  for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: non-finite coordinates");
-    h->c[a] = float(sum[a] / double(n));
-  }
-  // bounds of P' = fl(P - c): rounding is monotone, so they are fl(lo - c), fl(hi - c)
-  float plo[3], phi[3];
-  for (int a = 0; a < 3; ++a) { plo[a] = lo[a] - h->c[a]; phi[a] = hi[a] - h->c[a]; }
-  // grid plan: cell edge 1.02 d, enlarged x 1.25 until the dense grid fits the cell cap (cf. LcpGridHost::plan)
+  return S4P_ICP_OK;
+}
+
+// grid plan over the centred bounds [plo, phi] of n points: cell edge 1.02 d, enlarged x 1.25 until the dense grid fits the
+// cell cap (cf. LcpGridHost::plan)
+int32_t plan_grid(s4p_icp_ctx* h, const float plo[3], const float phi[3], uint64_t un, float d, GridDev* g, uint64_t* ncell,
+                  const char* who) {
   const uint64_t cap = std::min<uint64_t>(kMaxCells, std::max<uint64_t>(1ull << 20, 2 * un));
   double hh = double(d) * double(kCellFactor);
   int dims[3];
@@ -1199,33 +1278,105 @@ int32_t set_target_impl(s4p_icp_ctx* h, const float* x, const float* y, const fl
       nc *= uint64_t(dims[a]);
       if (nc > cap) { ok = false; break; }
     }
-    if (ok) { h->g.h = hh; h->g.inv_h = inv; h->ncell = nc; break; }
-    if (guard > 400) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: no grid fits the cloud's extent");
+    if (ok) { g->h = hh; g->inv_h = inv; *ncell = nc; break; }
+    if (guard > 400) return fail(h, S4P_ICP_ERR_BAD_ARG, std::string(who) + ": no grid fits the cloud's extent");
     hh *= 1.25;
   }
-  h->g.ox = plo[0]; h->g.oy = plo[1]; h->g.oz = plo[2];
-  h->g.nx = dims[0]; h->g.ny = dims[1]; h->g.nz = dims[2];
-  h->d = d;
-  h->d2max = d * d;
-  // cell-ordered target
+  g->ox = plo[0]; g->oy = plo[1]; g->oz = plo[2];
+  g->nx = dims[0]; g->ny = dims[1]; g->nz = dims[2];
+  return S4P_ICP_OK;
+}
+
+// the cell-ordered cloud fl(p - c) (w = the index) and the start of every cell of the planned grid g; *pts and *start are
+// allocated here and entered into g
+int32_t build_grid(s4p_icp_ctx* h, Scratch& S, float* const p[3], uint64_t un, const float c[3], GridDev* g, uint64_t ncell, float4** pts,
+                   uint32_t** start) {
+  const int nb = blocks_for(int64_t(un));
   uint32_t *keys, *vals, *keys2, *vals2;
   ICP_HIP(S.alloc((void**)&keys, un * 4)); ICP_HIP(S.alloc((void**)&vals, un * 4));
   ICP_HIP(S.alloc((void**)&keys2, un * 4)); ICP_HIP(S.alloc((void**)&vals2, un * 4));
-  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, h->c[0], h->c[1], h->c[2], h->g, keys, vals);
+  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, c[0], c[1], c[2], *g, keys, vals);
   ICP_HIP(hipGetLastError());
-  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell - 1)) return rc;
-  ICP_HIP(hipMalloc((void**)&h->start, (h->ncell + 1) * sizeof(uint32_t)));
-  ICP_HIP(hipMalloc((void**)&h->tgt, un * sizeof(float4)));
-  hipLaunchKernelGGL(k_cell_starts, dim3(blocks_for(int64_t(h->ncell) + 1)), dim3(kBlock), 0, h->st, keys2, un, h->ncell, h->start);
+  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, ncell - 1)) return rc;
+  ICP_HIP(hipMalloc((void**)start, (ncell + 1) * sizeof(uint32_t)));
+  ICP_HIP(hipMalloc((void**)pts, un * sizeof(float4)));
+  hipLaunchKernelGGL(k_cell_starts, dim3(blocks_for(int64_t(ncell) + 1)), dim3(kBlock), 0, h->st, keys2, un, ncell, *start);
   ICP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_gather_target, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, h->c[0], h->c[1], h->c[2], vals2, h->tgt);
+  hipLaunchKernelGGL(k_gather_target, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], un, c[0], c[1], c[2], vals2, *pts);
   ICP_HIP(hipGetLastError());
   ICP_HIP(hipStreamSynchronize(h->st));          // the scratch is freed on return
-  h->g.tgt = h->tgt;
-  h->g.start = h->start;
+  g->tgt = *pts;
+  g->start = *start;
+  return S4P_ICP_OK;
+}
+
+void drop_source_grid(s4p_icp_ctx* h) {
+  h->sgrid_valid = false;
+  dfree(h->sgrid); dfree(h->sstart);
+  h->sgrid = nullptr; h->sstart = nullptr;
+}
+
+int32_t set_target_impl(s4p_icp_ctx* h, const float* x, const float* y, const float* z, int64_t n, float d, hipMemcpyKind kind) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!x || !y || !z || n < 1) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: empty or null cloud");
+  if (n >= int64_t(0x7FFFFFFF)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: more than 2^31 - 1 points");
+  if (!(d > 0.f) || !std::isfinite(d)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: max_distance must be finite and > 0");
+  ICP_HIP(hipSetDevice(h->device));
+  h->has_target = false;
+  h->has_normals = false;
+  dfree(h->nrm); h->nrm = nullptr;
+  h->has_tint = h->has_grad = false;
+  dfree(h->tint); dfree(h->grad); h->tint = nullptr; h->grad = nullptr;
+  dfree(h->tgt); h->tgt = nullptr;
+  dfree(h->start); h->start = nullptr;
+  drop_source_grid(h);                            // the frame and d are the target's
+  Scratch S;
+  const uint64_t un = uint64_t(n);
+  float* p[3];
+  const float* in[3] = {x, y, z};
+  for (int a = 0; a < 3; ++a) {
+    ICP_HIP(S.alloc((void**)&p[a], un * sizeof(float)));
+    ICP_HIP(hipMemcpyAsync(p[a], in[a], un * sizeof(float), kind, h->st));
+  }
+  // frame and bounds
+  double sum[3];
+  float lo[3], hi[3];
+  if (int32_t rc = cloud_stats(h, S, p, n, sum, lo, hi)) return rc;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_target: non-finite coordinates");
+    h->c[a] = float(sum[a] / double(n));
+  }
+  // bounds of P' = fl(P - c): rounding is monotone, so they are fl(lo - c), fl(hi - c)
+  float plo[3], phi[3];
+  for (int a = 0; a < 3; ++a) { plo[a] = lo[a] - h->c[a]; phi[a] = hi[a] - h->c[a]; }
+  if (int32_t rc = plan_grid(h, plo, phi, un, d, &h->g, &h->ncell, "set_target")) return rc;
+  h->d = d;
+  h->d2max = d * d;
+  if (int32_t rc = build_grid(h, S, p, un, h->c, &h->g, h->ncell, &h->tgt, &h->start)) return rc;
   h->n_p = n;
   h->has_target = true;
   h->src_dirty = true;                          // Q' depends on c
+  return S4P_ICP_OK;
+}
+
+// The source grid of the reverse search (include/s4p_icp_reject.h): set_target's plan and build over Q' = fl(Q - c) in the
+// uploaded order, from the coordinates as uploaded.  Built once; set_source and set_target drop it.
+int32_t source_grid_ready(s4p_icp_ctx* h) {
+  if (h->sgrid_valid) return S4P_ICP_OK;
+  drop_source_grid(h);
+  Scratch S;
+  double sum[3];
+  float lo[3], hi[3];
+  if (int32_t rc = cloud_stats(h, S, h->qraw, h->n_q, sum, lo, hi)) return rc;
+  float plo[3], phi[3];
+  for (int a = 0; a < 3; ++a) {
+    plo[a] = lo[a] - h->c[a]; phi[a] = hi[a] - h->c[a];
+    if (!std::isfinite(plo[a]) || !std::isfinite(phi[a])) return fail(h, S4P_ICP_ERR_BAD_ARG, "rejection: non-finite source coordinates");
+  }
+  uint64_t ncell = 0;
+  if (int32_t rc = plan_grid(h, plo, phi, uint64_t(h->n_q), h->d, &h->gs, &ncell, "rejection")) return rc;
+  if (int32_t rc = build_grid(h, S, h->qraw, uint64_t(h->n_q), h->c, &h->gs, ncell, &h->sgrid, &h->sstart)) return rc;
+  h->sgrid_valid = true;
   return S4P_ICP_OK;
 }
 
@@ -1237,6 +1388,7 @@ int32_t set_source_impl(s4p_icp_ctx* h, const float* x, const float* y, const fl
   h->has_source = false;
   h->has_src_normals = false;
   h->has_sint = false;
+  drop_source_grid(h);
   if (n != h->n_q) {
     for (int a = 0; a < 3; ++a) { dfree(h->qraw[a]); h->qraw[a] = nullptr; }
     dfree(h->src); dfree(h->src_ord); h->src = h->src_ord = nullptr;
@@ -1300,6 +1452,39 @@ int32_t robust_cfg(s4p_icp_ctx* h, int32_t metric, const s4p_icp_robust* R, Robu
   return S4P_ICP_OK;
 }
 
+// T- of include/s4p_icp_reject.h: the transposed float entries and t-_a = float(-((m_0a t_0 + m_1a t_1) + m_2a t_2)) in double
+Tf reverse_map(const Tf& T) {
+  Tf R;
+  for (int a = 0; a < 3; ++a) {
+    for (int b = 0; b < 3; ++b) R.m[4 * a + b] = T.m[4 * b + a];
+    R.m[4 * a + 3] = float(-((double(T.m[a]) * double(T.m[3]) + double(T.m[4 + a]) * double(T.m[7])) + double(T.m[8 + a]) * double(T.m[11])));
+  }
+  return R;
+}
+
+// k_reject on the slots and keys k_search has just written for (T, src), after reject_prepare for this src; the counters
+// follow the pass's sums to the host (reject_done after the pass's synchronisation).  code: optional, per visited lane.
+int32_t launch_reject(s4p_icp_ctx* h, const Tf& T, const float4* src, uint8_t* code) {
+  ICP_HIP(hipMemsetAsync(h->rcnt, 0, 4 * sizeof(unsigned long long), h->st));
+  RejectArgs A;
+  A.T = T; A.Ti = reverse_map(T); A.g = h->g; A.gs = h->gs; A.src = src; A.snrm = h->snrm; A.nrm = h->nrm; A.n = uint64_t(h->n_q);
+  A.d2max = h->d2max; A.oriented = h->rej.normal_mode == S4P_ICP_REJECT_NORMALS_ORIENTED; A.ncos = h->rej.normal_cos;
+  A.slot = h->rslot; A.key = h->rkey; A.code = code; A.counts = h->rcnt;
+  const int nb = blocks_for(h->n_q);
+  const bool rc = h->rej.reciprocal != 0, nm = h->rej.normal_mode != S4P_ICP_REJECT_NORMALS_OFF;
+  if (rc && nm) hipLaunchKernelGGL((k_reject<true, true>), dim3(nb), dim3(kBlock), 0, h->st, A);
+  else if (rc) hipLaunchKernelGGL((k_reject<true, false>), dim3(nb), dim3(kBlock), 0, h->st, A);
+  else if (nm) hipLaunchKernelGGL((k_reject<false, true>), dim3(nb), dim3(kBlock), 0, h->st, A);
+  else hipLaunchKernelGGL((k_reject<false, false>), dim3(nb), dim3(kBlock), 0, h->st, A);      // s4p_icp_rejection with everything off
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(h->rhcnt, h->rcnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->st));
+  return S4P_ICP_OK;
+}
+
+void reject_done(s4p_icp_ctx* h) {
+  for (int k = 0; k < 4; ++k) h->rej_counts[k] = int64_t(h->rhcnt[k]);
+}
+
 // One robust pass over `src` for T: one search, the selection, the weighted sums; sums and info on the host.
 int32_t robust_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, bool plane, const RobustCfg& C, double* sums, double* info) {
   const uint64_t un = uint64_t(h->n_q);
@@ -1324,6 +1509,7 @@ int32_t robust_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, bool plane, 
   if (plane) hipLaunchKernelGGL(k_search<true>, dim3(nb), dim3(kBlock), 0, h->st, S);
   else hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, S);
   ICP_HIP(hipGetLastError());
+  if (h->rej_on) if (int32_t rc = launch_reject(h, T, src, nullptr)) return rc;
   const int passes = C.mode == kSelNone ? 1 : kDigits;         // without a selection, pass 0 still counts M
   for (int p = 0; p < passes; ++p) {
     hipLaunchKernelGGL(k_key_hist, dim3(nb), dim3(kBlock), 0, h->st, (const uint32_t*)h->rkey, un, p, (const SelState*)h->rst,
@@ -1353,7 +1539,17 @@ int32_t robust_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, bool plane, 
   std::memcpy(sums, h->rhsum, ns * sizeof(double));
   for (int k = 0; k < S4P_ICP_ROBUST_NINFO; ++k) info[k] = k < 5 ? h->rhsum[ns + k] : 0.0;
   info[5] = sums[0];
+  if (h->rej_on) reject_done(h);
   return S4P_ICP_OK;
+}
+
+// The plain point / plane sums under rejection: search, k_reject, and the weighted sums with every weight 1
+// (s4p_icp_sums' / s4p_icp_plane_sums' bits on the surviving pairs, as include/s4p_icp_robust.h states).
+int32_t ones_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, bool plane, double* sums) {
+  RobustCfg C;
+  C.loss = kLossOnes;
+  double info[S4P_ICP_ROBUST_NINFO];
+  return robust_pass(h, T, src, plane, C, sums, info);
 }
 
 // one correspondence pass over `src` for T: the 17 sums (and, if idx, the per-point answers) on the host
@@ -1476,6 +1672,26 @@ int32_t split_buffers(s4p_icp_ctx* h) {
   return S4P_ICP_OK;
 }
 
+// Before the passes of a stage call or a refine over `src` with the rejection on (always: s4p_icp_rejection): the split
+// buffers, the counters, the source grid (reciprocity) and the source normals in src's order (normal test, gicp_prepare's
+// gather).  Nothing of a rejection is built or allocated inside the iteration loop.
+int32_t reject_prepare(s4p_icp_ctx* h, const float4* src, bool always = false) {
+  if (!h->rej_on && !always) return S4P_ICP_OK;
+  const bool nm = h->rej.normal_mode != S4P_ICP_REJECT_NORMALS_OFF;
+  if (nm && !h->has_normals) return fail(h, S4P_ICP_ERR_STATE, "rejection by normals: target normals first (set_target_normals or estimate_normals)");
+  if (nm && !h->has_src_normals) return fail(h, S4P_ICP_ERR_STATE, "rejection by normals: source normals first (set_source_normals)");
+  if (int32_t rc = split_buffers(h)) return rc;
+  if (!h->rcnt) ICP_HIP(hipMalloc((void**)&h->rcnt, 4 * sizeof(unsigned long long)));
+  if (!h->rhcnt) ICP_HIP(hipHostMalloc((void**)&h->rhcnt, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+  if (h->rej.reciprocal) if (int32_t rc = source_grid_ready(h)) return rc;
+  if (nm) {
+    hipLaunchKernelGGL(k_gather_source_normals, dim3(blocks_for(h->n_q)), dim3(kBlock), 0, h->st, (const float*)h->sn[0],
+                       (const float*)h->sn[1], (const float*)h->sn[2], src, uint64_t(h->n_q), h->snrm);
+    ICP_HIP(hipGetLastError());
+  }
+  return S4P_ICP_OK;
+}
+
 // the buffers of a generalized pass and the source normals in src's order
 int32_t gicp_prepare(s4p_icp_ctx* h, const float4* src) {
   if (int32_t rc = split_buffers(h)) return rc;
@@ -1493,6 +1709,7 @@ int32_t gicp_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double epsilon
   S.T = T; S.g = h->g; S.src = src; S.nrm = h->nrm; S.n = uint64_t(h->n_q); S.d2max = h->d2max; S.slot = h->rslot; S.key = h->rkey;
   hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, S);
   ICP_HIP(hipGetLastError());
+  if (h->rej_on) if (int32_t rc = launch_reject(h, T, src, nullptr)) return rc;
   GicpArgs A;
   A.T = T; A.g = h->g; A.src = src; A.snrm = h->snrm; A.nrm = h->nrm; A.n = uint64_t(h->n_q); A.slot = h->rslot;
   A.k = 1.0 - epsilon; A.slab = h->pslab;
@@ -1504,6 +1721,7 @@ int32_t gicp_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double epsilon
   ICP_HIP(hipEventRecord(h->ev, h->st));
   ICP_HIP(hipEventSynchronize(h->ev));
   std::memcpy(out, h->hsum, S4P_ICP_GICP_NSUMS * sizeof(double));
+  if (h->rej_on) reject_done(h);
   return S4P_ICP_OK;
 }
 
@@ -1575,6 +1793,7 @@ int32_t color_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double lambda
   S.T = T; S.g = h->g; S.src = src; S.nrm = h->nrm; S.n = uint64_t(h->n_q); S.d2max = h->d2max; S.slot = h->rslot; S.key = h->rkey;
   hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, S);
   ICP_HIP(hipGetLastError());
+  if (h->rej_on) if (int32_t rc = launch_reject(h, T, src, nullptr)) return rc;
   ColorArgs A;
   A.T = T; A.g = h->g; A.src = src; A.sint = h->sint; A.nrm = h->nrm; A.grad = h->grad; A.n = uint64_t(h->n_q); A.slot = h->rslot;
   A.wg = lambda; A.wc = 1.0 - lambda; A.slab = h->pslab;
@@ -1586,6 +1805,7 @@ int32_t color_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double lambda
   ICP_HIP(hipEventRecord(h->ev, h->st));
   ICP_HIP(hipEventSynchronize(h->ev));
   std::memcpy(out, h->hsum, S4P_ICP_COLOR_NSUMS * sizeof(double));
+  if (h->rej_on) reject_done(h);
   return S4P_ICP_OK;
 }
 
@@ -1643,6 +1863,7 @@ int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_in
   auto run_pass = [&](const float4* src) {
     if (gicp) return gicp_pass(h, to_float(T), src, epsilon, sums);
     if (color) return color_pass(h, to_float(T), src, epsilon, sums);
+    if (h->rej_on) return ones_pass(h, to_float(T), src, plane, sums);       // off: the fused k_match / k_match_plane, untouched
     return plane ? plane_pass(h, to_float(T), src, sums) : pass(h, to_float(T), src, nullptr, nullptr, sums);
   };
   to_centred(T16_inout, h->c, T);
@@ -1650,6 +1871,7 @@ int32_t refine_impl(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_in
   if (int32_t rc = source_for(h, P, T, &src)) return rc;
   if (gicp) if (int32_t rc = gicp_prepare(h, src)) return rc;      // the normals follow the source's order
   if (color) if (int32_t rc = color_prepare(h, src)) return rc;    // and so do the intensities
+  if (int32_t rc = reject_prepare(h, src)) return rc;
   double prev = 0.0;
   R.status = S4P_ICP_MAX_ITERATIONS;
   for (int k = 0; k < P.max_iterations; ++k) {
@@ -1701,6 +1923,7 @@ int32_t refine_robust_impl(s4p_icp_ctx* h, const s4p_icp_params* params, int32_t
   to_centred(T16_inout, h->c, T);
   const float4* src = nullptr;
   if (int32_t rc = source_for(h, P, T, &src)) return rc;
+  if (int32_t rc = reject_prepare(h, src)) return rc;
   double prev = 0.0;
   R.status = S4P_ICP_MAX_ITERATIONS;
   for (int k = 0; k < P.max_iterations; ++k) {
@@ -1786,6 +2009,8 @@ void s4p_icp_destroy(s4p_icp_ctx* h) {
   for (int a = 0; a < 3; ++a) dfree(h->sn[a]);
   dfree(h->snrm);
   dfree(h->tint); dfree(h->grad); dfree(h->si); dfree(h->sint);
+  dfree(h->sgrid); dfree(h->sstart); dfree(h->rcnt);
+  if (h->rhcnt) (void)hipHostFree(h->rhcnt);
   if (h->rhsum) (void)hipHostFree(h->rhsum);
   if (h->hsum) (void)hipHostFree(h->hsum);
   if (h->ev) (void)hipEventDestroy(h->ev);
@@ -1833,6 +2058,10 @@ int32_t s4p_icp_sums(s4p_icp_ctx* h, const float* T16_centred, double* sums) {
   if (!h) return S4P_ICP_ERR_BAD_ARG;
   if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "sums: null argument");
   if (int32_t rc = ready(h)) return rc;
+  if (h->rej_on) {
+    if (int32_t rc = reject_prepare(h, h->src)) return rc;
+    return ones_pass(h, centred_from_float16(T16_centred), h->src, false, sums);
+  }
   return pass(h, centred_from_float16(T16_centred), h->src, nullptr, nullptr, sums);
 }
 
@@ -1956,6 +2185,10 @@ int32_t s4p_icp_plane_sums(s4p_icp_ctx* h, const float* T16_centred, double* sum
   if (!h) return S4P_ICP_ERR_BAD_ARG;
   if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "plane_sums: null argument");
   if (int32_t rc = plane_ready(h)) return rc;
+  if (h->rej_on) {
+    if (int32_t rc = reject_prepare(h, h->src)) return rc;
+    return ones_pass(h, centred_from_float16(T16_centred), h->src, true, sums);
+  }
   return plane_pass(h, centred_from_float16(T16_centred), h->src, sums);
 }
 
@@ -2046,6 +2279,7 @@ int32_t s4p_icp_robust_sums(s4p_icp_ctx* h, const float* T16_centred, int32_t me
   RobustCfg C;
   if (int32_t rc = robust_cfg(h, metric, robust, &C)) return rc;
   double inf[S4P_ICP_ROBUST_NINFO];
+  if (int32_t rc = reject_prepare(h, h->src)) return rc;
   if (int32_t rc = robust_pass(h, centred_from_float16(T16_centred), h->src, plane, C, sums, inf)) return rc;
   if (info) std::memcpy(info, inf, sizeof(inf));
   return S4P_ICP_OK;
@@ -2098,6 +2332,7 @@ int32_t s4p_icp_gicp_sums(s4p_icp_ctx* h, const float* T16_centred, double epsil
   if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "gicp_sums: null argument");
   if (int32_t rc = gicp_ready(h, epsilon)) return rc;
   if (int32_t rc = gicp_prepare(h, h->src)) return rc;
+  if (int32_t rc = reject_prepare(h, h->src)) return rc;
   return gicp_pass(h, centred_from_float16(T16_centred), h->src, epsilon, sums);
 }
 
@@ -2188,11 +2423,78 @@ int32_t s4p_icp_color_sums(s4p_icp_ctx* h, const float* T16_centred, double lamb
   if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "color_sums: null argument");
   if (int32_t rc = color_ready(h, lambda)) return rc;
   if (int32_t rc = color_prepare(h, h->src)) return rc;
+  if (int32_t rc = reject_prepare(h, h->src)) return rc;
   return color_pass(h, centred_from_float16(T16_centred), h->src, lambda, sums);
 }
 
 int32_t s4p_icp_refine_color(s4p_icp_ctx* h, const s4p_icp_params* params, double lambda, double* T16_inout, s4p_icp_result* result) {
   return refine_impl(h, params, T16_inout, result, kRefineColor, lambda);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// correspondence rejection (include/s4p_icp_reject.h)
+
+void s4p_icp_reject_defaults(s4p_icp_reject* r) {
+  if (r) std::memset(r, 0, sizeof(*r));
+}
+
+int32_t s4p_icp_set_rejection(s4p_icp_ctx* h, const s4p_icp_reject* r) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  s4p_icp_reject R;
+  s4p_icp_reject_defaults(&R);
+  if (r) {
+    if (r->reciprocal != 0 && r->reciprocal != 1) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_rejection: reciprocal must be 0 or 1");
+    R.reciprocal = r->reciprocal;
+    R.normal_mode = r->normal_mode;
+    if (r->normal_mode == S4P_ICP_REJECT_NORMALS_UNORIENTED) {
+      if (!(r->normal_cos >= 0.0 && r->normal_cos <= 1.0)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_rejection: normal_cos must be in [0, 1] (unoriented)");
+      R.normal_cos = r->normal_cos;
+    } else if (r->normal_mode == S4P_ICP_REJECT_NORMALS_ORIENTED) {
+      if (!(r->normal_cos >= -1.0 && r->normal_cos <= 1.0)) return fail(h, S4P_ICP_ERR_BAD_ARG, "set_rejection: normal_cos must be in [-1, 1] (oriented)");
+      R.normal_cos = r->normal_cos;
+    } else if (r->normal_mode != S4P_ICP_REJECT_NORMALS_OFF) {
+      return fail(h, S4P_ICP_ERR_BAD_ARG, "set_rejection: unknown normal_mode");
+    }
+  }
+  h->rej = R;
+  h->rej_on = R.reciprocal != 0 || R.normal_mode != S4P_ICP_REJECT_NORMALS_OFF;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_rejection(s4p_icp_ctx* h, const float* T16_centred, int32_t* idx, float* d2, int32_t* why) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !idx || !d2 || !why) return fail(h, S4P_ICP_ERR_BAD_ARG, "rejection: null argument");
+  if (int32_t rc = ready(h)) return rc;
+  if (int32_t rc = reject_prepare(h, h->src, true)) return rc;
+  Scratch S;
+  const uint64_t un = uint64_t(h->n_q);
+  int32_t *di, *dw;
+  float* dd;
+  uint8_t* code;
+  ICP_HIP(S.alloc((void**)&di, un * 4)); ICP_HIP(S.alloc((void**)&dd, un * 4)); ICP_HIP(S.alloc((void**)&dw, un * 4));
+  ICP_HIP(S.alloc((void**)&code, un));
+  const Tf T = centred_from_float16(T16_centred);
+  const int nb = blocks_for(h->n_q);
+  SearchArgs A;
+  A.T = T; A.g = h->g; A.src = h->src; A.nrm = h->nrm; A.n = un; A.d2max = h->d2max; A.slot = h->rslot; A.key = h->rkey;
+  hipLaunchKernelGGL(k_search<false>, dim3(nb), dim3(kBlock), 0, h->st, A);
+  ICP_HIP(hipGetLastError());
+  if (int32_t rc = launch_reject(h, T, h->src, code)) return rc;
+  hipLaunchKernelGGL(k_reject_out, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->src, (const float4*)h->tgt, (const uint32_t*)h->rslot,
+                     (const uint32_t*)h->rkey, (const uint8_t*)code, un, di, dd, dw);
+  ICP_HIP(hipGetLastError());
+  ICP_HIP(hipMemcpyAsync(idx, di, un * 4, hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipMemcpyAsync(d2, dd, un * 4, hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipMemcpyAsync(why, dw, un * 4, hipMemcpyDeviceToHost, h->st));
+  ICP_HIP(hipStreamSynchronize(h->st));
+  reject_done(h);
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_rejection_counts(const s4p_icp_ctx* h, int64_t counts[4]) {
+  if (!h || !counts) return S4P_ICP_ERR_BAD_ARG;
+  for (int k = 0; k < 4; ++k) counts[k] = h->rej_counts[k];
+  return S4P_ICP_OK;
 }
 
 }  // extern "C"
