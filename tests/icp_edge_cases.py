@@ -13,7 +13,7 @@ import numpy as np
 
 F = np.float32
 Case = namedtuple("Case", "name P Q d T0 origin", defaults=(np.zeros(3),))
-K_BLOCK, K_MAX_BLOCKS = 256, 2048               # s4p_icp.hip's launch geometry (blocks_for)
+K_BLOCK, K_MAX_BLOCKS = 256, 2048               # icp_src/s4p_icp_k_common.hip.hpp's launch geometry (blocks_for)
 RAGGED_N = (1, 63, 64, 65, 255, 256, 257)
 FULL_LAUNCH_N = (524_288, 524_289)              # 2048 x 256: the last single-trip size and the first two-trip one
 

@@ -1,4 +1,4 @@
-// Literal CPU restatement of k_normals of libsuper4pcs_icp.so (super4pcs_amd/icp_src/s4p_icp.hip), for bit-for-bit
+// Literal CPU restatement of k_normals of libsuper4pcs_icp.so (super4pcs_amd/icp_src/s4p_icp_k_build.hip.hpp), for bit-for-bit
 // comparison of the estimated target normals: set_target's grid plan in the same double arithmetic, the target in cell
 // order (cells ascending, original index ascending inside a cell: the device's radix sort is stable), the 27 cells around a
 // point visited in k_normals' order with the neighbours of a cell in cell order, so that every double sum adds the same
