@@ -9,7 +9,7 @@
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
 //             [--remove-outliers k] [--remove-outliers-std ratio]
-//             [--voxel-size v] [--icp-scales v1,v2,...]
+//             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -31,6 +31,11 @@
 // --icp-scales v1,v2,... (needs --icp) refines coarse to fine (algorithms/icp_multiscale.h): one level per voxel size, both
 // inputs downsampled at it (the second in its own frame; 0, allowed last, takes them as they are), the level's distance
 // max(--icp-dist, 3 v) and --icp iterations per level; every --icp-metric and --icp-loss applies to every level.
+// --icp-starts K (needs --icp; K in 1..64) refines several start poses in one batch (algorithms/icp_batch.h): the matcher runs
+// with a TopPoses(K, 10 degrees, 2 x the ICP distance) listener, its own result is start 0 and its other distinct candidates of
+// greatest LCP follow; RefineICPBatch keeps the pose with the most correspondences on the full clouds (then the least rmse), so
+// the outcome never has fewer correspondences than --icp alone.  Point and plane metrics only, no --icp-loss, no pair
+// rejection.  With --icp-scales the batch runs on the coarsest level's clouds and the other levels follow from its pose.
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
@@ -38,6 +43,7 @@
 #include <vector>
 
 #include "super4pcs/algorithms/icp.h"
+#include "super4pcs/algorithms/icp_batch.h"
 #include "super4pcs/algorithms/icp_multiscale.h"
 #include "super4pcs/algorithms/normals.h"
 #include "super4pcs/algorithms/outliers.h"
@@ -102,6 +108,17 @@ bool save_points(IOManager& io, const std::string& path, const std::vector<Point
   return m.save(io, path);
 }
 
+// Progress and TopPoses together: one visitor for the matcher
+struct ProgressAndPoses {
+  const TopPoses* top;
+  inline void operator()(float fraction, float best_lcp, Match4PCSBase::MatrixRef T) const {
+    if (fraction < 0) { (*top)(fraction, best_lcp, T); return; }
+    std::printf("done: %d%c best: %f                  \r", int(fraction * 100), '%', best_lcp);
+    std::fflush(stdout);
+  }
+  constexpr bool needsGlobalTransformation() const { return true; }
+};
+
 // progress line while the matcher runs: one call per trial with the fraction done; per-candidate calls carry -1
 struct Progress {
   inline void operator()(float fraction, float best_lcp, Match4PCSBase::MatrixRef) const {
@@ -162,9 +179,18 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
     }
     std::vector<Point3D> Q0;                                // the second input in its own frame: the matcher moves Q.points
     if (opt.icp_iterations > 0 && !opt.icp_scales.empty()) Q0 = Q.points;
+    const double icp_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
     MatchSuper4PCS matcher(mopt, log);
     log.Log<Utils::Verbose>("Use Super4PCS");
-    score = matcher.ComputeTransformation(P.points, &Q.points, mat, Sampling::UniformDistSampler(), Progress());
+    std::vector<Match4PCSBase::MatrixType> starts;           // --icp-starts: relative to Q as the matcher leaves it
+    if (opt.icp_starts > 0) {
+      const TopPoses top(opt.icp_starts, 10.0, 2.0 * icp_distance, TopPoses::Centroid(Q.points));
+      score = matcher.ComputeTransformation(P.points, &Q.points, mat, Sampling::UniformDistSampler(), ProgressAndPoses{&top});
+      starts = top.StartsAfter(mat);
+      log.Log<Utils::Verbose>("ICP starts: ", starts.size(), " of ", top.arrivals(), " candidates (the matcher's own first)");
+    } else {
+      score = matcher.ComputeTransformation(P.points, &Q.points, mat, Sampling::UniformDistSampler(), Progress());
+    }
     const std::vector<Point3D>* sampled[2] = {&matcher.getFirstSampled(), &matcher.getSecondSampled()};
     for (int k = 0; k < 2; ++k) {
       if (opt.sampled[k].empty()) continue;
@@ -174,7 +200,7 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
     if (opt.icp_iterations > 0) {
       ICPOptions icp;
       icp.max_iterations = opt.icp_iterations;
-      icp.max_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
+      icp.max_distance = icp_distance;
       icp.metric = opt.icp_gicp ? ICPMetric::Generalized : (opt.icp_plane ? ICPMetric::PointToPlane : ICPMetric::PointToPoint);
       if (opt.icp_color) icp.metric = ICPMetric::Colored;
       icp.color_lambda = opt.icp_color_lambda;
@@ -195,11 +221,48 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
           levels.push_back(level);
         }
         std::vector<ICPResult> res;
-        RefineICPMultiScale(P.points, &Q0, mat, icp, levels, &res);
+        if (!starts.empty()) {
+          // the coarsest level as a batch on its clouds (RefineICPMultiScale's order: downsample, move by mat, refine),
+          // then the remaining levels from the pose it picked
+          std::vector<Point3D> Pl = P.points, Ql = Q0;
+          if (levels[0].voxel_size > 0) {
+            VoxelGridOptions vopt;
+            vopt.voxel_size = levels[0].voxel_size;
+            VoxelDownsample(Pl, vopt);
+            VoxelDownsample(Ql, vopt);
+          }
+          detail::icp_move_points(Ql, mat);
+          ICPOptions lopt = icp;
+          lopt.max_distance = levels[0].max_distance;
+          lopt.max_iterations = levels[0].max_iterations;
+          std::vector<ICPResult> bres;
+          const auto best = RefineICPBatch(Pl, &Ql, starts, lopt, &bres);
+          mat = Compose(best.first, mat);
+          log.Log<Utils::Verbose>("ICP best pose: start ", best.second, " of ", starts.size(), ", correspondences ",
+                                  bres[size_t(best.second)].n_corr, " (start 0: ", bres[0].n_corr, ")");
+          const ICPLevel first = levels[0];
+          levels.erase(levels.begin());
+          std::vector<ICPResult> rest;
+          if (!levels.empty()) RefineICPMultiScale(P.points, &Q0, mat, icp, levels, &rest);
+          else detail::icp_move_points(Q0, mat);
+          levels.insert(levels.begin(), first);
+          res.push_back(bres[size_t(best.second)]);
+          res.insert(res.end(), rest.begin(), rest.end());
+        } else {
+          RefineICPMultiScale(P.points, &Q0, mat, icp, levels, &res);
+        }
         for (size_t i = 0; i < Q0.size(); ++i) Q.points[i].pos() = Q0[i].pos();
         for (size_t l = 0; l < res.size(); ++l)
           log.Log<Utils::Verbose>("ICP level ", l, " (voxel ", levels[l].voxel_size, ", distance ", levels[l].max_distance, "): ",
                                   res[l].iterations, " iterations, rmse ", res[l].rmse, ", fitness ", res[l].fitness);
+      } else if (!starts.empty()) {
+        std::vector<ICPResult> bres;
+        const auto best = RefineICPBatch(P.points, &Q.points, starts, icp, &bres);
+        mat = Compose(best.first, mat);
+        const ICPResult& res = bres[size_t(best.second)];
+        log.Log<Utils::Verbose>("ICP best pose: start ", best.second, " of ", starts.size(), ", correspondences ", res.n_corr,
+                                " (start 0: ", bres[0].n_corr, ")");
+        log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);
       } else {
         ICPResult res;
         RefineICP(P.points, &Q.points, mat, icp, &res);

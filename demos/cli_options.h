@@ -49,6 +49,8 @@ struct Options {
   double voxel_size = -1;                                    // --voxel-size v  voxel-grid downsampling of both inputs (off)
   std::vector<double> icp_scales;                            // --icp-scales v1,v2,...  multi-scale ICP levels, coarse to fine (needs --icp)
   bool icp_scales_set = false;
+  int icp_starts = 0;                                        // --icp-starts K  refine the matcher's K best distinct poses in one batch (needs --icp)
+  bool icp_starts_set = false;
   bool bad_value = false;                                    // a flag's value does not parse
 };
 
@@ -181,6 +183,12 @@ inline const Flag* flag_table(size_t* n) {
            p = end + 1;
          }
        }},
+      {"--icp-starts", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long k = std::strtol(v[0], &end, 10);
+         o.icp_starts_set = true;
+         if (end == v[0] || *end != '\0' || k < 1 || k > 64) o.bad_value = true; else o.icp_starts = int(k);
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -213,6 +221,9 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.icp_color_lambda_set && !o.icp_color) return Parse::Bad;       // --icp-color-lambda needs --icp-metric color
   if (o.icp_scales_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-scales needs --icp
   if ((o.icp_reciprocal || o.icp_normal_angle_set) && o.icp_iterations == 0) return Parse::Bad;    // pair rejection needs --icp
+  if (o.icp_starts_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-starts needs --icp
+  // the batch refines point and plane only, without a loss and without pair rejection
+  if (o.icp_starts_set && (o.icp_loss != 0 || o.icp_gicp || o.icp_color || o.icp_reciprocal || o.icp_normal_angle_set)) return Parse::Bad;
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -250,6 +261,10 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ --icp-scales v1,v2,... (needs --icp; off) ]\n");
   std::fprintf(stderr, "\t    (multi-scale ICP: one level per voxel size, coarse to fine, non-increasing, the last may be 0 = the inputs as\n");
   std::fprintf(stderr, "\t     they are; level distance max(--icp-dist, 3 v), --icp iterations per level)\n");
+  std::fprintf(stderr, "\t[ --icp-starts K (1..64, needs --icp; off) ]\n");
+  std::fprintf(stderr, "\t    (multi-start ICP: the matcher's K best distinct poses, its own result first, refined in one batch; the one with\n");
+  std::fprintf(stderr, "\t     the most correspondences on the full clouds, then the least rmse, is kept; --icp-metric point or plane only, no\n");
+  std::fprintf(stderr, "\t     --icp-loss, no pair rejection; with --icp-scales the batch is the coarsest level)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

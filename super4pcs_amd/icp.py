@@ -1,7 +1,8 @@
 """ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
-include/s4p_icp_color.h and include/s4p_icp_reject.h (libsuper4pcs_icp.so): point-to-point, point-to-plane, generalized
-(plane-to-plane) and coloured ICP refinement on the full-resolution clouds, with optional robust losses for the first two and
-optional correspondence rejection (reciprocal pairs, normal angle) for all of them.
+include/s4p_icp_color.h, include/s4p_icp_reject.h and include/s4p_icp_batch.h (libsuper4pcs_icp.so): point-to-point,
+point-to-plane, generalized (plane-to-plane) and coloured ICP refinement on the full-resolution clouds, with optional robust
+losses for the first two, optional correspondence rejection (reciprocal pairs, normal angle) for all of them, and batched
+multi-start refinement (many start poses in one pass, ranked on the full clouds) for the first two.
 
     from super4pcs_amd import icp
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta)     # T maps Q onto P (caller frame, float64 4x4)
@@ -10,6 +11,7 @@ optional correspondence rejection (reciprocal pairs, normal angle) for all of th
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="gicp")    # normals of both clouds (given or estimated)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="color", target_intensity=rgbP, source_intensity=rgbQ)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, reciprocal=True, normal_angle=60)   # pair rejection, any metric / loss
+    T, res, i = icp.refine_best(P, Q, T0s, max_distance=4 * delta)          # up to 64 starts side by side; the best by n_corr, rmse
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -67,6 +69,10 @@ COLOR_SYMBOLS = [                                          # include/s4p_icp_col
 REJECT_SYMBOLS = [                                         # include/s4p_icp_reject.h
     "s4p_icp_reject_defaults", "s4p_icp_set_rejection", "s4p_icp_rejection", "s4p_icp_rejection_counts",
 ]
+BATCH_SYMBOLS = [                                          # include/s4p_icp_batch.h
+    "s4p_icp_sums_batch", "s4p_icp_refine_batch", "s4p_icp_rank_batch",
+]
+BATCH_MAX = 64                                             # S4P_ICP_BATCH_MAX
 NORMALS_OFF, NORMALS_UNORIENTED, NORMALS_ORIENTED = 0, 1, 2         # S4P_ICP_REJECT_NORMALS_*
 WHY_KEPT, WHY_UNMATCHED, WHY_NORMALS, WHY_RECIPROCITY = 0, 1, 2, 3  # S4P_ICP_WHY_*
 
@@ -80,6 +86,10 @@ class ICPError(RuntimeError):
 class Params(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("min_correspondences", C.c_int32), ("rel_tol", C.c_double),
                 ("order_source", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BatchParams(C.Structure):
+    _fields_ = [("icp", Params), ("metric", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Robust(C.Structure):
@@ -187,6 +197,12 @@ def load_library():
     L.s4p_icp_rejection.argtypes = [vp, fp, ip, fp, ip]
     L.s4p_icp_rejection_counts.restype = C.c_int32
     L.s4p_icp_rejection_counts.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.s4p_icp_sums_batch.restype = C.c_int32
+    L.s4p_icp_sums_batch.argtypes = [vp, C.c_int32, C.c_int32, fp, dp]
+    L.s4p_icp_refine_batch.restype = C.c_int32
+    L.s4p_icp_refine_batch.argtypes = [vp, C.POINTER(BatchParams), C.c_int32, dp, C.POINTER(Result), ip]
+    L.s4p_icp_rank_batch.restype = C.c_int32
+    L.s4p_icp_rank_batch.argtypes = [C.POINTER(Result), C.c_int32, ip]
     _LIB = L
     return L
 
@@ -280,6 +296,37 @@ def compose(A, B):
 
 def _is_torch(t):
     return type(t).__module__.startswith("torch")
+
+
+def _batch_metric(metric):
+    if metric not in METRICS:
+        raise ValueError("a batch refines metric \"point\" or \"plane\" (robust losses, \"gicp\" and \"color\" have no batch form)")
+    return METRICS.index(metric)
+
+
+def _batch_transforms(Ts, dtype):
+    """(B, 4, 4) contiguous of the given type from B transforms, 1 <= B <= BATCH_MAX."""
+    T = np.ascontiguousarray(np.asarray(Ts, dtype))
+    if T.ndim == 2 and T.shape == (4, 4):
+        T = T.reshape(1, 4, 4)
+    if T.ndim != 3 or T.shape[1:] != (4, 4):
+        raise ValueError("the transforms of a batch are (B, 4, 4)")
+    if not (1 <= T.shape[0] <= BATCH_MAX):
+        raise ValueError("a batch holds 1..%d transforms, not %d" % (BATCH_MAX, T.shape[0]))
+    return T.copy()
+
+
+def rank_batch(results):
+    """int32 (B,): the order of include/s4p_icp_batch.h over a sequence of Result -- n_corr descending, then rmse ascending,
+    then the index; poses without a correspondence last.  Host only, needs no device."""
+    L = load_library()
+    B = len(results)
+    arr = (Result * max(B, 1))(*results)
+    order = np.empty(max(B, 1), np.int32)
+    rc = L.s4p_icp_rank_batch(arr, B, order.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise ICPError(rc, "rank_batch: 1..%d results" % BATCH_MAX)
+    return order
 
 
 def _check_metric(metric, loss):
@@ -567,6 +614,34 @@ class ICP:
         self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
         return T.reshape(4, 4), r
 
+    def sums_batch(self, Ts, metric="point"):
+        """float64 (B, 17) for "point" or (B, 31) for "plane": row b holds the bits of sums(Ts[b]) / plane_sums(Ts[b]), from
+        one launch over all B float transforms in the centred frame (include/s4p_icp_batch.h)."""
+        m = _batch_metric(metric)
+        T = _batch_transforms(Ts, np.float32)
+        B = T.shape[0]
+        out = np.empty((B, PLANE_NSUMS if metric == "plane" else NSUMS), np.float64)
+        self._chk(self.L.s4p_icp_sums_batch(self.h, m, B, _fp(T), _dp(out)))
+        return out
+
+    def refine_batch(self, T0s, max_iterations=30, rel_tol=1e-6, min_correspondences=3, order_source=True, metric="point"):
+        """(Ts float64 (B, 4, 4) in the caller's frame, [Result] * B, order int32 (B,)) from the B start transforms T0s,
+        refined side by side (include/s4p_icp_batch.h): a pose that stops leaves the launches, the final pass covers all
+        B.  order[0] is the best pose: n_corr descending, then rmse ascending, then the index.  order_source=True orders
+        the source once, by its image under T0s[0]."""
+        m = _batch_metric(metric)
+        T = _batch_transforms(T0s, np.float64)
+        B = T.shape[0]
+        p = BatchParams()
+        self.L.s4p_icp_default_params(C.byref(p.icp))
+        p.icp.max_iterations, p.icp.rel_tol, p.icp.min_correspondences = int(max_iterations), float(rel_tol), int(min_correspondences)
+        p.icp.order_source = int(bool(order_source))
+        p.metric = m
+        res = (Result * B)()
+        order = np.empty(B, np.int32)
+        self._chk(self.L.s4p_icp_refine_batch(self.h, C.byref(p), B, _dp(T), res, order.ctypes.data_as(C.POINTER(C.c_int32))))
+        return T, [Result.from_buffer_copy(r) for r in res], order
+
     def apply(self, T, X):
         """float32 (N, 3): float(T) applied to X on the device in k_apply's rounding order."""
         T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
@@ -621,5 +696,32 @@ def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_no
             r_n = max_distance if normal_radius is None else normal_radius
             ctx.estimate_color_gradients(r_n if color_radius is None else color_radius)
         return ctx.refine(T0, metric=metric, **params)
+    finally:
+        ctx.close()
+
+
+def refine_best(P, Q, T0s, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None, **params):
+    """(T, Result, index): every start of T0s (B, 4, 4; 1 <= B <= 64) refined in one batch on one context (target P, source
+    Q, numpy arrays or GPU torch tensors as for refine), and the one the full clouds prefer: the most correspondences, then
+    the least rmse, then the first.  metric "point" or "plane" (target normals as for refine); params go to
+    ICP.refine_batch.  max_distance is required."""
+    if max_distance is None:
+        raise ValueError("max_distance is required (4 * delta after a registration at delta)")
+    _batch_metric(metric)
+    T0s = _batch_transforms(T0s, np.float64)
+    if metric != "plane" and (target_normals is not None or normal_radius is not None):
+        raise ValueError("target_normals / normal_radius need metric \"plane\"")
+    ctx = ICP(device)
+    try:
+        ctx.set_target(P, max_distance)
+        ctx.set_source(Q)
+        if metric == "plane":
+            if target_normals is not None:
+                ctx.set_target_normals(target_normals)
+            else:
+                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
+        Ts, results, order = ctx.refine_batch(T0s, metric=metric, **params)
+        i = int(order[0])
+        return Ts[i], results[i], i
     finally:
         ctx.close()

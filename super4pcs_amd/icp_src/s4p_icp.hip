@@ -39,6 +39,7 @@
 #include "s4p_icp_gicp.h"
 #include "s4p_icp_color.h"
 #include "s4p_icp_reject.h"
+#include "s4p_icp_batch.h"
 
 
 // The parts, in dependency order ("ICP sources: layout"):
@@ -58,3 +59,8 @@
 #include "s4p_icp_ctx.inc"
 #include "s4p_icp_pass.inc"
 #include "s4p_icp_abi.inc"
+// batched multi-start ICP (include/s4p_icp_batch.h), after the existing parts so that their kernels keep their places:
+//   s4p_icp_k_batch.hip.hpp    k_match_batch, k_final_batch: a pose per row of workgroups
+//   s4p_icp_batch.inc          the batch's buffers, the batched pass, the refine loop over an active list, the ranking
+#include "s4p_icp_k_batch.hip.hpp"
+#include "s4p_icp_batch.inc"

@@ -80,6 +80,12 @@ struct s4p_icp_ctx {
   Pinned<unsigned long long> rhcnt;
   bool rej_pending = false;          // a k_reject of this pass is in flight: its counters follow the sums to the host
   int64_t rej_counts[4] = {0, 0, 0, 0};
+  // batched multi-start ICP (include/s4p_icp_batch.h), allocated on the first batch call (s4p_icp_batch.inc)
+  Buf<double> bslab;                 // [pose][kMaxBlocks] slab rows
+  Buf<double> bsum;                  // one row of sums per pose of a launch
+  Pinned<double> bhsum;
+  Buf<unsigned char> bposes;         // a BatchPoses: every transform and the active list
+  Pinned<unsigned char> bstage;      // its staging, one upload per launch
 
   // runs before the buffers release themselves; hidden: the library exports its C ABI only
   __attribute__((visibility("hidden"))) ~s4p_icp_ctx() { (void)hipSetDevice(device); }

@@ -6,7 +6,8 @@
 // move without touching a kernel's own code: a kernel's code ends with the padding up to the next one, so the last kernel
 // of the code object differs from one that is followed.  Non-template kernels are emitted in the order of their
 // definitions and k_final_plane is the last of them; template kernels follow in the order of their first launch in the
-// host parts, and k_match<false> is the last of those (s4p_icp_pass.inc).
+// host parts, and k_match<false> is the last of those in these parts (s4p_icp_pass.inc); the kernels of s4p_icp_k_batch.hip.hpp
+// are launched from a later part and follow it.
 #pragma once
 
 namespace s4p_icp {

@@ -218,7 +218,8 @@ int32_t color_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double lambda
 }
 
 // The fused passes come last of the passes: template kernels are emitted in the order of their first launch in this file,
-// and k_match<false> stays the last kernel of the code object (the end of a kernel's code includes the padding up to the next).
+// and k_match<false> stays the last kernel these parts emit (the end of a kernel's code includes the padding up to the next;
+// the batch kernels of s4p_icp_batch.inc come after it).
 
 // the fused point pass: the 17 sums (and, if idx, the per-point answers)
 int32_t pass(s4p_icp_ctx* h, const Tf& T, const float4* src, int32_t* idx_dev, float* d2_dev, double* out) {

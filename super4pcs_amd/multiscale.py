@@ -60,8 +60,12 @@ def _level_cloud(X, v, normals, intensity, device):
     return xyz, nrm, inten
 
 
+_BATCH_PARAMS = ("rel_tol", "min_correspondences", "order_source", "normal_radius")
+
+
 def refine_multiscale(P, Q, T0=None, voxel_sizes=(0,), max_distances=None, max_iterations=None, device=0, metric="point",
-                      target_normals=None, source_normals=None, target_intensity=None, source_intensity=None, **params):
+                      target_normals=None, source_normals=None, target_intensity=None, source_intensity=None, starts=None,
+                      **params):
     """Coarse-to-fine ICP: (T float64 4x4, [icp.Result per level]).
 
     Levels run in the order given.  voxel_sizes[l] > 0 downsamples both clouds at that size (voxel.voxel_downsample; Q in its
@@ -73,7 +77,20 @@ def refine_multiscale(P, Q, T0=None, voxel_sizes=(0,), max_distances=None, max_i
 
     max_distances: one distance per level.  max_distances=None needs max_distance= (d); then d_l = max(d, 3 * v_l).  The factor
     3 follows common practice (level distances of about three voxels); it is not measured here.  max_iterations: one count
-    per level, or one number for all; None is 30 per level."""
+    per level, or one number for all; None is 30 per level.
+
+    starts: B start transforms (B, 4, 4) in place of T0.  The coarsest level is then one icp.refine_best on the level's
+    clouds (every start refined side by side, ranked by correspondences, then rmse), and its best pose feeds the remaining
+    levels unchanged; results[0] is that pose's Result.  Only the metrics "point" and "plane" without a loss and without pair
+    rejection have a batch form: anything else with starts= raises ValueError."""
+    if starts is not None:
+        if T0 is not None:
+            raise ValueError("give T0 (one start) or starts (several), not both")
+        if metric not in _icp.METRICS or params.get("loss") is not None:
+            raise ValueError("starts= needs metric \"point\" or \"plane\" and no loss (robust losses, \"gicp\" and \"color\" have no batch form)")
+        if params.get("reciprocal") or params.get("normal_angle") is not None:
+            raise ValueError("starts= takes no pair rejection (the batch has no split pass)")
+        starts = _icp._batch_transforms(starts, np.float64)
     plan = level_plan(voxel_sizes, max_distances, max_iterations, params.pop("max_distance", None))
     _icp._check_metric(metric, params.get("loss"))
     if target_intensity is not None:
@@ -88,6 +105,12 @@ def refine_multiscale(P, Q, T0=None, voxel_sizes=(0,), max_distances=None, max_i
             cache = {v: (_level_cloud(P, v, target_normals, target_intensity, device),
                          _level_cloud(Q, v, source_normals, source_intensity, device))}
         (Pl, Pn, Pi), (Ql, Qn, Qi) = cache[v]
+        if starts is not None and not results:
+            T, r, _ = _icp.refine_best(Pl, Ql, starts, max_distance=d, device=device, metric=metric,
+                                       target_normals=Pn if metric == "plane" else None, max_iterations=it,
+                                       **{k: params[k] for k in _BATCH_PARAMS if k in params and (k != "normal_radius" or metric == "plane")})
+            results.append(r)
+            continue
         T, r = _icp.refine(Pl, Ql, T0=T, max_distance=d, device=device, metric=metric, target_normals=Pn, source_normals=Qn,
                            target_intensity=Pi, source_intensity=Qi, max_iterations=it, **params)
         results.append(r)
