@@ -41,10 +41,11 @@ def planar_case(seed=3, n_p=20_000, n_q=5_000):
     return dict(P=P, N=N, Ip=Ip, Q=Q, Iq=Ip[pick].copy(), T_true=np.linalg.inv(M), d=0.03, r=0.03)
 
 
-def neighbour_pairs(Pc, r, chunk=20_000):
+def neighbour_pairs(Pc, r, chunk=20_000, which=None):
     """N(i) of include/s4p_icp_plane.h / s4p_icp_color.h for the centred target Pc: yields (i, j) index arrays, i ascending,
     with float32 d2(p_i, p_j) = dx*dx + (dy*dy + dz*dz) <= fl(r*r), i itself included.  Candidates come from a grid of edge
-    1.01 r (27 cells hold every point within r); the decision is the contract's float comparison."""
+    1.01 r (27 cells hold every point within r); the decision is the contract's float comparison.  which (sorted indices):
+    only those i, from the same grid over all points and in the same order per i."""
     Pc = np.ascontiguousarray(Pc, np.float32)
     n = len(Pc)
     r2 = np.float32(r) * np.float32(r)
@@ -56,8 +57,9 @@ def neighbour_pairs(Pc, r, chunk=20_000):
     order = np.argsort(key, kind="stable")
     skey = key[order]
     offs = np.array([(dz * dims[1] + dy) * dims[0] + dx for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1)], np.int64)
-    for a in range(0, n, chunk):
-        ii = np.arange(a, min(n, a + chunk))
+    rows = np.arange(n) if which is None else np.asarray(which, np.int64)
+    for a in range(0, len(rows), chunk):
+        ii = rows[a:a + chunk]
         nk = (key[ii][:, None] + offs[None, :]).ravel()
         b = np.searchsorted(skey, nk, "left"); e = np.searchsorted(skey, nk, "right")
         cnt = e - b
@@ -70,18 +72,23 @@ def neighbour_pairs(Pc, r, chunk=20_000):
         yield i_rep[keep], j[keep]
 
 
-def gradient_systems(Pc, Nc, I, r):
-    """(k int64[n], A float64[n, 3, 3], b float64[n, 3]) of the header: S = sum u u^T, b = sum u dI over N(i), A = S + tr(S) n n^T."""
-    n = len(Pc)
+def gradient_systems(Pc, Nc, I, r, which=None):
+    """(k int64[n], A float64[n, 3, 3], b float64[n, 3]) of the header: S = sum u u^T, b = sum u dI over N(i), A = S + tr(S) n n^T.
+    which (sorted indices): the rows of those points only (n = len(which)), the same terms in the same order."""
+    rows = np.arange(len(Pc)) if which is None else np.asarray(which, np.int64)
+    assert np.all(np.diff(rows) > 0)
+    n = len(rows)
     P64 = np.asarray(Pc, np.float32).astype(np.float64); N64 = np.asarray(Nc, np.float32).astype(np.float64)
     I64 = np.asarray(I, np.float32).astype(np.float64)
     k = np.zeros(n, np.int64); S = np.zeros((n, 6)); b = np.zeros((n, 3))
-    for i, j in neighbour_pairs(Pc, r):
+    for i, j in neighbour_pairs(Pc, r, which=which):
         e = P64[j] - P64[i]
         nv = N64[i]
         en = (e[:, 0] * nv[:, 0] + e[:, 1] * nv[:, 1]) + e[:, 2] * nv[:, 2]
         u = e - en[:, None] * nv
         dI = I64[j] - I64[i]
+        if which is not None:
+            i = np.searchsorted(rows, i)                                # the point's row
         k += np.bincount(i, minlength=n)
         for c, (p, q) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
             S[:, c] += np.bincount(i, weights=u[:, p] * u[:, q], minlength=n)
@@ -89,17 +96,20 @@ def gradient_systems(Pc, Nc, I, r):
             b[:, c] += np.bincount(i, weights=u[:, c] * dI, minlength=n)
     tr = (S[:, 0] + S[:, 3]) + S[:, 5]
     A = np.empty((n, 3, 3))
+    N64 = N64[rows]
     for c, (p, q) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
         A[:, p, q] = S[:, c] + tr * (N64[:, p] * N64[:, q])
         A[:, q, p] = A[:, p, q]
     return k, A, b
 
 
-def color_gradients(Pc, Nc, I, r, min_neighbours):
+def color_gradients(Pc, Nc, I, r, min_neighbours, which=None):
     """(g float32[n, 3], ratio float64[n], k): the header's gradients, zero where k < min_neighbours, the normal is zero or
     ratio = lambda_min(A) / lambda_max(A) <= 1e-6 (numpy's eigvalsh for the device's Jacobi: the callers keep the ratio
-    away from the gate).  ratio is nan where there is no system (zero normal or too few neighbours) or A = 0."""
-    k, A, b = gradient_systems(Pc, Nc, I, r)
+    away from the gate).  ratio is nan where there is no system (zero normal or too few neighbours) or A = 0.  which (sorted
+    indices): those points' rows only."""
+    k, A, b = gradient_systems(Pc, Nc, I, r, which=which)
+    Nc = np.asarray(Nc) if which is None else np.asarray(Nc)[np.asarray(which, np.int64)]
     has = np.any(np.asarray(Nc) != 0, axis=1) & (k >= min_neighbours)
     w = np.linalg.eigvalsh(A)
     with np.errstate(invalid="ignore", divide="ignore"):

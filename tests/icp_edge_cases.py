@@ -142,11 +142,202 @@ def long_launch():
     return Case("long_launch", P, Q, 4 * 0.004, np.array(T, np.float64))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# dense variants and tiny targets: targets whose points have neighbours within d, so that the
+# target-side walks (k_normals, k_color_gradient) sum something in the plan's other branch
+
+DENSE_SEED = 77
+CLUSTER = 10                                    # points per cluster centre
+CLUSTER_HALF = 0.35                             # a cluster is uniform in +-0.35 d per axis: nearly every two of its points are within d
+
+
+def _dense(parent, name, n_q, sigma, flatten=False):
+    """The parent's first n_P / 10 points as cluster centres, 10 points per centre uniform in +-0.35 d per axis (z = 0
+    afterwards for the flat case): the parent's n_P, d and grid regime, and about 10 points within d of every point (two
+    points of a cluster are at most 0.7 d apart per axis; the host module asserts at least 6 neighbours everywhere).
+    Q: the first n_q points plus noise, as the parent cuts its own."""
+    case = parent()
+    rng = np.random.default_rng(DENSE_SEED)
+    m = len(case.P) // CLUSTER
+    P = np.repeat(case.P[:m].astype(np.float64), CLUSTER, 0) + rng.uniform(-CLUSTER_HALF * case.d, CLUSTER_HALF * case.d, (m * CLUSTER, 3))
+    if flatten:
+        P[:, 2] = 0.0
+    P = P.astype(F)
+    Q = (P[:n_q] + rng.normal(scale=sigma, size=(n_q, 3))).astype(F)
+    return Case(name, P, Q, case.d, np.eye(4))
+
+
+def enlarged_dense():
+    return _dense(enlarged, "enlarged_dense", 50_000, 0.002)
+
+
+def needle_dense():
+    return _dense(needle, "needle_dense", 9001, 0.02)
+
+
+def flat_dense():
+    return _dense(flat, "flat_dense", 4099, 0.004, flatten=True)
+
+
+DENSE = {"enlarged_dense": enlarged_dense, "needle_dense": needle_dense, "flat_dense": flat_dense}
+
+
+def dup_mixed():
+    """5000 cube points and 50 of them 20 more times each, d = 0.1 (about 21 neighbours within d): duplicates inside ordinary
+    neighbourhoods, for the sums whose terms are then exactly zero.  The copies follow the originals in the upload."""
+    P, rng = _cube(3, 5000)
+    pick = np.sort(rng.choice(5000, 50, replace=False))
+    P = np.concatenate([P, np.repeat(P[pick], 20, 0)])
+    Q = (P[:1500] + rng.normal(scale=0.02, size=(1500, 3))).astype(F)
+    return Case("dup_mixed", P, Q, 0.1, np.eye(4))
+
+
+TINY_N = (1, 5, 6, 63, 64, 65, 257)
+
+
+def tiny_target(n):
+    """The first n cube points scaled into a box of edge d / 2: every two within d, one cell; n = 5 is below min_neighbours = 6
+    and n = 6 exactly at it."""
+    d = 0.1
+    P = (_cube(2)[0][:n].astype(np.float64) * (0.5 * d)).astype(F)
+    rng = np.random.default_rng(300 + n)
+    Q = (P[np.arange(40) % n] + rng.normal(scale=0.2 * d, size=(40, 3))).astype(F)
+    return Case("tiny_target_%d" % n, P, Q, d, np.eye(4))
+
+
+TINY = {"tiny_target_%d" % n: (lambda n=n: tiny_target(n)) for n in TINY_N}
+
+TEXTURE_SCALE = {"needle": 0.02, "needle_dense": 0.02, "one_target": 4.0, "identical_targets": 4.0, "far": 4.0}
+
+
+def texture_scale(name):
+    """The scale at which icp_color_helpers.texture is sampled: about 1.5 periods across the cloud (the needle is 1000 long: a
+    scale of 1 would alias along x), 10 periods per unit for the tiny targets (d / 2 across)."""
+    if name.startswith("tiny_target"):
+        return 10.0
+    return TEXTURE_SCALE.get(name, 1.0)
+
+
+def intensity(case, X=None):
+    """texture() at coordinates relative to the case's origin (a field that varies over the cloud, wherever the cloud sits)."""
+    from tests import icp_color_helpers as CH
+    X = case.P if X is None else X
+    return CH.texture(np.asarray(X, np.float64) - case.origin, texture_scale(case.name))
+
+
+def caller_normals(P, seed):
+    """Section 15's caller normals: random directions, not unit length, every 11th zero."""
+    raw = np.random.default_rng(seed).normal(size=P.shape).astype(F) * 3
+    raw[::11] = 0
+    return raw
+
+
+TILTED = np.array([0.36, -0.48, 0.8], F)          # a unit vector in double (0.1296 + 0.2304 + 0.64)
+
+
+def gradient_normals(case):
+    """The caller normals the gradient tests use per case, as (label, raw) pairs.  flat_dense: constant ones, (0, 0, 1) and a
+    tilted unit vector with every 11th zero; random directions there put tangent planes edge-on to z = 0 and 17 points within a
+    factor 2 of the gate, which is outside the restatement's input condition."""
+    n = len(case.P)
+    if case.name == "flat_dense":
+        up = np.tile(np.array([0, 0, 1], F), (n, 1))
+        tilted = np.tile(TILTED, (n, 1))
+        tilted[::11] = 0
+        return [("up", up), ("tilted", tilted)]
+    return [("random", caller_normals(case.P, 4))]
+
+
+def source_normals(n, seed):
+    """Caller source normals as the generalized, coloured and rejection modules make them: not unit length, every 11th zero,
+    one NaN."""
+    raw = np.random.default_rng(seed).normal(size=(n, 3)).astype(F) * 3
+    raw[::11] = 0
+    if n > 5:
+        raw[5, 0] = np.nan
+    return raw
+
+
+SUMS_MOTION = (0.3, 0.002)                      # degrees, shift: the one motion of the sums tests, about the case's origin
+REJECTIONS = (dict(reciprocal=True), dict(reciprocal=True, normal_mode=1, normal_cos=float(np.cos(np.deg2rad(60.0)))))
+
+
+def sums_inputs(case):
+    """What the sums tests upload next to the clouds: raw target normals (the case's first gradient_normals), raw source normals,
+    both intensities (one field: the source's is sampled where the base pose puts it) and the two poses."""
+    from tests import icp_robust_helpers as RH
+    Qm = case.Q.astype(np.float64) @ case.T0[:3, :3].T + case.T0[:3, 3]
+    return dict(raw_p=gradient_normals(case)[0][1], raw_q=source_normals(len(case.Q), 8), Ip=intensity(case), Iq=intensity(case, Qm),
+                poses=(pose(case, np.eye(4)), pose(case, RH.motion(*SUMS_MOTION))))
+
+
+def cell_order_position(P, d):
+    """Position of every point in the library's cell order under plan(): cells ascending (x fastest), upload order inside a cell."""
+    pl = plan(P, d)
+    Pc = (np.asarray(P, F) - pl["c"]).astype(F)
+    f = np.clip(cell_coords(pl, Pc).astype(np.int64), 0, pl["dims"] - 1)
+    key = (f[:, 2] * pl["dims"][1] + f[:, 1]) * pl["dims"][0] + f[:, 0]
+    order = np.argsort(key, kind="stable")
+    pos = np.empty(len(P), np.int64)
+    pos[order] = np.arange(len(P))
+    return pos
+
+
+def gradient_sample(P, d, seed=9, n_random=3000, n_late=2000, margin=1000):
+    """(sorted sample, positions under plan()'s cell order): n_random random points; n_late whose position is at least
+    2048 x 256 + margin, so that a lane's second trip computes them even if the library's cell order moves a point by up to
+    margin places against plan()'s (equal only up to the rounding of the plan); every point within margin places of
+    position 2048 x 256, where the second trip begins (a stride that is off by one loses exactly that position); and the last
+    margin / 2 positions, where it ends."""
+    pos = cell_order_position(P, d)
+    rng = np.random.default_rng(seed)
+    lanes = K_MAX_BLOCKS * K_BLOCK
+    late = np.flatnonzero(pos >= lanes + margin)
+    seam = np.flatnonzero(((pos >= lanes - margin) & (pos < lanes + margin)) | (pos >= len(P) - margin // 2))
+    pick = np.union1d(np.union1d(rng.choice(len(P), n_random, replace=False), rng.choice(late, n_late, replace=False)), seam)
+    return pick, pos
+
+
 SMALL = {"one_target": one_target, "identical_targets": identical_targets, "flat": flat, "needle": needle, "enlarged": enlarged,
          "box_faces": box_faces, "far": far}
 SMALL.update({"ragged_%d" % n: (lambda n=n: ragged(n)) for n in RAGGED_N})
 # DESIGN.md section 15: cases that must leave some sources unmatched
 HAS_MISSES = ("one_target", "identical_targets", "flat", "needle", "enlarged", "box_faces", "far")
+# DESIGN.md section 15.1: one entry per distinct target of SMALL (the ragged cases have box_faces' target and d: the gradients
+# are a function of the target alone), the dense variants, dup_mixed and the tiny targets
+GRADIENT_CASES = {k: v for k, v in SMALL.items() if not k.startswith("ragged_")}
+GRADIENT_CASES.update(DENSE)
+GRADIENT_CASES["dup_mixed"] = dup_mixed
+GRADIENT_CASES.update(TINY)
+SPARSE = ("one_target", "enlarged", "needle", "flat")       # section 15: almost no point has min_neighbours points within d
+NO_GRADIENT = ("one_target", "identical_targets", "tiny_target_1", "tiny_target_5", "needle", "enlarged")
+SUMS_CASES = HAS_MISSES + tuple(DENSE)
+
+
+def gradient_floor(name, n):
+    """The count of nonzero gradients a case must show (a predicate): none where no point has a system or every system is
+    A = 0; more than half where the target is dense (a tenth of the caller normals are zero, and the cube's faces are thin);
+    some for the flat cloud, where 481 of 20 000 points have 6 neighbours."""
+    if name in NO_GRADIENT:
+        return lambda k: k == 0
+    if name == "flat":
+        return lambda k: k > 0
+    return lambda k: k > n / 2
+
+
+def check_reject_counts(name, kw, pl, Qc, Tc, idx, why, counts):
+    """What makes the degenerate cases bite under reciprocity, asserted on a rejection result (restated or the device's): one
+    target keeps one pair at most, and exactly one when reciprocity is the only filter; of 1000 equal targets only index 0 is
+    ever kept; box_faces keeps and rejects pairs whose moved source lies outside the target's box."""
+    from tests import icp_robust_helpers as RH
+    if name in ("one_target", "identical_targets"):
+        assert counts[3] == 1 if not kw.get("normal_mode") else counts[3] <= 1, (name, kw, counts)
+        assert counts[2] > 100 and np.all(idx[why == 0] == 0)
+    if name == "box_faces":
+        f = cell_coords(pl, RH.apply_f32(Tc, Qc))
+        outside = np.any((f < 0) | (f >= pl["dims"]), axis=1)
+        kept, rejected = np.count_nonzero(outside & (why == 0)), np.count_nonzero(outside & (why == 3))
+        assert kept >= 10 and rejected >= 10, (kept, rejected)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
