@@ -4,7 +4,7 @@
 // options, 255 (-1) unreadable input.
 //   Super4PCS -i P.obj Q.obj [-o overlap] [-d delta] [-n samples] [-t seconds] [-a normal_deg] [-c colour]
 //             [-r registered_geometry] [-m polyworks_matrix] [--sampled1 file] [--sampled2 file]
-//             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane|gicp|color] [--icp-normal-radius r]
+//             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane|gicp|symmetric|color] [--icp-normal-radius r]
 //             [--icp-gicp-epsilon e] [--icp-color-lambda l]
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
@@ -14,6 +14,8 @@
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
 // normals as for plane, Q's own when all are nonzero (after --estimate-normals they are), else estimated with k = 16; no --icp-loss.
+// With --icp-metric symmetric it is symmetric ICP (include/s4p_icp_symm.h): point-to-plane along the sum of both normals, the
+// normals of both inputs as for gicp; no parameter, no --icp-loss, no --icp-starts.
 // With --icp-metric color it is coloured ICP (include/s4p_icp_color.h, weight of the geometric term --icp-color-lambda): P's
 // normals as for plane, the colours of both inputs (a coloured PLY or a PTX), gradients within --icp-normal-radius; no --icp-loss.
 // --icp-loss refines with a robust loss (include/s4p_icp_robust.h): trimmed keeps the --icp-trim fraction of |Q| (default
@@ -202,6 +204,7 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       icp.max_iterations = opt.icp_iterations;
       icp.max_distance = icp_distance;
       icp.metric = opt.icp_gicp ? ICPMetric::Generalized : (opt.icp_plane ? ICPMetric::PointToPlane : ICPMetric::PointToPoint);
+      if (opt.icp_symm) icp.metric = ICPMetric::Symmetric;
       if (opt.icp_color) icp.metric = ICPMetric::Colored;
       icp.color_lambda = opt.icp_color_lambda;
       icp.gicp_epsilon = opt.icp_gicp_epsilon;

@@ -25,8 +25,9 @@ struct Options {
   bool legacy_4pcs = false;                                  // -x
   int icp_iterations = 0;                                    // --icp  ICP refinement after the registration (0: off)
   double icp_distance = -1;                                  // --icp-dist  (default 4 delta)
-  bool icp_plane = false;                                    // --icp-metric point|plane|gicp|color  (default point)
+  bool icp_plane = false;                                    // --icp-metric point|plane|gicp|symmetric|color  (default point)
   bool icp_gicp = false;                                     //   gicp: generalized ICP, normals of both clouds
+  bool icp_symm = false;                                     //   symmetric: symmetric ICP, normals of both clouds, no parameter
   bool icp_color = false;                                    //   color: coloured ICP, the colours of both clouds
   double icp_color_lambda = 0.968;                           // --icp-color-lambda l  (color; in [0, 1])
   bool icp_color_lambda_set = false;
@@ -88,10 +89,11 @@ inline const Flag* flag_table(size_t* n) {
          if (end == v[0] || *end != '\0' || !(d > 0)) o.bad_value = true; else o.icp_distance = d;
        }},
       {"--icp-metric", 1, [](Options& o, char** v) {
-         o.icp_plane = o.icp_gicp = o.icp_color = false;
+         o.icp_plane = o.icp_gicp = o.icp_symm = o.icp_color = false;
          if (!std::strcmp(v[0], "point")) {}
          else if (!std::strcmp(v[0], "plane")) o.icp_plane = true;
          else if (!std::strcmp(v[0], "gicp")) o.icp_gicp = true;
+         else if (!std::strcmp(v[0], "symmetric")) o.icp_symm = true;
          else if (!std::strcmp(v[0], "color")) o.icp_color = true;
          else o.bad_value = true;
        }},
@@ -217,13 +219,14 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
   if (o.icp_gicp_epsilon_set && !o.icp_gicp) return Parse::Bad;        // --icp-gicp-epsilon needs --icp-metric gicp
+  if (o.icp_symm && o.icp_loss != 0) return Parse::Bad;                // the symmetric metric takes no loss
   if (o.icp_color && o.icp_loss != 0) return Parse::Bad;               // the coloured metric takes no loss
   if (o.icp_color_lambda_set && !o.icp_color) return Parse::Bad;       // --icp-color-lambda needs --icp-metric color
   if (o.icp_scales_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-scales needs --icp
   if ((o.icp_reciprocal || o.icp_normal_angle_set) && o.icp_iterations == 0) return Parse::Bad;    // pair rejection needs --icp
   if (o.icp_starts_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-starts needs --icp
   // the batch refines point and plane only, without a loss and without pair rejection
-  if (o.icp_starts_set && (o.icp_loss != 0 || o.icp_gicp || o.icp_color || o.icp_reciprocal || o.icp_normal_angle_set)) return Parse::Bad;
+  if (o.icp_starts_set && (o.icp_loss != 0 || o.icp_gicp || o.icp_symm || o.icp_color || o.icp_reciprocal || o.icp_normal_angle_set)) return Parse::Bad;
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
   if (o.registered.empty() && o.matrix.empty()) o.registered = "output.obj";
   return Parse::Run;
@@ -239,8 +242,10 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ -x (legacy 4PCS: not available in this build) ]\n");
   std::fprintf(stderr, "\t[ --sampled1 file ] [ --sampled2 file ]  (sampled clouds)\n");
   std::fprintf(stderr, "\t[ --icp iterations (%d: off) ] [ --icp-dist max_distance (4 delta) ]  (ICP refinement)\n", o.icp_iterations);
-  std::fprintf(stderr, "\t[ --icp-metric point|plane|gicp|color (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
+  std::fprintf(stderr, "\t[ --icp-metric point|plane|gicp|symmetric|color (point) ] [ --icp-normal-radius r (max_distance) ]  (ICP metric)\n");
   std::fprintf(stderr, "\t[ --icp-gicp-epsilon e (gicp; 0.001, in [1e-6, 1]; gicp takes no --icp-loss) ]\n");
+  std::fprintf(stderr, "\t    (symmetric: point-to-plane along the sum of both inputs' normals, obtained as for gicp; no parameter, no --icp-loss,\n");
+  std::fprintf(stderr, "\t     no --icp-starts)\n");
   std::fprintf(stderr, "\t[ --icp-color-lambda l (color; 0.968, in [0, 1]: the weight of the geometric term; color needs coloured\n");
   std::fprintf(stderr, "\t    inputs and takes no --icp-loss) ]\n");
   std::fprintf(stderr, "\t[ --icp-loss none|trimmed|huber|tukey (none) ] [ --icp-trim fraction (trimmed; -o) ]\n");
@@ -249,7 +254,7 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t    keep a pair only when it is nearest in both directions / when its normals, up to sign, differ by at most deg)\n");
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
-  std::fprintf(stderr, "\t     them and --icp-metric plane / gicp / color use P's (gicp: Q's too) when all are nonzero)\n");
+  std::fprintf(stderr, "\t     them and --icp-metric plane / gicp / symmetric / color use P's (gicp, symmetric: Q's too) when all are nonzero)\n");
   std::fprintf(stderr, "\t[ --remove-outliers k (1..32; off) ] [ --remove-outliers-std ratio (needs k; 2.0, >= 0) ]\n");
   std::fprintf(stderr, "\t    (statistical outlier removal of both inputs on the device, right after loading: a point is kept when the mean\n");
   std::fprintf(stderr, "\t     distance to its k nearest others is at most mean + ratio * stddev over the cloud; point sets only, -r writes\n");

@@ -1,11 +1,11 @@
-// RefineICP: point-to-point, point-to-plane, generalized or coloured ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
+// RefineICP: point-to-point, point-to-plane, generalized, symmetric or coloured ICP on the full-resolution clouds, on the MI355X, after a registration.  The reference's
 // documentation recommends refining a coarse Super4PCS pose "using a local algorithm, like the ICP" (doc/Usage.md) instead
 // of sampling more; this header does that step through the C ABI of libsuper4pcs_icp.so (include/s4p_icp.h,
-// include/s4p_icp_plane.h, include/s4p_icp_gicp.h, include/s4p_icp_color.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
+// include/s4p_icp_plane.h, include/s4p_icp_gicp.h, include/s4p_icp_symm.h, include/s4p_icp_color.h), and its robust losses (include/s4p_icp_robust.h: trimmed ICP, Huber, Tukey).
 // Pair rejection (include/s4p_icp_reject.h: reciprocal pairs, normal angle) applies to every metric and loss.
 // Link with -lsuper4pcs_icp.  Builds with and without Eigen, like the rest of the facade.
 //
-// ICPMetric::Generalized needs normals of both clouds.  Q's own are used when every point of Q has a nonzero one.
+// ICPMetric::Generalized and ICPMetric::Symmetric need normals of both clouds.  Q's own are used when every point of Q has a nonzero one.
 // ComputeTransformation moves Q's positions only and leaves its normals in the frame of the file, so RefineICP rotates them
 // by the linear part of `transformation` (in double, row by row as (m0 * x + m1 * y) + m2 * z) before the upload.  Otherwise
 // the normals are estimated on the moved Q as EstimateNormals does with k = 16 (algorithms/normals.h).  That one step binds
@@ -36,6 +36,7 @@
 #include "s4p_icp_plane.h"
 #include "s4p_icp_robust.h"
 #include "s4p_icp_gicp.h"
+#include "s4p_icp_symm.h"
 #include "s4p_icp_color.h"
 #include "s4p_icp_reject.h"
 #include "s4p_normals.h"
@@ -43,7 +44,7 @@
 
 namespace GlobalRegistration {
 
-enum class ICPMetric { PointToPoint, PointToPlane, Generalized, Colored };
+enum class ICPMetric { PointToPoint, PointToPlane, Generalized, Colored, Symmetric };
 enum class ICPLoss { None, Trimmed, Huber, Tukey };
 
 struct ICPOptions {
@@ -59,6 +60,8 @@ struct ICPOptions {
   // Generalized: target normals as for PointToPlane; source normals as described at the top of this header; the covariance
   // parameter epsilon of include/s4p_icp_gicp.h, in [1e-6, 1].  Takes no loss.
   double gicp_epsilon = S4P_ICP_GICP_EPSILON;
+  // Symmetric (include/s4p_icp_symm.h): point-to-plane along the sum of both normals; the normals of both clouds as for
+  // Generalized, no parameter.  Takes no loss.
   // Colored: target normals as for PointToPlane; intensities from rgb() of both clouds; intensity gradients of P estimated
   // on the device within normal_radius (<= 0: max_distance) with at least 6 neighbours; the weight color_lambda of the
   // geometric term (include/s4p_icp_color.h), in [0, 1].  Takes no loss.
@@ -79,7 +82,7 @@ struct ICPOptions {
 
 struct ICPResult {
   int iterations = 0;
-  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane, generalized, coloured)
+  int status = 0;                   // S4P_ICP_MAX_ITERATIONS / _CONVERGED / _TOO_FEW / _DEGENERATE (point-to-plane, generalized, symmetric, coloured)
   int64_t n_corr = 0;
   double rmse = 0.0;
   double fitness = 0.0;             // n_corr / |Q|
@@ -122,12 +125,14 @@ inline void icp_knn_normals(const std::vector<float> (&c)[3], int k, int device,
 // Q as it stands after ComputeTransformation (already moved).  Finds dT, moves Q in place (in k_apply's rounding order)
 // and sets transformation <- dT * transformation.  Returns the fitness of the refined pose.  Throws std::runtime_error
 // when there is no device (no CPU fallback) or an argument is invalid, std::invalid_argument for an empty cloud, a loss with
-// the generalized or coloured metric, or the coloured metric on a cloud with a point that has no colour.
+// the generalized, symmetric or coloured metric, or the coloured metric on a cloud with a point that has no colour.
 inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, Match4PCSBase::MatrixRef transformation,
                        const ICPOptions& options, ICPResult* result = nullptr) {
   if (Q == nullptr || P.empty() || Q->empty()) throw std::invalid_argument("RefineICP: empty cloud");
   const bool gicp = options.metric == ICPMetric::Generalized;
   if (gicp && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the generalized metric takes no loss");
+  const bool symm = options.metric == ICPMetric::Symmetric;
+  if (symm && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the symmetric metric takes no loss");
   const bool colored = options.metric == ICPMetric::Colored;
   if (colored && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the coloured metric takes no loss");
   std::vector<float> ip, iq;
@@ -165,7 +170,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   const bool by_normals = options.normal_angle_deg >= 0;
   if (by_normals && !(options.normal_angle_deg <= (options.normals_oriented ? 180.0 : 90.0)))
     throw std::invalid_argument("RefineICP: normal_angle_deg must be at most 90 (oriented normals: 180)");
-  if (plane || gicp || colored || by_normals) {
+  if (plane || gicp || symm || colored || by_normals) {
     bool all = true;
     for (const Point3D& pt : P) {
       const auto& nv = pt.normal();
@@ -181,7 +186,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
       H.check(s4p_icp_estimate_normals(H.h, float(r), 6));
     }
   }
-  if (gicp || by_normals) {
+  if (gicp || symm || by_normals) {
     bool all = true;
     for (const Point3D& pt : *Q) {
       const auto& nv = pt.normal();
@@ -231,6 +236,7 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   s4p_icp_result r;
   if (options.loss == ICPLoss::None) {
     if (gicp) H.check(s4p_icp_refine_gicp(H.h, &prm, options.gicp_epsilon, dT, &r));
+    else if (symm) H.check(s4p_icp_refine_symm(H.h, &prm, dT, &r));
     else if (colored) H.check(s4p_icp_refine_color(H.h, &prm, options.color_lambda, dT, &r));
     else H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
   } else {

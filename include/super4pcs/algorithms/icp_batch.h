@@ -178,7 +178,7 @@ inline std::pair<Match4PCSBase::MatrixType, int> RefineICPBatch(const std::vecto
   if (starts.empty() || starts.size() > size_t(S4P_ICP_BATCH_MAX)) throw std::invalid_argument("RefineICPBatch: 1..64 starts");
   const bool plane = options.metric == ICPMetric::PointToPlane;
   if (!plane && options.metric != ICPMetric::PointToPoint)
-    throw std::invalid_argument("RefineICPBatch: point-to-point and point-to-plane only (the generalized and coloured metrics have no batch form)");
+    throw std::invalid_argument("RefineICPBatch: point-to-point and point-to-plane only (the generalized, symmetric and coloured metrics have no batch form)");
   if (options.loss != ICPLoss::None) throw std::invalid_argument("RefineICPBatch: robust losses have no batch form");
   if (options.reciprocal || options.normal_angle_deg >= 0) throw std::invalid_argument("RefineICPBatch: pair rejection has no batch form");
   struct Handle {

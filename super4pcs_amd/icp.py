@@ -1,6 +1,6 @@
 """ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
-include/s4p_icp_color.h, include/s4p_icp_reject.h and include/s4p_icp_batch.h (libsuper4pcs_icp.so): point-to-point,
-point-to-plane, generalized (plane-to-plane) and coloured ICP refinement on the full-resolution clouds, with optional robust
+include/s4p_icp_symm.h, include/s4p_icp_color.h, include/s4p_icp_reject.h and include/s4p_icp_batch.h (libsuper4pcs_icp.so):
+point-to-point, point-to-plane, generalized (plane-to-plane), symmetric and coloured ICP refinement on the full-resolution clouds, with optional robust
 losses for the first two, optional correspondence rejection (reciprocal pairs, normal angle) for all of them, and batched
 multi-start refinement (many start poses in one pass, ranked on the full clouds) for the first two.
 
@@ -9,6 +9,7 @@ multi-start refinement (many start poses in one pass, ranked on the full clouds)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="plane")   # target normals estimated on the device
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, loss="trimmed", trim_fraction=0.6)   # trimmed ICP
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="gicp")    # normals of both clouds (given or estimated)
+    T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="symmetric")   # the same normals, a wider basin than "plane"
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="color", target_intensity=rgbP, source_intensity=rgbQ)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, reciprocal=True, normal_angle=60)   # pair rejection, any metric / loss
     T, res, i = icp.refine_best(P, Q, T0s, max_distance=4 * delta)          # up to 64 starts side by side; the best by n_corr, rmse
@@ -34,8 +35,10 @@ STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged", TOO_FE
 ERR_DEGENERATE = -8
 ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE", ERR_DEGENERATE: "DEGENERATE"}
 METRICS = ("point", "plane")
-REFINE_METRICS = METRICS + ("gicp", "color")     # include/s4p_icp_gicp.h, include/s4p_icp_color.h: no robust losses
+REFINE_METRICS = METRICS + ("gicp", "symmetric", "color")   # include/s4p_icp_gicp.h, _symm.h, _color.h: no robust losses
+NORMAL_PAIR_METRICS = ("gicp", "symmetric")      # the metrics on the normals of both clouds
 GICP_NSUMS = PLANE_NSUMS
+SYMM_NSUMS = PLANE_NSUMS
 GICP_EPSILON = 1e-3
 COLOR_NSUMS = PLANE_NSUMS
 COLOR_LAMBDA = 0.968            # S4P_ICP_COLOR_LAMBDA: the weight of the geometric term
@@ -60,6 +63,9 @@ ROBUST_SYMBOLS = [                                         # include/s4p_icp_rob
 GICP_SYMBOLS = [                                           # include/s4p_icp_gicp.h
     "s4p_icp_set_source_normals", "s4p_icp_set_source_normals_device", "s4p_icp_source_normals", "s4p_icp_gicp_sums",
     "s4p_icp_refine_gicp",
+]
+SYMM_SYMBOLS = [                                           # include/s4p_icp_symm.h
+    "s4p_icp_symm_sums", "s4p_icp_solve_symmetric", "s4p_icp_refine_symm",
 ]
 COLOR_SYMBOLS = [                                          # include/s4p_icp_color.h
     "s4p_icp_set_target_intensity", "s4p_icp_set_target_intensity_device", "s4p_icp_set_source_intensity",
@@ -177,6 +183,12 @@ def load_library():
     L.s4p_icp_gicp_sums.argtypes = [vp, fp, C.c_double, dp]
     L.s4p_icp_refine_gicp.restype = C.c_int32
     L.s4p_icp_refine_gicp.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
+    L.s4p_icp_symm_sums.restype = C.c_int32
+    L.s4p_icp_symm_sums.argtypes = [vp, fp, dp]
+    L.s4p_icp_solve_symmetric.restype = C.c_int32
+    L.s4p_icp_solve_symmetric.argtypes = [dp, dp]
+    L.s4p_icp_refine_symm.restype = C.c_int32
+    L.s4p_icp_refine_symm.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
     for name in ("s4p_icp_set_target_intensity", "s4p_icp_set_target_intensity_device", "s4p_icp_set_source_intensity",
                  "s4p_icp_set_source_intensity_device"):
         getattr(L, name).restype = C.c_int32
@@ -235,6 +247,19 @@ def solve_plane(sums):
     rc = L.s4p_icp_solve_plane(_dp(s), _dp(out))
     if rc != 0:
         raise ICPError(rc, "solve_plane: degenerate system" if rc == ERR_DEGENERATE else "solve_plane: bad argument")
+    return out.reshape(4, 4)
+
+
+def solve_symmetric(sums):
+    """The symmetric step on the 31 symmetric sums (host only, no device; include/s4p_icp_symm.h): with A (a, t) = b solved
+    as solve_plane solves it and Rh the rotation by atan |a| about a, dT = [Rh Rh | Rh (cos(atan |a|) t)].  Raises ICPError
+    with code ERR_DEGENERATE where solve_plane does."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, np.float64).reshape(SYMM_NSUMS)
+    out = np.empty(16, np.float64)
+    rc = L.s4p_icp_solve_symmetric(_dp(s), _dp(out))
+    if rc != 0:
+        raise ICPError(rc, "solve_symmetric: degenerate system" if rc == ERR_DEGENERATE else "solve_symmetric: bad argument")
     return out.reshape(4, 4)
 
 
@@ -300,7 +325,7 @@ def _is_torch(t):
 
 def _batch_metric(metric):
     if metric not in METRICS:
-        raise ValueError("a batch refines metric \"point\" or \"plane\" (robust losses, \"gicp\" and \"color\" have no batch form)")
+        raise ValueError("a batch refines metric \"point\" or \"plane\" (robust losses, \"gicp\", \"symmetric\" and \"color\" have no batch form)")
     return METRICS.index(metric)
 
 
@@ -332,7 +357,7 @@ def rank_batch(results):
 def _check_metric(metric, loss):
     if metric not in REFINE_METRICS:
         raise ValueError("metric must be one of %s" % (REFINE_METRICS,))
-    if metric in ("gicp", "color") and loss is not None:
+    if metric in ("gicp", "symmetric", "color") and loss is not None:
         raise ValueError("metric \"%s\" takes no loss (robust losses cover \"point\" and \"plane\")" % metric)
 
 
@@ -476,6 +501,13 @@ class ICP:
         self._chk(self.L.s4p_icp_gicp_sums(self.h, _fp(T), float(epsilon), _dp(out)))
         return out
 
+    def symmetric_sums(self, T):
+        """The 31 symmetric sums for a float T in the centred frame (layout in include/s4p_icp_symm.h)."""
+        T = self._t32(T)
+        out = np.empty(SYMM_NSUMS, np.float64)
+        self._chk(self.L.s4p_icp_symm_sums(self.h, _fp(T), _dp(out)))
+        return out
+
     def _scalars(self, v):
         """(entry-point suffix, pointer, n, keep-alive) of one float per point: numpy, or a torch tensor on the GPU."""
         if _is_torch(v):
@@ -583,7 +615,9 @@ class ICP:
         """(T float64 4x4 in the caller's frame, Result) from the start transform T0 (default identity).  metric "plane"
         minimises point-to-plane distances and needs target normals (set_target_normals or estimate_normals); metric
         "gicp" is generalized ICP (include/s4p_icp_gicp.h) with the covariance parameter gicp_epsilon in [1e-6, 1], needs
-        source normals too (set_source_normals) and takes no loss; metric "color" is coloured ICP
+        source normals too (set_source_normals) and takes no loss; metric "symmetric" is symmetric ICP
+        (include/s4p_icp_symm.h): point-to-plane along the sum of both clouds' normals, the same normals as "gicp", no
+        parameter and no loss; metric "color" is coloured ICP
         (include/s4p_icp_color.h) with the geometric weight color_lambda in [0, 1], needs target normals, both intensities and
         the gradients (estimate_color_gradients) and takes no loss.  loss "trimmed" / "huber" / "tukey" refines on the
         weighted sums (include/s4p_icp_robust.h); loss=None is the plain refine.  info: an optional float64 array of 8 that
@@ -606,6 +640,9 @@ class ICP:
             return T.reshape(4, 4), r
         if metric == "gicp":
             self._chk(self.L.s4p_icp_refine_gicp(self.h, C.byref(p), float(gicp_epsilon), _dp(T), C.byref(r)))
+            return T.reshape(4, 4), r
+        if metric == "symmetric":
+            self._chk(self.L.s4p_icp_refine_symm(self.h, C.byref(p), _dp(T), C.byref(r)))
             return T.reshape(4, 4), r
         if metric == "color":
             self._chk(self.L.s4p_icp_refine_color(self.h, C.byref(p), float(color_lambda), _dp(T), C.byref(r)))
@@ -654,9 +691,9 @@ class ICP:
 def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None,
            source_normals=None, normal_k=16, target_intensity=None, source_intensity=None, color_radius=None,
            reciprocal=False, normal_angle=None, normals_oriented=False, **params):
-    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane", "gicp" and
-    "color": the target normals are target_normals if given, else estimated within normal_radius (default max_distance).  metric
-    "gicp": the source normals (in Q's frame as given) are source_normals if given, else the normal_k-nearest-neighbour
+    """Convenience: one context, target P, source Q, refine from T0.  max_distance is required.  metric "plane", "gicp",
+    "symmetric" and "color": the target normals are target_normals if given, else estimated within normal_radius (default max_distance).  metric
+    "gicp" and "symmetric": the source normals (in Q's frame as given) are source_normals if given, else the normal_k-nearest-neighbour
     normals of Q (super4pcs_amd.normals.estimate_normals).  metric "color": target_intensity and source_intensity are
     required, one value per point as (N,), or rgb in 0..255 as (N, 3), which goes through rgb_to_intensity; the gradients are
     estimated within color_radius (default: the radius of the normals).  reciprocal / normal_angle (degrees) /
@@ -674,19 +711,19 @@ def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_no
         raise ValueError("target_intensity / source_intensity / color_radius need metric \"color\"")
     rej = reject_params(reciprocal, normal_angle, normals_oriented)       # validates before any device work
     by_normals = rej.normal_mode != NORMALS_OFF
-    if (metric == "gicp" or by_normals) and source_normals is None:
+    if (metric in NORMAL_PAIR_METRICS or by_normals) and source_normals is None:
         from super4pcs_amd import normals
         source_normals = normals.estimate_normals(Q, k=normal_k)
     ctx = ICP(device)
     try:
         ctx.set_target(P, max_distance)
         ctx.set_source(Q)
-        if metric in ("plane", "gicp", "color") or by_normals:
+        if metric in ("plane", "gicp", "symmetric", "color") or by_normals:
             if target_normals is not None:
                 ctx.set_target_normals(target_normals)
             else:
                 ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
-        if metric == "gicp" or by_normals:
+        if metric in NORMAL_PAIR_METRICS or by_normals:
             ctx.set_source_normals(source_normals)
         if rej.reciprocal or by_normals:
             ctx._chk(ctx.L.s4p_icp_set_rejection(ctx.h, C.byref(rej)))

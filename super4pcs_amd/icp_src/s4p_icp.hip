@@ -15,6 +15,9 @@
 //                the keys (k_key_hist + k_key_digit x 4, on the device), k_wsum + k_wfinal (weighted sums), host solve.
 //   generalized  (include/s4p_icp_gicp.h) source normals in the order of the source (k_gather_source_normals); per iteration
 //                k_search (winner slot per lane), k_gicp_sum (31 double sums streamed from the slots) + k_final_plane, host solve.
+//   symmetric    (include/s4p_icp_symm.h) the generalized metric's inputs; per iteration k_search, k_symm_sum (31 double sums
+//                streamed from the slots: the plane term along the sum of both normals) + k_final_plane, host solve
+//                (the plane solve's 6x6 path, then the half-way rotation applied twice).
 //   coloured     (include/s4p_icp_color.h) target intensities in cell order (k_gather_target_intensity), their tangent-plane
 //                gradients (k_color_gradient, k_normals' walk), source intensities in the order of the source
 //                (k_gather_source_intensity); per iteration k_search, k_color_sum (31 joint sums) + k_final_plane, host solve.
@@ -37,6 +40,7 @@
 #include "s4p_icp_plane.h"
 #include "s4p_icp_robust.h"
 #include "s4p_icp_gicp.h"
+#include "s4p_icp_symm.h"
 #include "s4p_icp_color.h"
 #include "s4p_icp_reject.h"
 #include "s4p_icp_batch.h"
@@ -47,8 +51,8 @@
 //   s4p_icp_k_build.hip.hpp    kernels outside the iteration: statistics, cell keys and starts, gathers and scatters, the
 //                              source order, the final apply, target normals and colour gradients
 //   s4p_icp_k_pass.hip.hpp     kernels of a pass: the fused k_match / k_match_plane, k_search, k_reject, the selection, the
-//                              weighted / generalized / coloured sums, the final sums, k_reject_out
-//   s4p_icp_solve.inc          host only: Horn's and the plane solve, transform helpers
+//                              weighted / generalized / symmetric / coloured sums, the final sums, k_reject_out
+//   s4p_icp_solve.inc          host only: Horn's, the plane and the symmetric solve, transform helpers
 //   s4p_icp_ctx.inc            owned buffers, the context, ICP_HIP / ICP_LAUNCH, scratch, grid plan and build, set_target / set_source
 //   s4p_icp_pass.inc           prepare, the passes over one search / finish skeleton, the one refine loop
 //   s4p_icp_abi.inc            the extern "C" entry points

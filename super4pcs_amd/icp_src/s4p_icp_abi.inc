@@ -364,6 +364,20 @@ int32_t s4p_icp_refine_gicp(s4p_icp_ctx* h, const s4p_icp_params* params, double
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// symmetric ICP (include/s4p_icp_symm.h)
+
+int32_t s4p_icp_symm_sums(s4p_icp_ctx* h, const float* T16_centred, double* sums) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "symm_sums: null argument");
+  if (int32_t rc = symm_ready(h)) return rc;
+  return sums_call(h, kind_of(kSymm), T16_centred, sums, nullptr);
+}
+
+int32_t s4p_icp_refine_symm(s4p_icp_ctx* h, const s4p_icp_params* params, double* T16_inout, s4p_icp_result* result) {
+  return refine_loop(h, params, kind_of(kSymm), 0, nullptr, T16_inout, result, nullptr, "refine");
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // coloured ICP (include/s4p_icp_color.h)
 
 int32_t s4p_icp_set_target_intensity(s4p_icp_ctx* h, const float* intensity, int64_t n) {

@@ -320,6 +320,12 @@ int32_t gicp_ready(s4p_icp_ctx* h, double epsilon) {
   return S4P_ICP_OK;
 }
 
+int32_t symm_ready(s4p_icp_ctx* h) {
+  if (int32_t rc = plane_ready(h)) return rc;
+  if (!h->has_src_normals) return fail(h, S4P_ICP_ERR_STATE, "source normals first (set_source_normals)");
+  return S4P_ICP_OK;
+}
+
 int32_t color_ready(s4p_icp_ctx* h, double lambda) {
   if (!(lambda >= 0.0 && lambda <= 1.0)) return fail(h, S4P_ICP_ERR_BAD_ARG, "color: lambda must be in [0, 1]");
   if (int32_t rc = plane_ready(h)) return rc;

@@ -1,5 +1,5 @@
 // s4p_icp_k_pass.hip.hpp -- the kernels of a pass: the fused k_match / k_match_plane, and the split passes' k_search,
-// k_reject, the selection (k_key_hist, k_key_digit), the sum kernels (k_wsum, k_gicp_sum, k_color_sum), the final sums and
+// k_reject, the selection (k_key_hist, k_key_digit), the sum kernels (k_wsum, k_gicp_sum, k_symm_sum, k_color_sum), the final sums and
 // k_reject_out.  Every sum kernel ends in block_row and every final sum is slab_total's order (s4p_icp_k_common.hip.hpp).
 //
 // The measured kernels are pinned instruction for instruction ("ICP sources: layout").  What a change here can
@@ -235,6 +235,60 @@ __global__ __launch_bounds__(kBlock) void k_gicp_sum(GicpArgs A) {
     s[26] += qd[2] * g[0] - qd[0] * g[2];
     s[27] += qd[0] * g[1] - qd[1] * g[0];
     s[28] += g[0]; s[29] += g[1]; s[30] += g[2];
+  }
+  block_row<NS, kPlanePitch>(s, A.slab);
+}
+
+struct SymmArgs {
+  Tf T;
+  GridDev g;
+  const float4* src;
+  const float4* snrm;       // the order of src
+  const float4* nrm;        // cell order, as g.tgt
+  uint64_t n;
+  const uint32_t* slot;     // k_search's
+  double* slab;             // one kPlanePitch row per workgroup
+};
+
+// The symmetric sums, term by term as include/s4p_icp_symm.h states them: k_match_plane's shape with n = np +- nh (both
+// normals on one side) and a = (q^ + p') x n.  No search: the winner comes from k_search's slot.
+__global__ __launch_bounds__(kBlock) void k_symm_sum(SymmArgs A) {
+  constexpr int NS = S4P_ICP_PLANE_NSUMS;
+  double s[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = 0.0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t sl = A.slot[j];
+    if (sl == kNoSlot) continue;
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    const float4 p = A.g.tgt[sl];
+    const float d2 = winner_d2(x, y, z, p);
+    s[0] += 1.0;
+    s[1] += double(d2);
+    const float4 nf = A.nrm[sl], mf = A.snrm[j];
+    const double np[3] = {double(nf.x), double(nf.y), double(nf.z)}, mq[3] = {double(mf.x), double(mf.y), double(mf.z)};
+    double nh[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) nh[a] = (double(A.T.m[4 * a]) * mq[0] + double(A.T.m[4 * a + 1]) * mq[1]) + double(A.T.m[4 * a + 2]) * mq[2];
+    const double dot = (np[0] * nh[0] + np[1] * nh[1]) + np[2] * nh[2];
+    const bool flip = dot < 0.0;
+    const double nd[3] = {flip ? np[0] - nh[0] : np[0] + nh[0], flip ? np[1] - nh[1] : np[1] + nh[1], flip ? np[2] - nh[2] : np[2] + nh[2]};
+    if (nd[0] == 0.0 && nd[1] == 0.0 && nd[2] == 0.0) continue;
+    const double u[3] = {double(x), double(y), double(z)}, v[3] = {double(p.x), double(p.y), double(p.z)};
+    const double e[3] = {v[0] - u[0], v[1] - u[1], v[2] - u[2]}, h[3] = {u[0] + v[0], u[1] + v[1], u[2] + v[2]};
+    const double a[6] = {h[1] * nd[2] - h[2] * nd[1], h[2] * nd[0] - h[0] * nd[2], h[0] * nd[1] - h[1] * nd[0], nd[0], nd[1], nd[2]};
+    const double r = (e[0] * nd[0] + e[1] * nd[1]) + e[2] * nd[2];
+    s[2] += 1.0;
+    s[3] += r * r;
+    int o = 4;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int k = i; k < 6; ++k) s[o++] += a[i] * a[k];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s[25 + i] += a[i] * r;
   }
   block_row<NS, kPlanePitch>(s, A.slab);
 }

@@ -1,5 +1,5 @@
 // s4p_icp_pass.inc -- what one call runs on the device and the one refine loop: what a pass needs beforehand (prepare), the
-// five passes over one search / finish skeleton, the source order of a refine, and refine_loop.
+// six passes over one search / finish skeleton, the source order of a refine, and refine_loop.
 
 namespace {
 
@@ -36,13 +36,13 @@ int32_t robust_cfg(s4p_icp_ctx* h, int32_t metric, const s4p_icp_robust* R, Robu
 }
 
 // What a sums call or a refine minimises: the metric, its parameter, and for the robust variants the validated loss.
-enum Metric { kPoint = 0, kPlane = 1, kGicp = 2, kColor = 3 };
+enum Metric { kPoint = 0, kPlane = 1, kGicp = 2, kColor = 3, kSymm = 4 };
 struct PassKind {
   int metric = kPoint;
   double param = 0.0;       // generalized: epsilon; coloured: lambda
   bool robust = false;      // point / plane on the weighted sums of cfg
   RobustCfg cfg;
-  bool plane() const { return metric != kPoint; }                                  // the 31 sums and s4p_icp_solve_plane
+  bool plane() const { return metric != kPoint; }                                  // the 31 sums and their 6x6 solve
   int nsums() const { return plane() ? S4P_ICP_PLANE_NSUMS : S4P_ICP_NSUMS; }
 };
 
@@ -56,13 +56,15 @@ struct PassOut {
 int32_t ready_for(s4p_icp_ctx* h, const PassKind& K) {
   if (K.metric == kGicp) return gicp_ready(h, K.param);
   if (K.metric == kColor) return color_ready(h, K.param);
+  if (K.metric == kSymm) return symm_ready(h);
   return K.plane() ? plane_ready(h) : ready(h);
 }
 
 // the one place the plane slab is allocated
 int32_t plane_slab(s4p_icp_ctx* h) { ICP_HIP(h->pslab.ensure(size_t(kMaxBlocks) * kPlanePitch)); return S4P_ICP_OK; }
 
-// the stored source normals in the order of `src` (w = original source index), for the generalized sums and the normal test
+// the stored source normals in the order of `src` (w = original source index), for the generalized and symmetric sums and
+// the normal test
 int32_t gather_source_normals(s4p_icp_ctx* h, const float4* src) {
   ICP_LAUNCH(k_gather_source_normals, blocks_for(h->n_q), h->sn[0], h->sn[1], h->sn[2], src, uint64_t(h->n_q), h->snrm);
   return S4P_ICP_OK;
@@ -76,7 +78,8 @@ bool weighted(const s4p_icp_ctx* h, const PassKind& K) { return K.robust || (h->
 // (the source normals, gathered once whoever needs them; the source intensities), the rejection's counters and the source
 // grid (reciprocity).  Nothing is built or allocated inside the iteration loop.
 int32_t prepare(s4p_icp_ctx* h, const float4* src, const PassKind* K) {
-  const bool rej = h->rej_on || !K, gicp = K && K->metric == kGicp, color = K && K->metric == kColor;
+  // gicp: a metric that reads the source normals (generalized, symmetric)
+  const bool rej = h->rej_on || !K, gicp = K && (K->metric == kGicp || K->metric == kSymm), color = K && K->metric == kColor;
   const bool nm = rej && h->rej.normal_mode != S4P_ICP_REJECT_NORMALS_OFF;
   if (nm && !h->has_normals) return fail(h, S4P_ICP_ERR_STATE, "rejection by normals: target normals first (set_target_normals or estimate_normals)");
   if (nm && !h->has_src_normals) return fail(h, S4P_ICP_ERR_STATE, "rejection by normals: source normals first (set_source_normals)");
@@ -205,6 +208,17 @@ int32_t gicp_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double epsilon
   return finish_pass(h, h->dsum, h->hsum, S4P_ICP_GICP_NSUMS, out);
 }
 
+// one symmetric pass: the search, the 31 sums streamed from the slots
+int32_t symm_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double* out) {
+  if (int32_t rc = launch_search(h, T, src, false)) return rc;
+  SymmArgs A;
+  A.T = T; A.g = h->g; A.src = src; A.snrm = h->snrm; A.nrm = h->nrm; A.n = uint64_t(h->n_q); A.slot = h->rslot; A.slab = h->pslab;
+  const int nb = blocks_for(h->n_q);
+  ICP_LAUNCH(k_symm_sum, nb, A);
+  ICP_LAUNCH(k_final_plane, 1, h->pslab, nb, h->dsum);
+  return finish_pass(h, h->dsum, h->hsum, S4P_ICP_SYMM_NSUMS, out);
+}
+
 // one colour pass: the search, the 31 joint sums streamed from the slots
 int32_t color_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double lambda, double* out) {
   if (int32_t rc = launch_search(h, T, src, false)) return rc;
@@ -255,6 +269,7 @@ int32_t run_pass(s4p_icp_ctx* h, const PassKind& K, const Tf& T, const float4* s
   }
   if (K.metric == kGicp) rc = gicp_pass(h, T, src, K.param, o.sums);
   else if (K.metric == kColor) rc = color_pass(h, T, src, K.param, o.sums);
+  else if (K.metric == kSymm) rc = symm_pass(h, T, src, o.sums);
   else rc = K.plane() ? plane_pass(h, T, src, o.sums) : pass(h, T, src, nullptr, nullptr, o.sums);
   o.n = o.sums[0];
   return rc;
@@ -292,7 +307,8 @@ int32_t source_for(s4p_icp_ctx* h, const s4p_icp_params& P, const double* T, con
 // The refine loop of every metric.  K.robust unset: K.metric and K.param are the call's.  K.robust set: robust_metric and
 // robust are the caller's, validated here behind the readiness check (as every robust entry point orders them), and `who`
 // names the entry point in the messages.  rmse = sqrt(sum (w) d2 / sum (w)) with sum d2 at [1] (the 31 sums) or [16]; the
-// count n is the pass's; a degenerate s4p_icp_solve_plane stops the loop with T_k.
+// count n is the pass's; a degenerate s4p_icp_solve_plane / s4p_icp_solve_symmetric stops the loop
+// with T_k.
 int32_t refine_loop(s4p_icp_ctx* h, const s4p_icp_params* params, PassKind K, int32_t robust_metric, const s4p_icp_robust* robust,
                     double* T16_inout, s4p_icp_result* result, double* info_out, const char* who) {
   if (!h) return S4P_ICP_ERR_BAD_ARG;
@@ -324,7 +340,8 @@ int32_t refine_loop(s4p_icp_ctx* h, const s4p_icp_params* params, PassKind K, in
     if (k < S4P_ICP_HISTORY) { R.history_rmse[k] = rmse; R.history_n[k] = int64_t(n); R.history_len = k + 1; }
     if (n < double(std::max(P.min_correspondences, 1)) || (K.robust && !plane && !(sw >= 1.0))) { R.status = S4P_ICP_TOO_FEW; break; }
     if (plane) {
-      if (s4p_icp_solve_plane(sums, dT) != S4P_ICP_OK) { R.status = S4P_ICP_DEGENERATE; break; }
+      const int32_t rc = K.metric == kSymm ? s4p_icp_solve_symmetric(sums, dT) : s4p_icp_solve_plane(sums, dT);
+      if (rc != S4P_ICP_OK) { R.status = S4P_ICP_DEGENERATE; break; }
     } else {
       s4p_icp_solve(sums, dT);
     }

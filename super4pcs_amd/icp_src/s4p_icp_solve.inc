@@ -69,6 +69,56 @@ Tf centred_from_float16(const float* T16) {
   return f;
 }
 
+// The 6x6 step of the 31 sums (include/s4p_icp_plane.h's layout), shared by s4p_icp_solve_plane and s4p_icp_solve_symmetric:
+// x = (rotation part, translation part) of A x = b, or S4P_ICP_ERR_DEGENERATE.
+int32_t solve_sums6(const double* sums, double* x) {
+  if (!(sums[2] >= 6.0)) return S4P_ICP_ERR_DEGENERATE;
+  double A[6][6], b[6];
+  for (int u = 0, o = 4; u < 6; ++u)
+    for (int v = u; v < 6; ++v, ++o) A[u][v] = A[v][u] = sums[o];
+  for (int u = 0; u < 6; ++u) b[u] = sums[25 + u];
+  // balance the rotation block (length^2) against the translation block (unitless): the test below is unit-free
+  const double tw = A[0][0] + A[1][1] + A[2][2], tt = A[3][3] + A[4][4] + A[5][5];
+  if (!(tw > 0.0) || !(tt > 0.0) || !std::isfinite(tw) || !std::isfinite(tt)) return S4P_ICP_ERR_DEGENERATE;
+  const double sc = std::sqrt(tt / tw);
+  const double D[6] = {sc, sc, sc, 1.0, 1.0, 1.0};
+  double B[6][6], E[6][6], V[6][6], bb[6];
+  for (int u = 0; u < 6; ++u) {
+    bb[u] = D[u] * b[u];
+    for (int v = 0; v < 6; ++v) B[u][v] = E[u][v] = D[u] * A[u][v] * D[v];
+  }
+  jacobi_sym<6>(E, V);
+  double lmin = E[0][0], lmax = E[0][0];
+  for (int u = 1; u < 6; ++u) { lmin = std::min(lmin, E[u][u]); lmax = std::max(lmax, E[u][u]); }
+  if (!(lmin > 1e-10 * lmax)) return S4P_ICP_ERR_DEGENERATE;
+  // Cholesky B = L L^T, then B y = D b, x = D y
+  double L[6][6] = {};
+  for (int u = 0; u < 6; ++u)
+    for (int v = 0; v <= u; ++v) {
+      double acc = B[u][v];
+      for (int k = 0; k < v; ++k) acc -= L[u][k] * L[v][k];
+      if (u == v) {
+        if (!(acc > 0.0)) return S4P_ICP_ERR_DEGENERATE;
+        L[u][u] = std::sqrt(acc);
+      } else {
+        L[u][v] = acc / L[v][v];
+      }
+    }
+  double y[6];
+  for (int u = 0; u < 6; ++u) {
+    double acc = bb[u];
+    for (int k = 0; k < u; ++k) acc -= L[u][k] * y[k];
+    y[u] = acc / L[u][u];
+  }
+  for (int u = 5; u >= 0; --u) {
+    double acc = y[u];
+    for (int k = u + 1; k < 6; ++k) acc -= L[k][u] * x[k];
+    x[u] = acc / L[u][u];
+  }
+  for (int u = 0; u < 6; ++u) x[u] *= D[u];
+  return S4P_ICP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -108,50 +158,8 @@ int32_t s4p_icp_solve(const double* sums, double* dT16) {
 
 int32_t s4p_icp_solve_plane(const double* sums, double* dT16) {
   if (!sums || !dT16) return S4P_ICP_ERR_BAD_ARG;
-  if (!(sums[2] >= 6.0)) return S4P_ICP_ERR_DEGENERATE;
-  double A[6][6], b[6];
-  for (int u = 0, o = 4; u < 6; ++u)
-    for (int v = u; v < 6; ++v, ++o) A[u][v] = A[v][u] = sums[o];
-  for (int u = 0; u < 6; ++u) b[u] = sums[25 + u];
-  // balance the rotation block (length^2) against the translation block (unitless): the test below is unit-free
-  const double tw = A[0][0] + A[1][1] + A[2][2], tt = A[3][3] + A[4][4] + A[5][5];
-  if (!(tw > 0.0) || !(tt > 0.0) || !std::isfinite(tw) || !std::isfinite(tt)) return S4P_ICP_ERR_DEGENERATE;
-  const double sc = std::sqrt(tt / tw);
-  const double D[6] = {sc, sc, sc, 1.0, 1.0, 1.0};
-  double B[6][6], E[6][6], V[6][6], bb[6];
-  for (int u = 0; u < 6; ++u) {
-    bb[u] = D[u] * b[u];
-    for (int v = 0; v < 6; ++v) B[u][v] = E[u][v] = D[u] * A[u][v] * D[v];
-  }
-  jacobi_sym<6>(E, V);
-  double lmin = E[0][0], lmax = E[0][0];
-  for (int u = 1; u < 6; ++u) { lmin = std::min(lmin, E[u][u]); lmax = std::max(lmax, E[u][u]); }
-  if (!(lmin > 1e-10 * lmax)) return S4P_ICP_ERR_DEGENERATE;
-  // Cholesky B = L L^T, then B y = D b, x = D y
-  double L[6][6] = {};
-  for (int u = 0; u < 6; ++u)
-    for (int v = 0; v <= u; ++v) {
-      double acc = B[u][v];
-      for (int k = 0; k < v; ++k) acc -= L[u][k] * L[v][k];
-      if (u == v) {
-        if (!(acc > 0.0)) return S4P_ICP_ERR_DEGENERATE;
-        L[u][u] = std::sqrt(acc);
-      } else {
-        L[u][v] = acc / L[v][v];
-      }
-    }
-  double y[6], x[6];
-  for (int u = 0; u < 6; ++u) {
-    double acc = bb[u];
-    for (int k = 0; k < u; ++k) acc -= L[u][k] * y[k];
-    y[u] = acc / L[u][u];
-  }
-  for (int u = 5; u >= 0; --u) {
-    double acc = y[u];
-    for (int k = u + 1; k < 6; ++k) acc -= L[k][u] * x[k];
-    x[u] = acc / L[u][u];
-  }
-  for (int u = 0; u < 6; ++u) x[u] *= D[u];
+  double x[6];
+  if (int32_t rc = solve_sums6(sums, x)) return rc;
   // exact rotation of omega (Rodrigues): R = I + sin(th)/th K + (1 - cos(th))/th^2 K^2, K = [omega]x, K^2 = w w^T - th^2 I
   const double w[3] = {x[0], x[1], x[2]};
   const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(th2);
@@ -162,6 +170,29 @@ int32_t s4p_icp_solve_plane(const double* sums, double* dT16) {
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) dT16[4 * r + c] = (r == c ? 1.0 : 0.0) + c1 * K[r][c] + c2 * (w[r] * w[c] - (r == c ? th2 : 0.0));
     dT16[4 * r + 3] = x[3 + r];
+  }
+  dT16[12] = dT16[13] = dT16[14] = 0.0;
+  dT16[15] = 1.0;
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_solve_symmetric(const double* sums, double* dT16) {
+  if (!sums || !dT16) return S4P_ICP_ERR_BAD_ARG;
+  double x[6];
+  if (int32_t rc = solve_sums6(sums, x)) return rc;
+  // Rh: the rotation by atan |a~| about a~ (include/s4p_icp_symm.h); dT = [Rh Rh | Rh t'], t' = c t~
+  const double w[3] = {x[0], x[1], x[2]};
+  const double m2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+  const double c = 1.0 / std::sqrt(1.0 + m2), k = (c * c) / (1.0 + c);
+  const double K[3][3] = {{0.0, -w[2], w[1]}, {w[2], 0.0, -w[0]}, {-w[1], w[0], 0.0}};
+  double Rh[3][3], t[3];
+  for (int r = 0; r < 3; ++r) {
+    for (int s = 0; s < 3; ++s) Rh[r][s] = ((r == s ? 1.0 : 0.0) + c * K[r][s]) + k * (w[r] * w[s] - (r == s ? m2 : 0.0));
+    t[r] = c * x[3 + r];
+  }
+  for (int r = 0; r < 3; ++r) {
+    for (int s = 0; s < 3; ++s) dT16[4 * r + s] = (Rh[r][0] * Rh[0][s] + Rh[r][1] * Rh[1][s]) + Rh[r][2] * Rh[2][s];
+    dT16[4 * r + 3] = (Rh[r][0] * t[0] + Rh[r][1] * t[1]) + Rh[r][2] * t[2];
   }
   dT16[12] = dT16[13] = dT16[14] = 0.0;
   dT16[15] = 1.0;

@@ -87,7 +87,7 @@ def refine_multiscale(P, Q, T0=None, voxel_sizes=(0,), max_distances=None, max_i
         if T0 is not None:
             raise ValueError("give T0 (one start) or starts (several), not both")
         if metric not in _icp.METRICS or params.get("loss") is not None:
-            raise ValueError("starts= needs metric \"point\" or \"plane\" and no loss (robust losses, \"gicp\" and \"color\" have no batch form)")
+            raise ValueError("starts= needs metric \"point\" or \"plane\" and no loss (robust losses, \"gicp\", \"symmetric\" and \"color\" have no batch form)")
         if params.get("reciprocal") or params.get("normal_angle") is not None:
             raise ValueError("starts= takes no pair rejection (the batch has no split pass)")
         starts = _icp._batch_transforms(starts, np.float64)
