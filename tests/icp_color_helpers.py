@@ -166,33 +166,8 @@ def color_sums(Pc, Qc, T, idx, d2, Nc, G, Ip, Iq, lam):
 def cpu_refine_color(cpu, solve_plane, Pc, Qc, Nc, G, Ip, Iq, c, T0, d, lam=LAMBDA, max_iterations=30, rel_tol=1e-6,
                      min_correspondences=3):
     """The refine loop of s4p_icp_refine_color on the CPU restatement: (T caller frame, iterations, status, history)."""
-    from super4pcs_amd import icp
-    T = H.to_centred(np.asarray(T0, np.float64), c)
-    prev, status, its, hist = 0.0, icp.MAX_ITERATIONS, 0, []
-    for k in range(max_iterations):
-        Tf = T.astype(np.float32)
+    def step(Tf):
         idx, d2, _ = cpu.pass_(Pc, Qc, Tf, d)
-        s, _ = color_sums(Pc, Qc, Tf, idx, d2, Nc, G, Ip, Iq, lam)
-        n = s[0]
-        rmse = float(np.sqrt(s[1] / n)) if n > 0 else 0.0
-        hist.append(rmse)
-        if n < max(min_correspondences, 1):
-            status = icp.TOO_FEW
-            break
-        try:
-            dT = solve_plane(s)
-        except icp.ICPError as e:
-            if e.code != icp.ERR_DEGENERATE:
-                raise
-            status = icp.DEGENERATE
-            break
-        T = icp.compose(dT, T)
-        its = k + 1
-        if k + 1 == max_iterations:
-            status = icp.MAX_ITERATIONS
-            break
-        if k > 0 and abs(rmse - prev) <= rel_tol * prev:
-            status = icp.CONVERGED
-            break
-        prev = rmse
-    return H.from_centred(T, c), its, status, hist
+        s = color_sums(Pc, Qc, Tf, idx, d2, Nc, G, Ip, Iq, lam)[0]
+        return s, s[0]
+    return H.refine_loop(step, solve_plane, c, T0, max_iterations, rel_tol, min_correspondences)[:4]

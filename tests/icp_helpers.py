@@ -83,20 +83,55 @@ def from_centred(Tc, c):
     return T
 
 
-def cpu_refine(cpu, solve, Pc, Qc, c, T0, d, max_iterations=30, rel_tol=1e-6, min_correspondences=3, threads=0):
-    """The refine loop of s4p_icp_refine on the CPU restatement: (T caller frame, iterations, status, history)."""
+def motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
+    """4x4: the rotation by angle_deg about axis (Rodrigues) and the translation shift."""
+    a = np.asarray(axis, np.float64); a = a / np.linalg.norm(a)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    th = np.deg2rad(angle_deg)
+    T = np.eye(4); T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K; T[:3, 3] = shift
+    return T
+
+
+def rot_err_deg(A, B):
+    R = A[:3, :3] @ B[:3, :3].T
+    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
+
+
+def raw_normals(rng, n):
+    """Caller normals: not unit length, some zero, one NaN."""
+    raw = rng.normal(size=(n, 3)).astype(np.float32) * 3
+    raw[::11] = 0
+    if n > 5:
+        raw[5, 0] = np.nan
+    return raw
+
+
+def refine_loop(step, solve, c, T0, max_iterations=30, rel_tol=1e-6, min_correspondences=3, robust_point=False):
+    """s4p_icp_pass.inc's refine_loop on the CPU, comparison for comparison, for every metric: step(Tf) -> (sums, n) for the
+    centred transform rounded to float32 (n = sums[0], or info[4] under a robust loss), solve(sums) -> dT or an ICPError
+    with ERR_DEGENERATE.  robust_point: the robust point metric, where a weight sum below 1 is too few as well.
+    (T caller frame, iterations, status, rmse history, count history)."""
     from super4pcs_amd import icp
     T = to_centred(np.asarray(T0, np.float64), c)
-    prev, status, its, hist = 0.0, icp.MAX_ITERATIONS, 0, []
+    prev, status, its, hist, hist_n = 0.0, icp.MAX_ITERATIONS, 0, [], []
     for k in range(max_iterations):
-        _, _, s = cpu.pass_(Pc, Qc, T.astype(np.float32), d, want_idx=False, threads=threads)
-        n = s[0]
-        rmse = float(np.sqrt(s[16] / n)) if n > 0 else 0.0
+        s, n = step(T.astype(np.float32))
+        sw = s[0]                                       # the weight sum of every family
+        i_d2 = 16 if len(s) == 17 else 1                # sum (w) d2: [16] of the 17 point sums, [1] of the 31-sum families
+        rmse = float(np.sqrt(s[i_d2] / sw)) if sw > 0 else 0.0
         hist.append(rmse)
-        if n < max(min_correspondences, 1):
+        hist_n.append(int(n))
+        if n < max(min_correspondences, 1) or (robust_point and not sw >= 1.0):
             status = icp.TOO_FEW
             break
-        T = icp.compose(solve(s), T)
+        try:
+            dT = solve(s)
+        except icp.ICPError as e:
+            if e.code != icp.ERR_DEGENERATE:
+                raise
+            status = icp.DEGENERATE
+            break
+        T = icp.compose(dT, T)
         its = k + 1
         if k + 1 == max_iterations:
             status = icp.MAX_ITERATIONS
@@ -105,4 +140,12 @@ def cpu_refine(cpu, solve, Pc, Qc, c, T0, d, max_iterations=30, rel_tol=1e-6, mi
             status = icp.CONVERGED
             break
         prev = rmse
-    return from_centred(T, c), its, status, hist
+    return from_centred(T, c), its, status, hist, hist_n
+
+
+def cpu_refine(cpu, solve, Pc, Qc, c, T0, d, max_iterations=30, rel_tol=1e-6, min_correspondences=3, threads=0):
+    """The refine loop of s4p_icp_refine on the CPU restatement: (T caller frame, iterations, status, history)."""
+    def step(Tf):
+        s = cpu.pass_(Pc, Qc, Tf, d, want_idx=False, threads=threads)[2]
+        return s, s[0]
+    return refine_loop(step, solve, c, T0, max_iterations, rel_tol, min_correspondences)[:4]

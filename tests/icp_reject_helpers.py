@@ -103,62 +103,20 @@ def sums_abs(Pc, Qc, T, idx, d2, metric, Nc=None, loss=None, n_q=None, d=None, *
 def cpu_refine_reject(cpu, solve, Pc, Qc, c, T0, d, max_iterations=30, rel_tol=1e-6, min_correspondences=3, **rej):
     """The loop of s4p_icp_refine under rejection on the restatement: (T caller frame, iterations, status, rmse history,
     count history)."""
-    from super4pcs_amd import icp
-    T = H.to_centred(np.asarray(T0, np.float64), c)
-    prev, status, its, hist, hist_n = 0.0, icp.MAX_ITERATIONS, 0, [], []
-    for k in range(max_iterations):
-        Tf = T.astype(np.float32)
+    def step(Tf):
         idx, d2, _, _ = restate(cpu_search(cpu), Pc, Qc, Tf, d, **rej)
-        s, _ = RH.robust_sums(Pc, Qc, Tf, idx, d2, "point", "trimmed", len(Qc), d, trim_fraction=1.0)    # every weight 1
-        n = s[0]
-        rmse = float(np.sqrt(s[16] / n)) if n > 0 else 0.0
-        hist.append(rmse); hist_n.append(int(n))
-        if n < max(min_correspondences, 1):
-            status = icp.TOO_FEW
-            break
-        T = icp.compose(solve(s), T)
-        its = k + 1
-        if k + 1 == max_iterations:
-            status = icp.MAX_ITERATIONS
-            break
-        if k > 0 and abs(rmse - prev) <= rel_tol * prev:
-            status = icp.CONVERGED
-            break
-        prev = rmse
-    return H.from_centred(T, c), its, status, hist, hist_n
+        s = RH.robust_sums(Pc, Qc, Tf, idx, d2, "point", "trimmed", len(Qc), d, trim_fraction=1.0)[0]    # every weight 1
+        return s, s[0]
+    return H.refine_loop(step, solve, c, T0, max_iterations, rel_tol, min_correspondences)
 
 
 def cpu_refine_gicp_reject(cpu, solve_plane, Pc, Qc, Np, Nq, c, T0, d, eps=1e-3, max_iterations=30, rel_tol=1e-6, min_correspondences=3,
                            **rej):
-    """The loop of s4p_icp_refine_gicp under rejection on the restatement (tests/icp_gicp_helpers.py's loop on the kept pairs)."""
-    from super4pcs_amd import icp
+    """The loop of s4p_icp_refine_gicp under rejection on the restatement (tests/icp_gicp_helpers.py's sums on the kept pairs)."""
     from tests import icp_gicp_helpers as GH
-    T = H.to_centred(np.asarray(T0, np.float64), c)
-    prev, status, its, hist, hist_n = 0.0, icp.MAX_ITERATIONS, 0, [], []
-    for k in range(max_iterations):
-        Tf = T.astype(np.float32)
+
+    def step(Tf):
         idx, d2, _, _ = restate(cpu_search(cpu), Pc, Qc, Tf, d, Np=Np, Nq=Nq, **rej)
-        s, _ = GH.gicp_sums(Pc, Qc, Tf, idx, d2, Np, Nq, eps)
-        n = s[0]
-        rmse = float(np.sqrt(s[1] / n)) if n > 0 else 0.0
-        hist.append(rmse); hist_n.append(int(n))
-        if n < max(min_correspondences, 1):
-            status = icp.TOO_FEW
-            break
-        try:
-            dT = solve_plane(s)
-        except icp.ICPError as e:
-            if e.code != icp.ERR_DEGENERATE:
-                raise
-            status = icp.DEGENERATE
-            break
-        T = icp.compose(dT, T)
-        its = k + 1
-        if k + 1 == max_iterations:
-            status = icp.MAX_ITERATIONS
-            break
-        if k > 0 and abs(rmse - prev) <= rel_tol * prev:
-            status = icp.CONVERGED
-            break
-        prev = rmse
-    return H.from_centred(T, c), its, status, hist, hist_n
+        s = GH.gicp_sums(Pc, Qc, Tf, idx, d2, Np, Nq, eps)[0]
+        return s, s[0]
+    return H.refine_loop(step, solve_plane, c, T0, max_iterations, rel_tol, min_correspondences)

@@ -100,49 +100,15 @@ def robust_sums(Pc, Qc, T, idx, d2, metric, loss, n_q, d, Nc=None, trim_fraction
 def cpu_refine_robust(cpu, solve, solve_plane, Pc, Qc, c, T0, d, metric, loss, Nc=None, trim_fraction=None, scale=None,
                       max_iterations=30, rel_tol=1e-6, min_correspondences=3):
     """The loop of s4p_icp_refine_robust on the restatement: (T caller frame, iterations, status, rmse history, count history)."""
-    from super4pcs_amd import icp
-    T = H.to_centred(np.asarray(T0, np.float64), c)
-    i_d2 = 1 if metric == "plane" else 16
-    prev, status, its, hist, hist_n = 0.0, icp.MAX_ITERATIONS, 0, [], []
-    for k in range(max_iterations):
-        Tf = T.astype(np.float32)
+    def step(Tf):
         idx, d2, _ = cpu.pass_(Pc, Qc, Tf, d)
         s, info = robust_sums(Pc, Qc, Tf, idx, d2, metric, loss, len(Qc), d, Nc, trim_fraction, scale)
-        n, sw = info[4], s[0]
-        rmse = float(np.sqrt(s[i_d2] / sw)) if sw > 0 else 0.0
-        hist.append(rmse)
-        hist_n.append(int(n))
-        if n < max(min_correspondences, 1) or (metric == "point" and not sw >= 1.0):
-            status = icp.TOO_FEW
-            break
-        if metric == "plane":
-            try:
-                dT = solve_plane(s)
-            except icp.ICPError as e:
-                if e.code != icp.ERR_DEGENERATE:
-                    raise
-                status = icp.DEGENERATE
-                break
-        else:
-            dT = solve(s)
-        T = icp.compose(dT, T)
-        its = k + 1
-        if k + 1 == max_iterations:
-            status = icp.MAX_ITERATIONS
-            break
-        if k > 0 and abs(rmse - prev) <= rel_tol * prev:
-            status = icp.CONVERGED
-            break
-        prev = rmse
-    return H.from_centred(T, c), its, status, hist, hist_n
+        return s, info[4]
+    return H.refine_loop(step, solve_plane if metric == "plane" else solve, c, T0, max_iterations, rel_tol, min_correspondences,
+                         robust_point=metric == "point")
 
 
-def motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
-    a = np.asarray(axis, np.float64); a /= np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(angle_deg)
-    T = np.eye(4); T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K; T[:3, 3] = shift
-    return T
+motion = H.motion
 
 
 def outlier_scene(P, N, d, n_in=60_000, n_out=40_000, seed=31):

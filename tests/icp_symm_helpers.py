@@ -96,57 +96,25 @@ def solve_symmetric_numpy(s):
     return dT
 
 
-def cpu_refine(pass_, sums_fn, solve, Pc, Qc, c, T0, d, max_iterations=30, rel_tol=1e-6, min_correspondences=3):
-    """refine_loop on the CPU: pass_(Pc, Qc, Tf, d) -> (idx, d2, ...), sums_fn(Tf, idx, d2) -> the 31 sums, solve(sums) ->
-    dT or an ICPError with ERR_DEGENERATE.  (T caller frame, iterations, status, rmse history)."""
-    from super4pcs_amd import icp
-    T = H.to_centred(np.asarray(T0, np.float64), c)
-    prev, status, its, hist = 0.0, icp.MAX_ITERATIONS, 0, []
-    for k in range(max_iterations):
-        Tf = T.astype(np.float32)
-        idx, d2 = pass_(Pc, Qc, Tf, d)[:2]
-        s = sums_fn(Tf, idx, d2)
-        n = s[0]
-        rmse = float(np.sqrt(s[1] / n)) if n > 0 else 0.0
-        hist.append(rmse)
-        if n < max(min_correspondences, 1):
-            status = icp.TOO_FEW
-            break
-        try:
-            dT = solve(s)
-        except icp.ICPError as e:
-            if e.code != icp.ERR_DEGENERATE:
-                raise
-            status = icp.DEGENERATE
-            break
-        T = icp.compose(dT, T)
-        its = k + 1
-        if k + 1 == max_iterations:
-            status = icp.MAX_ITERATIONS
-            break
-        if k > 0 and abs(rmse - prev) <= rel_tol * prev:
-            status = icp.CONVERGED
-            break
-        prev = rmse
-    return H.from_centred(T, c), its, status, hist
-
-
 def cpu_refine_symm(cpu, solve_symmetric, Pc, Qc, Np, Nq, c, T0, d, **kw):
-    """The refine loop of s4p_icp_refine_symm on the CPU restatement."""
-    return cpu_refine(cpu.pass_, lambda Tf, idx, d2: symm_sums(Pc, Qc, Tf, idx, d2, Np, Nq)[0], solve_symmetric, Pc, Qc, c, T0, d, **kw)
+    """The refine loop of s4p_icp_refine_symm on the CPU restatement: (T caller frame, iterations, status, history)."""
+    def step(Tf):
+        idx, d2, _ = cpu.pass_(Pc, Qc, Tf, d)
+        s = symm_sums(Pc, Qc, Tf, idx, d2, Np, Nq)[0]
+        return s, s[0]
+    return H.refine_loop(step, solve_symmetric, c, T0, **kw)[:4]
 
 
 def cpu_refine_plane(cpu, solve_plane, Pc, Qc, Np, c, T0, d, **kw):
     """The refine loop of s4p_icp_refine_plane on the same restatement (for iteration counts, not for bits)."""
-    return cpu_refine(cpu.pass_, lambda Tf, idx, d2: plane_sums(Pc, Qc, Tf, idx, d2, Np), solve_plane, Pc, Qc, c, T0, d, **kw)
+    def step(Tf):
+        idx, d2, _ = cpu.pass_(Pc, Qc, Tf, d)
+        s = plane_sums(Pc, Qc, Tf, idx, d2, Np)
+        return s, s[0]
+    return H.refine_loop(step, solve_plane, c, T0, **kw)[:4]
 
 
-def motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
-    a = np.asarray(axis, np.float64); a = a / np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(angle_deg)
-    T = np.eye(4); T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K; T[:3, 3] = shift
-    return T
+motion = H.motion
 
 
 def analytic_pair(n_p=6000, n_q=2500, seed=1):

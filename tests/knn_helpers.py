@@ -4,18 +4,17 @@ numpy float32 in the contract's order, lists without self as the first k of (the
 neighbour distances in double in ascending order, and the clouds the tests share."""
 import math
 import os
-import subprocess
 
 import numpy as np
 
+from tests import apps
 from tests import normals_helpers as NH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -52
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+bits = NH.bits
 
 
 def d2_of(X, Q, idx):
@@ -124,21 +123,9 @@ def tiny_radius(n):
     return np.float32(0.5 * n ** (-1.0 / 3.0))
 
 
-def write_obj(path, pts, faces=()):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        for t in faces:
-            f.write("f %d %d %d\n" % tuple(t))
-        f.write("# End of File\n")
+write_obj = apps.write_obj
 
 
 def build_app(outdir, extra=()):
     """tests/knn_app/main.cpp against the facade header and libsuper4pcs_normals.so."""
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = os.path.join(str(outdir), "knn_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + list(extra) +
-                          [os.path.join(ROOT, "tests", "knn_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_normals",
-                           "-Wl,-rpath," + libdir, "-o", exe])
-    return exe
+    return apps.build_app(outdir, "knn_app", ("super4pcs_normals",), ("-Werror",) + tuple(extra))

@@ -2,6 +2,8 @@
 lidar pair of the basin test, start poses and the pose error."""
 import numpy as np
 
+from tests import apps
+
 
 def rot_about(axis, deg, centre):
     """4x4: a rotation by deg degrees about the axis through centre."""
@@ -61,22 +63,10 @@ def basin_start(T_gt, Q, deg):
 
 def build_app(outdir, extra=()):
     """tests/icp_multiscale_app/main.cpp against the facade headers, libsuper4pcs_icp.so and libsuper4pcs_normals.so."""
-    import os
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    libdir = os.path.join(root, "super4pcs_amd", "lib")
-    exe = os.path.join(str(outdir), "icp_multiscale_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(root, "include")] + list(extra) +
-                          [os.path.join(root, "tests", "icp_multiscale_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_icp",
-                           "-lsuper4pcs_normals", "-ldl", "-Wl,-rpath," + libdir, "-o", exe])
-    return exe
+    return apps.build_app(outdir, "icp_multiscale_app", ("super4pcs_icp", "super4pcs_normals", "dl"), ("-Werror",) + tuple(extra))
 
 
-def move(T32, X):
-    """float32 (n, 3): X moved by the float matrix in the facade's order, ((m0 * x + m1 * y) + m2 * z) + m3."""
-    T32 = np.asarray(T32, np.float32); X = np.asarray(X, np.float32)
-    x, y, z = X[:, 0], X[:, 1], X[:, 2]
-    return np.stack([((T32[k, 0] * x + T32[k, 1] * y) + T32[k, 2] * z) + T32[k, 3] for k in range(3)], 1).astype(np.float32)
+move = apps.move_f32
 
 
 def facade_chain(icp, voxel, P, Q, T0, levels, **kw):

@@ -22,6 +22,10 @@ def build_cpu(outdir):
     return CPU(L)
 
 
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
 def _cols(X):
     return [np.ascontiguousarray(np.asarray(X)[:, a], np.float32) for a in range(3)]
 

@@ -7,6 +7,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests import apps
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
@@ -16,13 +18,6 @@ def cli(s4p_lib_built):
     from super4pcs_amd import build as B
     return B.build_cli()
 
-
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
 
 
 def test_cli_usage_and_exit_codes(cli, tmp_path):
@@ -43,8 +38,8 @@ def test_cli_without_a_gpu_fails_loudly(cli, tmp_path):
     if torch.cuda.is_available():
         pytest.skip("a GPU is visible")
     pts = np.random.default_rng(0).normal(size=(50, 3)).astype(np.float32)
-    _write_obj(tmp_path / "a.obj", pts)
-    _write_obj(tmp_path / "b.obj", pts)
+    apps.write_obj(tmp_path / "a.obj", pts)
+    apps.write_obj(tmp_path / "b.obj", pts)
     r = subprocess.run([cli, "-i", str(tmp_path / "a.obj"), str(tmp_path / "b.obj"), "-r", str(tmp_path / "o.obj")],
                        capture_output=True, text=True)
     assert r.returncode == 254 and "no CPU fallback" in r.stderr          # the exception path, :147-151
@@ -56,8 +51,8 @@ def test_cli_registers_config1_like_the_reference(cli, tmp_path):
     """hippo1 <-> hippo2 with the flags of scripts/run-example.sh:68, through files.  The fixture holds the two clouds
     after the sampler (sampling them again at the same delta keeps every point) and the reference's own result."""
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
-    _write_obj(tmp_path / "P.obj", g["Ps"])
-    _write_obj(tmp_path / "Q.obj", g["Qu"])
+    apps.write_obj(tmp_path / "P.obj", g["Ps"])
+    apps.write_obj(tmp_path / "Q.obj", g["Qu"])
     r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", "0.7", "-d", "0.01", "-t", "1000",
                         "-n", "200", "-r", str(tmp_path / "out.obj"), "-m", str(tmp_path / "mat.txt"),
                         "--sampled1", str(tmp_path / "s1.ply"), "--sampled2", str(tmp_path / "s2.ply")],

@@ -5,16 +5,13 @@ import subprocess
 
 import pytest
 
+from tests import apps
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _build(tmp_path, s4p_lib_built):
-    exe = str(tmp_path / "facade_app")
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "facade_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-Wl,-rpath," + libdir, "-o", exe])
-    return exe
+    return apps.build_app(tmp_path, "facade_app", ("super4pcs_amd",))
 
 
 def test_facade_compiles_and_fails_loudly_without_gpu(tmp_path, s4p_lib_built):

@@ -8,16 +8,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import apps
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
 
 
 def _matrix(path):
@@ -32,7 +27,7 @@ def test_icp_starts_runs_and_keeps_at_least_the_single_refinements_correspondenc
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
     base = [cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000", "-n", str(n_s),
             "--icp", "10"]
     one = subprocess.run(base + ["-m", str(tmp_path / "one.txt")], capture_output=True, text=True, timeout=300)

@@ -2,12 +2,12 @@
 (tests/icp_cpu/icp_cpu.cpp), sums, determinism, convergence to an exact pose, the refine trajectory against the CPU loop,
 refinement after a registration on the full clouds, and the facade / command line / torch entry points."""
 import os
-import subprocess
 import time
 
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import icp_helpers as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,19 +41,6 @@ def lidar():
     return P, Q, T
 
 
-def _motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
-    a = np.asarray(axis, np.float64); a /= np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(angle_deg)
-    T = np.eye(4); T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K; T[:3, 3] = shift
-    return T
-
-
-def _rot_err_deg(A, B):
-    R = A[:3, :3] @ B[:3, :3].T
-    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
-
-
 def _check_pass(ctx, cpu, P, Q, T_caller, d):
     c = ctx.frame()
     Pc, Qc = (P - c).astype(np.float32), (Q - c).astype(np.float32)
@@ -80,7 +67,7 @@ def test_correspondences_and_sums_are_the_contract(icp, cpu, bumpy, lidar):
         ctx.set_target(P, d)
         ctx.set_source(Q)
         for k, (ang, sh) in enumerate(((0.0, 0.0), (0.3, 0.002), (-1.0, 0.01), (2.0, -0.02))):
-            n = _check_pass(ctx, cpu, P, Q, _motion(ang, sh) @ T_gt, d)
+            n = _check_pass(ctx, cpu, P, Q, H.motion(ang, sh) @ T_gt, d)
             assert n > 1000, (k, n)
         ctx.close()
 
@@ -114,7 +101,7 @@ def test_refine_is_deterministic_and_converges_to_an_exact_pose(icp, bumpy):
     rng = np.random.default_rng(5)
     sub = P[np.sort(rng.choice(len(P), 100_000, replace=False))].astype(np.float64)
     extent = float(np.linalg.norm(P.max(0) - P.min(0)))
-    M = _motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
+    M = H.motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
     Q = (sub @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
     T_true = np.linalg.inv(M)
     ctx = icp.ICP(0)
@@ -134,7 +121,7 @@ def test_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
     """5: the CPU restatement plus s4p_icp_solve, from a start 1.5 degrees off the generator's pose."""
     P, Q, T_gt = bumpy
     d = 4 * 0.004
-    T0 = _motion(1.5, 0.004) @ T_gt
+    T0 = H.motion(1.5, 0.004) @ T_gt
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Q)
@@ -172,27 +159,15 @@ def test_refinement_after_registration_is_closer_to_the_generator(icp, which, li
     dT, r = icp.refine(P, Qm, np.eye(4), max_distance=4 * delta)
     secs = time.perf_counter() - t0
     Mr = icp.compose(dT, M)
-    e0 = (_rot_err_deg(M, T_gt), float(np.linalg.norm(M[:3, 3] - T_gt[:3, 3])))
-    e1 = (_rot_err_deg(Mr, T_gt), float(np.linalg.norm(Mr[:3, 3] - T_gt[:3, 3])))
+    e0 = (H.rot_err_deg(M, T_gt), float(np.linalg.norm(M[:3, 3] - T_gt[:3, 3])))
+    e1 = (H.rot_err_deg(Mr, T_gt), float(np.linalg.norm(Mr[:3, 3] - T_gt[:3, 3])))
     print("%s: n_P %d n_Q %d  Super4PCS rot %.4g deg trans %.4g -> ICP rot %.4g deg trans %.4g (%d its, %s, rmse %.4g, fitness %.3f, %.3f s)"
           % (which, len(P), len(Q), e0[0], e0[1], e1[0], e1[1], r.iterations, icp.STATUS_NAMES[r.status], r.rmse, r.fitness, secs))
     assert e1[0] < e0[0] and e1[1] < e0[1]
 
 
-def _write_xyz(path, pts):
-    np.savetxt(path, pts, fmt="%.9g")
-
-
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
-
 def test_facade_cli_and_torch_agree_with_the_python_binding(icp, tmp_path, s4p_lib_built):
-    """7: the hippo fixture through MatchSuper4PCS + RefineICP (tests/icp_app), through `Super4PCS ... --icp 30 -m`, and
+    """7: the hippo fixture through MatchSuper4PCS + RefineICP (tests/icp_facade_app), through `Super4PCS ... --icp 30 -m`, and
     through icp.py from the same Super4PCS result; then torch device tensors against numpy input."""
     import torch
     from super4pcs_amd import build as B
@@ -200,22 +175,12 @@ def test_facade_cli_and_torch_agree_with_the_python_binding(icp, tmp_path, s4p_l
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
     # facade application: MatchSuper4PCS + RefineICP
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd", "-lsuper4pcs_icp",
-                           "-Wl,-rpath," + libdir, "-o", exe])
-    _write_xyz(tmp_path / "P.xyz", Ps); _write_xyz(tmp_path / "Q.xyz", Qu)
-    out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s)],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    rows = {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-            for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
+    rows, _ = apps.run_icp_app(exe, Ps, Qu, delta, overlap, n_s)
     # icp.py from the same Super4PCS result: Q moved by it in k_apply's order
     M = rows["registered"].astype(np.float64)
     Mf = rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     ctx = icp.ICP(0)
     ctx.set_target(Ps, np.float32(4.0 * delta))
     ctx.set_source(Qm)
@@ -227,14 +192,9 @@ def test_facade_cli_and_torch_agree_with_the_python_binding(icp, tmp_path, s4p_l
     assert np.max(np.abs(rows["refined"] - Mf)) > 0               # the refinement moved the pose
     # command line
     cli = B.build_cli()
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
-    rc = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-                         "-n", str(n_s), "--icp", "30", "-m", str(tmp_path / "mat.txt")], capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    assert "ICP: " in rc.stdout + rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    assert lines[:2] == ["VERSION\t=\t1", "MATRIX\t="]
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
+    got, said = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s, ["--icp", "30"])
+    assert "ICP: " in said
     assert np.max(np.abs(got - want)) <= 2e-6
     # torch device tensors: the same bits as numpy input
     dev = torch.device("cuda:0")
@@ -246,7 +206,5 @@ def test_facade_cli_and_torch_agree_with_the_python_binding(icp, tmp_path, s4p_l
     assert np.array_equal(ctx2.frame(), ctx.frame())
     # apply: k_apply's rounding order
     Qa = ctx.apply(dT, Qm)
-    Tf = dT.astype(np.float32)
-    x, y, z = Qm[:, 0], Qm[:, 1], Qm[:, 2]
-    exp = np.stack([((Tf[k, 0] * x + Tf[k, 1] * y) + Tf[k, 2] * z) + Tf[k, 3] for k in range(3)], 1)
+    exp = apps.move_f32(dT.astype(np.float32), Qm)
     assert np.array_equal(Qa, exp)

@@ -2,12 +2,12 @@
 (tests/icp_color_helpers.py), state and argument errors, determinism, the trajectory against the CPU loop, the planar
 textured case the metric exists for, the facade / command line / Python binding agreeing, and edge sizes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import icp_color_helpers as CH
+from tests import apps
 from tests import icp_helpers as H
 from tests import icp_plane_helpers as PH
 
@@ -42,30 +42,11 @@ def lidar():
     return D.lidar_pair_scaled(0.02, delta=0.05)
 
 
-def _motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
-    T = np.eye(4); T[:3, :3] = CH.rot(axis, angle_deg); T[:3, 3] = shift
-    return T
-
-
-def _rot_err_deg(A, B):
-    R = A[:3, :3] @ B[:3, :3].T
-    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
-
-
 def _textured(pair, scale):
     """(P, Q, T_gt, Ip, Iq): texture() on P, and on Q where the generator's pose puts it, so both clouds carry one field."""
     P, Q, T_gt = pair
     Qm = Q.astype(np.float64) @ T_gt[:3, :3].T + T_gt[:3, 3]
     return P, Q, T_gt, CH.texture(P, scale), CH.texture(Qm, scale)
-
-
-def _raw_normals(rng, n):
-    """Caller normals: not unit length, some zero, one NaN."""
-    raw = rng.normal(size=(n, 3)).astype(np.float32) * 3
-    raw[::11] = 0
-    if n > 5:
-        raw[5, 0] = np.nan
-    return raw
 
 
 def _check_gradients(ctx, P, Np, Ip, r, min_nb, what, which=None):
@@ -183,13 +164,13 @@ def test_color_sums_are_the_contract(icp, cpu, bumpy, lidar):
         ctx.set_source(Q)
         ctx.set_source_intensity(Iq)
         ctx.set_target_intensity(Ip)
-        ctx.set_target_normals(_raw_normals(rng, len(P)))
+        ctx.set_target_normals(H.raw_normals(rng, len(P)))
         Np = ctx.target_normals()
         ctx.estimate_color_gradients(d / 2, MIN_NB)
         G = ctx.target_color_gradients()
         assert not G[::11].any() and G.any(1).sum() > 0.5 * len(P)
         for ang, sh in ((0.0, 0.0), (0.3, 0.002), (-1.0, 0.01)):
-            n, nt = _check_color_sums(ctx, cpu, P, Q, Np, G, Ip, Iq, _motion(ang, sh) @ T_gt, d)
+            n, nt = _check_color_sums(ctx, cpu, P, Q, Np, G, Ip, Iq, H.motion(ang, sh) @ T_gt, d)
             assert n > 1000 and 0.8 * n < nt < n
         ctx.estimate_normals(d, MIN_NB)
         Ne = ctx.target_normals()
@@ -198,7 +179,7 @@ def test_color_sums_are_the_contract(icp, cpu, bumpy, lidar):
         slab = Ip == np.float32(0.25)
         assert slab.sum() > 1000 and (~G[slab & Ne.any(1)].any(1)).sum() > 100         # exactly zero inside the stretch
         for ang, sh in ((0.0, 0.0), (0.5, -0.004), (2.0, -0.02)):
-            n, nt = _check_color_sums(ctx, cpu, P, Q, Ne, G, Ip, Iq, _motion(ang, sh) @ T_gt, d)
+            n, nt = _check_color_sums(ctx, cpu, P, Q, Ne, G, Ip, Iq, H.motion(ang, sh) @ T_gt, d)
             assert n > 1000
         ctx.close()
 
@@ -292,7 +273,7 @@ def _subset_setup(icp, bumpy):
     pick = np.sort(rng.choice(len(P), 100_000, replace=False))
     d = 4 * 0.004
     Ip = CH.texture(P, 4.0)
-    M = _motion(0.5, np.array([0.0012, -0.0016, 0.0]))
+    M = H.motion(0.5, np.array([0.0012, -0.0016, 0.0]))
     Q = (P[pick].astype(np.float64) @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
     return P, Q, Ip, Ip[pick].copy(), np.linalg.inv(M), d
 
@@ -302,7 +283,7 @@ def test_color_is_deterministic_and_torch_agrees(icp, bumpy):
     order_source on and off see the same correspondences."""
     import torch
     P, Q, Ip, Iq, T_true, d = _subset_setup(icp, bumpy)
-    T0 = _motion(0.3, 0.001) @ T_true
+    T0 = H.motion(0.3, 0.001) @ T_true
     ctx = icp.ICP(0)
     ctx.set_target(P, d); ctx.set_source(Q)
     ctx.estimate_normals(d)
@@ -341,7 +322,7 @@ def test_color_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
     off the generator's pose; estimated target normals, gradients within half the search distance."""
     P, Q, T_gt, Ip, Iq = _textured(bumpy, 4.0)
     d = 4 * 0.004
-    T0 = _motion(1.5, 0.004) @ T_gt
+    T0 = H.motion(1.5, 0.004) @ T_gt
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Q)
@@ -354,7 +335,7 @@ def test_color_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
                                                 ctx.target_normals(), ctx.target_color_gradients(), Ip, Iq, c, T0, d)
     print("color trajectory: gpu %d its (%s) rmse %.6g; cpu %d its (%s) |dT| %.2g; rot err %.4g -> %.4g deg"
           % (r.iterations, icp.STATUS_NAMES[r.status], r.rmse, its, icp.STATUS_NAMES[status], np.max(np.abs(T - Tc)),
-             _rot_err_deg(T0, T_gt), _rot_err_deg(T, T_gt)))
+             H.rot_err_deg(T0, T_gt), H.rot_err_deg(T, T_gt)))
     assert np.max(np.abs(T - Tc)) <= 1e-5
     assert abs(r.iterations - its) <= 1
     k = min(r.history_len, len(hist), 3)
@@ -402,7 +383,7 @@ def _write_ply(path, pts, grey):
 
 
 def test_facade_cli_and_binding_agree_on_the_textured_hippo(icp, tmp_path, s4p_lib_built):
-    """7: the hippo fixture with a grey texture through MatchSuper4PCS + RefineICP(Colored) (tests/icp_color_app), through
+    """7: the hippo fixture with a grey texture through MatchSuper4PCS + RefineICP(Colored) (tests/icp_facade_app), through
     `Super4PCS ... --icp 30 --icp-metric color -m` on coloured PLY files, and through icp.refine with rgb input from the same
     Super4PCS result; then what the facade rejects."""
     import torch
@@ -413,24 +394,11 @@ def test_facade_cli_and_binding_agree_on_the_textured_hippo(icp, tmp_path, s4p_l
     grey_q = np.rint(255 * CH.texture(Qu.astype(np.float64) @ Mg[:3, :3].T + Mg[:3, 3], 3.0)).astype(np.int64)
     rgb_p, rgb_q = np.repeat(grey_p[:, None], 3, 1), np.repeat(grey_q[:, None], 3, 1)
     delta, overlap, n_s = 0.01, 0.7, 200
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_color_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_color_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
-
-    def app(p_rows, q_rows, extra=()):
-        np.savetxt(tmp_path / "P.xyz", p_rows, fmt="%.9g"); np.savetxt(tmp_path / "Q.xyz", q_rows, fmt="%.9g")
-        return subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s)] + list(extra),
-                              capture_output=True, text=True, timeout=300)
-
-    out = app(np.column_stack([Ps, rgb_p]), np.column_stack([Qu, rgb_q]))
-    assert out.returncode == 0, out.stdout + out.stderr
-    rows = {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-            for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
+    flags = ("--metric", "color", "--rgb")
+    rows, _ = apps.run_icp_app(exe, np.column_stack([Ps, rgb_p]), np.column_stack([Qu, rgb_q]), delta, overlap, n_s, *flags)
     M, Mf = rows["registered"].astype(np.float64), rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     dT, r = icp.refine(Ps, Qm, np.eye(4), max_distance=np.float32(4.0 * delta), metric="color", target_intensity=rgb_p,
                        source_intensity=rgb_q)
     want = icp.compose(dT, M).astype(np.float32)
@@ -449,23 +417,14 @@ def test_facade_cli_and_binding_agree_on_the_textured_hippo(icp, tmp_path, s4p_l
     # command line
     cli = B.build_cli()
     _write_ply(tmp_path / "P.ply", Ps, grey_p); _write_ply(tmp_path / "Q.ply", Qu, grey_q)
-    rc = subprocess.run([cli, "-i", str(tmp_path / "P.ply"), str(tmp_path / "Q.ply"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-                         "-n", str(n_s), "--icp", "30", "--icp-metric", "color", "-m", str(tmp_path / "mat.txt")],
-                        capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    got, _ = apps.run_cli(cli, tmp_path / "P.ply", tmp_path / "Q.ply", delta, overlap, n_s, ["--icp", "30", "--icp-metric", "color"])
     assert np.max(np.abs(got - want)) <= 2e-6
     # the facade rejects a cloud with a point that has no colour, and a loss
-    q_rows = np.column_stack([Qu, rgb_q]).astype(np.float64)
-    np.savetxt(tmp_path / "P.xyz", np.column_stack([Ps, rgb_p]), fmt="%.9g")
-    with open(tmp_path / "Q.xyz", "w") as f:
-        for k, row in enumerate(q_rows):
-            f.write(" ".join("%.9g" % v for v in (row[:3] if k == 7 else row)) + "\n")
-    out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s)],
-                         capture_output=True, text=True, timeout=300)
+    q_rows = [row[:3] if k == 7 else row for k, row in enumerate(np.column_stack([Qu, rgb_q]))]
+    out = apps.start_icp_app(exe, np.column_stack([Ps, rgb_p]), q_rows, delta, overlap, n_s, *flags)
     assert out.returncode == 5 and "invalid:" in out.stdout and "colour" in out.stdout, out.stdout + out.stderr
-    out = app(np.column_stack([Ps, rgb_p]), np.column_stack([Qu, rgb_q]), extra=("0.968", "huber"))
+    out = apps.start_icp_app(exe, np.column_stack([Ps, rgb_p]), np.column_stack([Qu, rgb_q]), delta, overlap, n_s, *flags,
+                             "--color-lambda", "0.968", "--loss", "huber")
     assert out.returncode == 5 and "invalid:" in out.stdout and "loss" in out.stdout, out.stdout + out.stderr
 
 
@@ -474,7 +433,7 @@ def first_hit(cpu, bumpy):
     """The first source point of the bumpy pair with a correspondence at the edge test's transform (CPU restatement)."""
     P, Q, T_gt = bumpy
     c = P.astype(np.float64).mean(0).astype(np.float32)
-    idx, _, _ = cpu.pass_((P - c).astype(np.float32), (Q - c).astype(np.float32), H.to_centred(_motion(0.3, 0.002) @ T_gt, c).astype(np.float32),
+    idx, _, _ = cpu.pass_((P - c).astype(np.float32), (Q - c).astype(np.float32), H.to_centred(H.motion(0.3, 0.002) @ T_gt, c).astype(np.float32),
                           4 * 0.004)
     return int(np.flatnonzero(idx >= 0)[0])
 
@@ -517,7 +476,7 @@ def test_color_sums_at_edge_sizes(icp, cpu, bumpy, first_hit, edge_target, n_q):
     Iq = CH.texture(Qn.astype(np.float64) @ T_gt[:3, :3].T + T_gt[:3, 3], 4.0)
     ctx.set_source(Qn)
     ctx.set_source_intensity(Iq)
-    n, nt = _check_color_sums(ctx, cpu, P, Qn, Np, G, Ip, Iq, _motion(0.3, 0.002) @ T_gt, d)
+    n, nt = _check_color_sums(ctx, cpu, P, Qn, Np, G, Ip, Iq, H.motion(0.3, 0.002) @ T_gt, d)
     print("edge size %d: %d pairs, %d with a term" % (n_q, n, nt))
     assert n >= (1 if n_q < 1000 else 1000)
     T, r = ctx.refine(T_gt, metric="color", max_iterations=2)

@@ -2,12 +2,12 @@
 (tests/icp_gicp_helpers.py), state and argument errors, determinism, the trajectory against the CPU loop, an exact pose, a
 planar target at the smallest epsilon, the facade / command line / Python binding agreeing, and edge sizes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import icp_gicp_helpers as GH
+from tests import apps
 from tests import icp_helpers as H
 from tests import icp_plane_helpers as PH
 
@@ -43,28 +43,6 @@ def lidar():
     return D.lidar_pair_scaled(0.02, delta=0.05)
 
 
-def _motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
-    a = np.asarray(axis, np.float64); a /= np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(angle_deg)
-    T = np.eye(4); T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K; T[:3, 3] = shift
-    return T
-
-
-def _rot_err_deg(A, B):
-    R = A[:3, :3] @ B[:3, :3].T
-    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
-
-
-def _raw_normals(rng, n):
-    """Caller normals: not unit length, some zero, one NaN."""
-    raw = rng.normal(size=(n, 3)).astype(np.float32) * 3
-    raw[::11] = 0
-    if n > 5:
-        raw[5, 0] = np.nan
-    return raw
-
-
 def _check_gicp_sums(ctx, cpu, P, Q, Np, Nq, T_caller, d, eps_list=EPSILONS):
     """Correspondences bit for bit, [0] and [2] exactly, every other entry within 1e-10 of its sum of |term|."""
     c = ctx.frame()
@@ -92,22 +70,22 @@ def test_gicp_sums_are_the_contract(icp, cpu, bumpy, lidar):
         ctx = icp.ICP(0)
         ctx.set_target(P, d)
         ctx.set_source(Q)
-        raw_q = _raw_normals(rng, len(Q))
+        raw_q = H.raw_normals(rng, len(Q))
         ctx.set_source_normals(raw_q)
         Nq = PH.normalise(raw_q)
         assert np.array_equal(ctx.source_normals(), Nq)
         assert not Nq[::11].any() and not Nq[5].any() and Nq.any(1).sum() > 0.8 * len(Q)
-        raw_p = _raw_normals(rng, len(P))
+        raw_p = H.raw_normals(rng, len(P))
         ctx.set_target_normals(raw_p)
         Np = PH.normalise(raw_p)
         assert np.array_equal(ctx.target_normals(), Np)
         for ang, sh in ((0.0, 0.0), (0.3, 0.002), (-1.0, 0.01)):
-            assert _check_gicp_sums(ctx, cpu, P, Q, Np, Nq, _motion(ang, sh) @ T_gt, d) > 1000
+            assert _check_gicp_sums(ctx, cpu, P, Q, Np, Nq, H.motion(ang, sh) @ T_gt, d) > 1000
         ctx.estimate_normals(d, MIN_NB)
         Ne = ctx.target_normals()
         assert np.array_equal(ctx.source_normals(), Nq)              # untouched by the target's normals
         for ang, sh in ((0.0, 0.0), (0.5, -0.004), (2.0, -0.02)):
-            assert _check_gicp_sums(ctx, cpu, P, Q, Ne, Nq, _motion(ang, sh) @ T_gt, d) > 1000
+            assert _check_gicp_sums(ctx, cpu, P, Q, Ne, Nq, H.motion(ang, sh) @ T_gt, d) > 1000
         ctx.close()
 
 
@@ -166,7 +144,7 @@ def _exact_pose_setup(icp, bumpy):
     ctx.estimate_normals(d)
     Np = ctx.target_normals()
     ctx.close()
-    M = _motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
+    M = H.motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
     Q = (P[pick].astype(np.float64) @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
     Nq = (Np[pick].astype(np.float64) @ M[:3, :3].T).astype(np.float32)
     return P, Q, Np, Nq, np.linalg.inv(M), d
@@ -177,7 +155,7 @@ def test_gicp_is_deterministic_and_torch_agrees(icp, bumpy):
     order_source on and off see the same correspondences."""
     import torch
     P, Q, Np, Nq, T_true, d = _exact_pose_setup(icp, bumpy)
-    T0 = _motion(1.0, 0.002) @ T_true
+    T0 = H.motion(1.0, 0.002) @ T_true
     ctx = icp.ICP(0)
     ctx.set_target(P, d); ctx.set_source(Q)
     ctx.set_target_normals(Np); ctx.set_source_normals(Nq * 2.5)
@@ -210,7 +188,7 @@ def test_gicp_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
     from super4pcs_amd import normals
     P, Q, T_gt = bumpy
     d = 4 * 0.004
-    T0 = _motion(1.5, 0.004) @ T_gt
+    T0 = H.motion(1.5, 0.004) @ T_gt
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Q)
@@ -222,7 +200,7 @@ def test_gicp_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
                                                ctx.target_normals(), ctx.source_normals(), c, T0, d)
     print("gicp trajectory: gpu %d its (%s) rmse %.6g; cpu %d its (%s) |dT| %.2g; rot err %.4g -> %.4g deg"
           % (r.iterations, icp.STATUS_NAMES[r.status], r.rmse, its, icp.STATUS_NAMES[status], np.max(np.abs(T - Tc)),
-             _rot_err_deg(T0, T_gt), _rot_err_deg(T, T_gt)))
+             H.rot_err_deg(T0, T_gt), H.rot_err_deg(T, T_gt)))
     assert np.max(np.abs(T - Tc)) <= 1e-5
     assert abs(r.iterations - its) <= 1 and r.status == status
     k = min(r.history_len, len(hist), 3)
@@ -233,7 +211,7 @@ def test_gicp_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
 def test_gicp_refine_reaches_an_exact_pose(icp, bumpy):
     """5: a rigidly moved subset of P with the same normals on both clouds, from 1 degree off: back to 1e-5, fitness 1."""
     P, Q, Np, Nq, T_true, d = _exact_pose_setup(icp, bumpy)
-    T0 = _motion(1.0, 0.002) @ T_true
+    T0 = H.motion(1.0, 0.002) @ T_true
     ctx = icp.ICP(0)
     ctx.set_target(P, d); ctx.set_source(Q)
     ctx.set_target_normals(Np); ctx.set_source_normals(Nq)
@@ -250,7 +228,7 @@ def test_gicp_planar_target_at_the_smallest_epsilon(icp, cpu):
     rng = np.random.default_rng(8)
     P = np.column_stack([rng.uniform(-1, 1, (50_000, 2)), np.zeros(50_000)]).astype(np.float32)
     Q = P[rng.choice(len(P), 20_000, replace=False)] + np.array([0, 0, 0.01], np.float32)
-    T0 = _motion(0.5, np.array([0.01, -0.02, 0.0]), axis=(0, 0, 1))
+    T0 = H.motion(0.5, np.array([0.01, -0.02, 0.0]), axis=(0, 0, 1))
     up = np.array([0, 0, 1], np.float32)
     Np, Nq = np.tile(up, (len(P), 1)), np.tile(up, (len(Q), 1))
     eps = 1e-6
@@ -284,16 +262,8 @@ def test_gicp_planar_target_at_the_smallest_epsilon(icp, cpu):
     ctx.close()
 
 
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
-
 def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built):
-    """7: the hippo fixture through MatchSuper4PCS + RefineICP(Generalized) (tests/icp_gicp_app), through
+    """7: the hippo fixture through MatchSuper4PCS + RefineICP(Generalized) (tests/icp_facade_app), through
     `Super4PCS ... --icp 30 --icp-metric gicp -m`, and through icp.refine from the same Super4PCS result; then the facade
     with both clouds' own normals (Q's rotated by the registration) against the binding."""
     from super4pcs_amd import build as B
@@ -301,24 +271,14 @@ def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built)
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_gicp_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_gicp_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
 
     def app(p_rows, q_rows):
-        np.savetxt(tmp_path / "P.xyz", p_rows, fmt="%.9g"); np.savetxt(tmp_path / "Q.xyz", q_rows, fmt="%.9g")
-        out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s)],
-                             capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stdout + out.stderr
-        return {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-                for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
+        return apps.run_icp_app(exe, p_rows, q_rows, delta, overlap, n_s, "--metric", "gicp")[0]
 
     rows = app(Ps, Qu)
     M, Mf = rows["registered"].astype(np.float64), rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     dT, r = icp.refine(Ps, Qm, np.eye(4), max_distance=np.float32(4.0 * delta), metric="gicp")
     want = icp.compose(dT, M).astype(np.float32)
     print("hippo gicp: facade == icp.py max diff %.2g, %d iterations (%s), rmse %.4g"
@@ -327,13 +287,8 @@ def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built)
     assert np.max(np.abs(rows["refined"] - Mf)) > 0
     # command line
     cli = B.build_cli()
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
-    rc = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-                         "-n", str(n_s), "--icp", "30", "--icp-metric", "gicp", "-m", str(tmp_path / "mat.txt")],
-                        capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
+    got, _ = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s, ["--icp", "30", "--icp-metric", "gicp"])
     assert np.max(np.abs(got - want)) <= 2e-6
     # the facade with both clouds' own (nonzero) normals uploads them, Q's rotated by the registration's linear part
     Np = normals.estimate_normals(Ps, k=16); Nq = normals.estimate_normals(Qu, k=16)
@@ -353,7 +308,7 @@ def first_hit(cpu, bumpy):
     """The first source point of the bumpy pair with a correspondence at the edge test's transform (CPU restatement)."""
     P, Q, T_gt = bumpy
     c = P.astype(np.float64).mean(0).astype(np.float32)
-    idx, _, _ = cpu.pass_((P - c).astype(np.float32), (Q - c).astype(np.float32), H.to_centred(_motion(0.3, 0.002) @ T_gt, c).astype(np.float32),
+    idx, _, _ = cpu.pass_((P - c).astype(np.float32), (Q - c).astype(np.float32), H.to_centred(H.motion(0.3, 0.002) @ T_gt, c).astype(np.float32),
                           4 * 0.004)
     return int(np.flatnonzero(idx >= 0)[0])
 
@@ -376,13 +331,13 @@ def test_gicp_sums_at_edge_sizes(icp, cpu, bumpy, first_hit, n_q):
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Qn)
-    raw_q = _raw_normals(rng, n_q)
+    raw_q = H.raw_normals(rng, n_q)
     ctx.set_source_normals(raw_q)
     Nq = PH.normalise(raw_q)
     assert np.array_equal(ctx.source_normals(), Nq)
     ctx.estimate_normals(d, MIN_NB)
     Np = ctx.target_normals()
-    n = _check_gicp_sums(ctx, cpu, P, Qn, Np, Nq, _motion(0.3, 0.002) @ T_gt, d)
+    n = _check_gicp_sums(ctx, cpu, P, Qn, Np, Nq, H.motion(0.3, 0.002) @ T_gt, d)
     print("edge size %d: %d pairs" % (n_q, n))
     assert n >= (1 if n_q < 1000 else 1000)
     T, r = ctx.refine(T_gt, metric="gicp", max_iterations=2)

@@ -3,11 +3,11 @@
 iterations than point-to-point, the trajectory against the CPU loop, a degenerate planar target, refinement after a
 registration, and the facade / command line / Python binding agreeing."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import icp_helpers as H
 from tests import icp_plane_helpers as PH
 
@@ -44,19 +44,6 @@ def bumpy():
 def lidar():
     from super4pcs_amd import datasets as D
     return D.lidar_pair_scaled(0.02, delta=0.05)
-
-
-def _motion(angle_deg, shift, axis=(0.3, -0.5, 0.8)):
-    a = np.asarray(axis, np.float64); a /= np.linalg.norm(a)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    th = np.deg2rad(angle_deg)
-    T = np.eye(4); T[:3, :3] = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K; T[:3, 3] = shift
-    return T
-
-
-def _rot_err_deg(A, B):
-    R = A[:3, :3] @ B[:3, :3].T
-    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
 
 
 def _check_normals(ctx, pcpu, P, r):
@@ -139,11 +126,11 @@ def test_plane_sums_are_the_contract(icp, cpu, bumpy, lidar):
         Nu = PH.normalise(raw)
         assert np.array_equal(ctx.target_normals(), Nu)
         for ang, sh in ((0.0, 0.0), (0.3, 0.002), (-1.0, 0.01)):
-            assert _check_plane_sums(ctx, cpu, P, Q, Nu, _motion(ang, sh) @ T_gt, d) > 1000
+            assert _check_plane_sums(ctx, cpu, P, Q, Nu, H.motion(ang, sh) @ T_gt, d) > 1000
         ctx.estimate_normals(d, MIN_NB)
         Ne = ctx.target_normals()
         for ang, sh in ((0.0, 0.0), (0.5, -0.004), (2.0, -0.02)):
-            assert _check_plane_sums(ctx, cpu, P, Q, Ne, _motion(ang, sh) @ T_gt, d) > 1000
+            assert _check_plane_sums(ctx, cpu, P, Q, Ne, H.motion(ang, sh) @ T_gt, d) > 1000
         ctx.set_target(P, d)                                          # set_target invalidates the normals
         with pytest.raises(icp.ICPError) as e:
             ctx.refine(T_gt, metric="plane")
@@ -156,7 +143,7 @@ def _exact_pose_setup(bumpy):
     rng = np.random.default_rng(5)
     sub = P[np.sort(rng.choice(len(P), 100_000, replace=False))].astype(np.float64)
     extent = float(np.linalg.norm(P.max(0) - P.min(0)))
-    M = _motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
+    M = H.motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
     Q = (sub @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
     return P, Q, np.linalg.inv(M), extent
 
@@ -221,7 +208,7 @@ def test_plane_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
     """5: the CPU restatement of the plane sums plus s4p_icp_solve_plane, from 1.5 degrees off the generator's pose."""
     P, Q, T_gt = bumpy
     d = 4 * 0.004
-    T0 = _motion(1.5, 0.004) @ T_gt
+    T0 = H.motion(1.5, 0.004) @ T_gt
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Q)
@@ -232,7 +219,7 @@ def test_plane_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
                                                 ctx.target_normals(), c, T0, d)
     print("plane trajectory: gpu %d its (%s) rmse %.6g; cpu %d its (%s) |dT| %.2g; rot err %.4g -> %.4g deg"
           % (r.iterations, icp.STATUS_NAMES[r.status], r.rmse, its, icp.STATUS_NAMES[status], np.max(np.abs(T - Tc)),
-             _rot_err_deg(T0, T_gt), _rot_err_deg(T, T_gt)))
+             H.rot_err_deg(T0, T_gt), H.rot_err_deg(T, T_gt)))
     assert np.max(np.abs(T - Tc)) <= 1e-5
     assert abs(r.iterations - its) <= 1 and r.status == status
     k = min(r.history_len, len(hist), 3)
@@ -244,7 +231,7 @@ def test_planar_target_is_degenerate(icp):
     rng = np.random.default_rng(8)
     P = np.column_stack([rng.uniform(-1, 1, (50_000, 2)), np.zeros(50_000)]).astype(np.float32)
     Q = P[rng.choice(len(P), 20_000, replace=False)] + np.array([0, 0, 0.01], np.float32)
-    T0 = _motion(0.5, np.array([0.01, -0.02, 0.0]), axis=(0, 0, 1))
+    T0 = H.motion(0.5, np.array([0.01, -0.02, 0.0]), axis=(0, 0, 1))
     ctx = icp.ICP(0)
     ctx.set_target(P, 0.08)
     ctx.set_source(Q)
@@ -275,47 +262,29 @@ def test_plane_refinement_after_registration_is_closer_to_the_generator(icp):
     M, Qm = _register(P, Q, delta, 0.5, 2000)
     dT, r = icp.refine(P, Qm, np.eye(4), max_distance=4 * delta, metric="plane")
     Mr = icp.compose(dT, M)
-    e0 = (_rot_err_deg(M, T_gt), float(np.linalg.norm(M[:3, 3] - T_gt[:3, 3])))
-    e1 = (_rot_err_deg(Mr, T_gt), float(np.linalg.norm(Mr[:3, 3] - T_gt[:3, 3])))
+    e0 = (H.rot_err_deg(M, T_gt), float(np.linalg.norm(M[:3, 3] - T_gt[:3, 3])))
+    e1 = (H.rot_err_deg(Mr, T_gt), float(np.linalg.norm(Mr[:3, 3] - T_gt[:3, 3])))
     print("configs[2] plane: Super4PCS rot %.4g deg trans %.4g -> rot %.4g deg trans %.4g (%d its, %s, rmse %.4g, fitness %.3f)"
           % (e0[0], e0[1], e1[0], e1[1], r.iterations, icp.STATUS_NAMES[r.status], r.rmse, r.fitness))
     assert e1[0] < e0[0] and e1[1] < e0[1]
 
 
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
-
 def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built):
-    """8: the hippo fixture through MatchSuper4PCS + RefineICP(PointToPlane) (tests/icp_plane_app), through
+    """8: the hippo fixture through MatchSuper4PCS + RefineICP(PointToPlane) (tests/icp_facade_app), through
     `Super4PCS ... --icp 30 --icp-metric plane -m`, and through icp.py from the same Super4PCS result; then the facade
     with P's own normals against set_target_normals."""
     from super4pcs_amd import build as B
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_plane_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_plane_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
 
     def app(p_rows):
-        np.savetxt(tmp_path / "P.xyz", p_rows, fmt="%.9g"); np.savetxt(tmp_path / "Q.xyz", Qu, fmt="%.9g")
-        out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s)],
-                             capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stdout + out.stderr
-        return {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-                for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
+        return apps.run_icp_app(exe, p_rows, Qu, delta, overlap, n_s, "--metric", "plane")[0]
 
     rows = app(Ps)
     M, Mf = rows["registered"].astype(np.float64), rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     ctx = icp.ICP(0)
     ctx.set_target(Ps, np.float32(4.0 * delta))
     ctx.set_source(Qm)
@@ -328,13 +297,8 @@ def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built)
     assert np.max(np.abs(rows["refined"] - Mf)) > 0
     # command line
     cli = B.build_cli()
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
-    rc = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-                         "-n", str(n_s), "--icp", "30", "--icp-metric", "plane", "-m", str(tmp_path / "mat.txt")],
-                        capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
+    got, _ = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s, ["--icp", "30", "--icp-metric", "plane"])
     assert np.max(np.abs(got - want)) <= 2e-6
     # the facade with P's own (nonzero) normals uploads them
     N = ctx.target_normals()

@@ -4,13 +4,13 @@ kernels, ties / duplicates / the bound d on a dyadic lattice, edge sizes and deg
 trajectory against the CPU loop, state errors, the facade / command line / Python binding agreeing, and multi-scale."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import icp_color_helpers as CH
 from tests import icp_gicp_helpers as GH
+from tests import apps
 from tests import icp_helpers as H
 from tests import icp_plane_helpers as PH
 from tests import icp_reject_helpers as JH
@@ -48,15 +48,6 @@ def lidar():
     return D.lidar_pair_scaled(0.02, delta=0.05)
 
 
-def _raw_normals(rng, n):
-    """Caller normals: not unit length, some zero, one NaN."""
-    raw = rng.normal(size=(n, 3)).astype(np.float32) * 3
-    raw[::11] = 0
-    if n > 5:
-        raw[5, 0] = np.nan
-    return raw
-
-
 def _set(ctx, kw):
     ctx.set_rejection(reciprocal=kw.get("reciprocal", False), oriented=kw.get("normal_mode", 0) == 2,
                       normal_cos=kw["normal_cos"] if kw.get("normal_mode", 0) else None)
@@ -89,7 +80,7 @@ def test_rejection_is_the_contract_per_point(icp, cpu, bumpy, lidar):
         ctx.set_source(Q)
         c = ctx.frame()
         Pc, Qc = (P - c).astype(np.float32), (Q - c).astype(np.float32)
-        raw_p, raw_q = _raw_normals(rng, len(P)), _raw_normals(rng, len(Q))
+        raw_p, raw_q = H.raw_normals(rng, len(P)), H.raw_normals(rng, len(Q))
         Nq_est = normals.estimate_normals(Q, k=16)
         for ang, sh in ((0.0, 0.0), (0.3, 0.002), (-1.0, 0.01)):
             Tc = H.to_centred(RH.motion(ang, sh) @ T_gt, c).astype(np.float32)
@@ -138,7 +129,7 @@ def test_every_sums_call_runs_over_the_kept_pairs(icp, cpu, bumpy):
     c = ctx.frame()
     Pc, Qc = (P - c).astype(np.float32), (Q - c).astype(np.float32)
     ctx.estimate_normals(d, MIN_NB)
-    ctx.set_source_normals(_raw_normals(rng, len(Q)))
+    ctx.set_source_normals(H.raw_normals(rng, len(Q)))
     Ip, Iq = CH.texture(P, 4.0), CH.texture(Q, 4.0)
     ctx.set_target_intensity(Ip); ctx.set_source_intensity(Iq)
     ctx.estimate_color_gradients(d / 2, MIN_NB)
@@ -293,7 +284,7 @@ def test_rejection_at_edge_sizes(icp, cpu, bumpy, first_hit, n_q):
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Qn)
-    ctx.set_source_normals(_raw_normals(rng, n_q))
+    ctx.set_source_normals(H.raw_normals(rng, n_q))
     ctx.estimate_normals(d, MIN_NB)
     Np, Nq = ctx.target_normals(), ctx.source_normals()
     c = ctx.frame()
@@ -486,42 +477,23 @@ def test_state_and_argument_errors(icp, cpu, bumpy):
     ctx.close()
 
 
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
-
 def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built):
     """9: the hippo fixture through MatchSuper4PCS + RefineICP with reciprocal and normal_angle_deg = 60
-    (tests/icp_reject_app), through `Super4PCS ... --icp 30 --icp-reciprocal --icp-normal-angle 60 -m`, and through icp.refine
+    (tests/icp_facade_app), through `Super4PCS ... --icp 30 --icp-reciprocal --icp-normal-angle 60 -m`, and through icp.refine
     from the same Super4PCS result."""
     from super4pcs_amd import build as B
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_reject_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_reject_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
-    np.savetxt(tmp_path / "P.xyz", Ps, fmt="%.9g"); np.savetxt(tmp_path / "Q.xyz", Qu, fmt="%.9g")
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
 
-    def app(metric, reciprocal, angle):
-        out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s), metric,
-                              str(int(reciprocal)), str(angle)], capture_output=True, text=True, timeout=300)
-        assert out.returncode == 0, out.stdout + out.stderr
-        rows = {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-                for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
-        stats = [ln for ln in out.stdout.splitlines() if ln.startswith("icp iterations")][0].split()
+    def app(metric, angle):
+        rows, stats = apps.run_icp_app(exe, Ps, Qu, delta, overlap, n_s, "--metric", metric, "--reciprocal", "--normal-angle-deg", angle)
         return rows, int(stats[6])
 
-    rows, n_app = app("point", True, 60)
+    rows, n_app = app("point", 60)
     M, Mf = rows["registered"].astype(np.float64), rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     dT, r = icp.refine(Ps, Qm, np.eye(4), max_distance=np.float32(4.0 * delta), reciprocal=True, normal_angle=60)
     dT0, r0 = icp.refine(Ps, Qm, np.eye(4), max_distance=np.float32(4.0 * delta))
     want = icp.compose(dT, M).astype(np.float32)
@@ -531,19 +503,15 @@ def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built)
     assert 3 <= r.n_corr < r0.n_corr and np.max(np.abs(rows["refined"] - Mf)) > 0
     # the other metrics take the options too
     for metric in ("plane", "gicp"):
-        rows_m, n_m = app(metric, True, 60)
+        rows_m, n_m = app(metric, 60)
         assert np.array_equal(rows_m["registered"], Mf)
         dTm, rm = icp.refine(Ps, Qm, np.eye(4), max_distance=np.float32(4.0 * delta), metric=metric, reciprocal=True, normal_angle=60)
         assert np.max(np.abs(rows_m["refined"] - icp.compose(dTm, M).astype(np.float32))) <= 1e-6 and n_m == rm.n_corr
     # command line
     cli = B.build_cli()
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
-    rc = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-                         "-n", str(n_s), "--icp", "30", "--icp-reciprocal", "--icp-normal-angle", "60", "-m", str(tmp_path / "mat.txt")],
-                        capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
+    got, _ = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s,
+                          ["--icp", "30", "--icp-reciprocal", "--icp-normal-angle", "60"])
     assert np.max(np.abs(got - want)) <= 2e-6
 
 

@@ -3,11 +3,11 @@
 and torch inputs, the trajectory against the CPU loop, an outlier scene where plain point-to-plane stays off the pose and
 trimmed / Tukey reach it, and the facade / command line / Python binding agreeing."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import icp_helpers as H
 from tests import icp_plane_helpers as PH
 from tests import icp_robust_helpers as RH
@@ -44,11 +44,6 @@ def bumpy():
 def lidar():
     from super4pcs_amd import datasets as D
     return D.lidar_pair_scaled(0.02, delta=0.05)
-
-
-def _rot_err_deg(A, B):
-    R = A[:3, :3] @ B[:3, :3].T
-    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
 
 
 CASES = [dict(loss="trimmed", trim_fraction=0.7), dict(loss="trimmed", trim_fraction=0.3), dict(loss="huber"),
@@ -225,7 +220,7 @@ def test_robust_trajectory_equals_the_cpu_loop(icp, cpu, bumpy):
         Tc, its, status, hist, hist_n = RH.cpu_refine_robust(cpu, icp.solve, icp.solve_plane, Pc, Qc, c, T0, d, metric, Nc=N, **kw)
         print("robust trajectory %s %s: gpu %d its (%s) rmse %.6g; cpu %d its (%s) |dT| %.2g; rot err %.4g -> %.4g deg"
               % (metric, kw, r.iterations, icp.STATUS_NAMES[r.status], r.rmse, its, icp.STATUS_NAMES[status], np.max(np.abs(T - Tc)),
-                 _rot_err_deg(T0, T_gt), _rot_err_deg(T, T_gt)))
+                 H.rot_err_deg(T0, T_gt), H.rot_err_deg(T, T_gt)))
         k = min(r.history_len, len(hist), 3)
         assert np.allclose(list(r.history_rmse[:k]), hist[:k], rtol=1e-9, atol=0)
         assert list(r.history_n[:k]) == hist_n[:k]
@@ -251,42 +246,24 @@ def test_trimmed_and_tukey_reach_the_pose_in_clutter(icp, pcpu, bumpy):
     Tt, rt = ctx.refine(np.eye(4), metric="plane", loss="trimmed", trim_fraction=frac)
     Tk, rk = ctx.refine(np.eye(4), metric="plane", loss="tukey")
     print("clutter: plain %.4g deg / %.3g, trimmed %.3g, tukey %.3g (max |T - T_true|); fitness %.3f %.3f %.3f"
-          % (_rot_err_deg(Tp, M), np.linalg.norm(Tp[:3, 3] - M[:3, 3]), np.max(np.abs(Tt - M)), np.max(np.abs(Tk - M)),
+          % (H.rot_err_deg(Tp, M), np.linalg.norm(Tp[:3, 3] - M[:3, 3]), np.max(np.abs(Tt - M)), np.max(np.abs(Tk - M)),
              rp.fitness, rt.fitness, rk.fitness))
-    assert _rot_err_deg(Tp, M) > 0.1 and np.max(np.abs(Tp - M)) > 1e-3
+    assert H.rot_err_deg(Tp, M) > 0.1 and np.max(np.abs(Tp - M)) > 1e-3
     assert np.max(np.abs(Tt - M)) <= 1e-6 and np.max(np.abs(Tk - M)) <= 1e-6
     assert abs(rt.fitness - frac) < 0.01
 
 
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
-
 def test_facade_cli_and_binding_agree_on_the_hippo_with_trimmed_loss(icp, tmp_path, s4p_lib_built):
-    """7: the hippo fixture through MatchSuper4PCS + RefineICP(loss Trimmed, xi = the overlap) (tests/icp_robust_app),
+    """7: the hippo fixture through MatchSuper4PCS + RefineICP(loss Trimmed, xi = the overlap) (tests/icp_facade_app),
     through `Super4PCS ... --icp 30 --icp-loss trimmed -m` (xi defaults to -o), and through icp.py from the same result."""
     from super4pcs_amd import build as B
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_robust_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_robust_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
-    np.savetxt(tmp_path / "P.xyz", Ps, fmt="%.9g"); np.savetxt(tmp_path / "Q.xyz", Qu, fmt="%.9g")
-    out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s), "trimmed",
-                          str(overlap)], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    rows = {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-            for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
+    rows, _ = apps.run_icp_app(exe, Ps, Qu, delta, overlap, n_s, "--loss", "trimmed", "--trim-fraction", overlap)
     M, Mf = rows["registered"].astype(np.float64), rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     ctx = icp.ICP(0)
     ctx.set_target(Ps, np.float32(4.0 * delta))
     ctx.set_source(Qm)
@@ -297,11 +274,6 @@ def test_facade_cli_and_binding_agree_on_the_hippo_with_trimmed_loss(icp, tmp_pa
     assert np.max(np.abs(rows["refined"] - want)) <= 1e-6
     assert np.max(np.abs(rows["refined"] - Mf)) > 0
     cli = B.build_cli()
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
-    rc = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-                         "-n", str(n_s), "--icp", "30", "--icp-loss", "trimmed", "-m", str(tmp_path / "mat.txt")],
-                        capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
+    got, _ = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s, ["--icp", "30", "--icp-loss", "trimmed"])
     assert np.max(np.abs(got - want)) <= 2e-6

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import icp_helpers as H
 from tests import icp_plane_helpers as PH
 from tests import icp_symm_helpers as SH
@@ -46,21 +47,6 @@ def lidar():
     return D.lidar_pair_scaled(0.02, delta=0.05)
 
 
-_motion = SH.motion
-
-
-def _rot_err_deg(A, B):
-    R = A[:3, :3] @ B[:3, :3].T
-    return float(np.degrees(np.arccos(np.clip((np.trace(R) - 1) / 2, -1, 1))))
-
-
-def _raw_normals(rng, n):
-    """Caller normals: not unit length, some zero, one NaN."""
-    raw = rng.normal(size=(n, 3)).astype(np.float32) * 3
-    raw[::11] = 0
-    if n > 5:
-        raw[5, 0] = np.nan
-    return raw
 
 
 def _frames(ctx, P, Q, T_caller):
@@ -98,23 +84,23 @@ def test_symm_sums_are_the_contract(icp, cpu, bumpy, lidar):
         ctx = icp.ICP(0)
         ctx.set_target(P, d)
         ctx.set_source(Q)
-        raw_q = _raw_normals(rng, len(Q))
+        raw_q = H.raw_normals(rng, len(Q))
         ctx.set_source_normals(raw_q)
         Nq = PH.normalise(raw_q)
         assert np.array_equal(ctx.source_normals(), Nq)
         assert not Nq[::11].any() and not Nq[5].any() and Nq.any(1).sum() > 0.8 * len(Q)
-        raw_p = _raw_normals(rng, len(P))
+        raw_p = H.raw_normals(rng, len(P))
         ctx.set_target_normals(raw_p)
         Np = PH.normalise(raw_p)
         assert np.array_equal(ctx.target_normals(), Np)
         for ang, sh in ((0.0, 0.0), (0.3, 0.002), (-1.0, 0.01)):
-            n, nt = _check_symm_sums(ctx, cpu, P, Q, Np, Nq, _motion(ang, sh) @ T_gt, d, name + ", caller normals")
+            n, nt = _check_symm_sums(ctx, cpu, P, Q, Np, Nq, H.motion(ang, sh) @ T_gt, d, name + ", caller normals")
             assert n > 1000 and 0 < n - nt < n               # some pairs have two zero normals, most have a term
         ctx.estimate_normals(d, MIN_NB)
         Ne = ctx.target_normals()
         assert np.array_equal(ctx.source_normals(), Nq)              # untouched by the target's normals
         for ang, sh in ((0.0, 0.0), (0.5, -0.004), (2.0, -0.02)):
-            n, nt = _check_symm_sums(ctx, cpu, P, Q, Ne, Nq, _motion(ang, sh) @ T_gt, d, name + ", estimated target normals")
+            n, nt = _check_symm_sums(ctx, cpu, P, Q, Ne, Nq, H.motion(ang, sh) @ T_gt, d, name + ", estimated target normals")
             assert n > 1000 and nt > 1000
         ctx.close()
 
@@ -124,7 +110,7 @@ def first_hit(cpu, bumpy):
     """The first source point of the bumpy pair with a correspondence at the edge test's transform (CPU restatement)."""
     P, Q, T_gt = bumpy
     c = P.astype(np.float64).mean(0).astype(np.float32)
-    idx, _, _ = cpu.pass_((P - c).astype(np.float32), (Q - c).astype(np.float32), H.to_centred(_motion(0.3, 0.002) @ T_gt, c).astype(np.float32),
+    idx, _, _ = cpu.pass_((P - c).astype(np.float32), (Q - c).astype(np.float32), H.to_centred(H.motion(0.3, 0.002) @ T_gt, c).astype(np.float32),
                           D_BUMPY)
     return int(np.flatnonzero(idx >= 0)[0])
 
@@ -147,12 +133,12 @@ def test_symm_sums_at_edge_sizes(icp, cpu, bumpy, first_hit, n_q):
     ctx = icp.ICP(0)
     ctx.set_target(P, d)
     ctx.set_source(Qn)
-    raw_q = _raw_normals(rng, n_q)
+    raw_q = H.raw_normals(rng, n_q)
     ctx.set_source_normals(raw_q)
     Nq = PH.normalise(raw_q)
     ctx.estimate_normals(d, MIN_NB)
     Np = ctx.target_normals()
-    n, _ = _check_symm_sums(ctx, cpu, P, Qn, Np, Nq, _motion(0.3, 0.002) @ T_gt, d, "edge size")
+    n, _ = _check_symm_sums(ctx, cpu, P, Qn, Np, Nq, H.motion(0.3, 0.002) @ T_gt, d, "edge size")
     assert n >= (1 if n_q < 1000 else 1000)
     T, r = ctx.refine(T_gt, metric="symmetric", max_iterations=2)
     assert np.all(np.isfinite(T)) and r.history_n[0] >= 1
@@ -167,11 +153,11 @@ def test_symm_sums_ignore_the_sign_of_either_normal(icp, cpu, bumpy):
     rng = np.random.default_rng(21)
     ctx = icp.ICP(0)
     ctx.set_target(P, d); ctx.set_source(Q)
-    Rp, Rq = _raw_normals(rng, len(P)), _raw_normals(rng, len(Q))
+    Rp, Rq = H.raw_normals(rng, len(P)), H.raw_normals(rng, len(Q))
     Rp[5, 0] = Rq[5, 0] = 0.5                                         # a NaN has no negation to compare
     ctx.set_target_normals(Rp); ctx.set_source_normals(Rq)
     Np, Nq = ctx.target_normals(), ctx.source_normals()               # as stored: some zero, the rest of unit length
-    Pc, Qc, Tc = _frames(ctx, P, Q, _motion(0.4, 0.003) @ T_gt)
+    Pc, Qc, Tc = _frames(ctx, P, Q, H.motion(0.4, 0.003) @ T_gt)
     ci, cd, _ = cpu.pass_(Pc, Qc, Tc, d)
     assert SH.dot_is_decided(Pc, Qc, Tc, ci, Np, Nq)                   # the precondition: no pair with dot == 0 and two normals
     _, _, _, dot, _, _ = SH.pair_terms(Pc, Qc, Tc, ci, Np, Nq)
@@ -230,7 +216,7 @@ def test_symm_sums_under_rejection(icp, cpu, bumpy):
     ctx.estimate_normals(d, MIN_NB)
     ctx.set_source_normals(normals.estimate_normals(Q, k=16))
     Np, Nq = ctx.target_normals(), ctx.source_normals()
-    Pc, Qc, Tc = _frames(ctx, P, Q, _motion(0.5, 0.003) @ T_gt)
+    Pc, Qc, Tc = _frames(ctx, P, Q, H.motion(0.5, 0.003) @ T_gt)
     s_off = ctx.symmetric_sums(Tc)
     for kw in (dict(reciprocal=True), dict(normal_angle=60), dict(reciprocal=True, normal_angle=60)):
         ctx.set_rejection(**kw)
@@ -242,7 +228,7 @@ def test_symm_sums_under_rejection(icp, cpu, bumpy):
         cs, cabs = SH.symm_sums(Pc, Qc, Tc, ki, kd, Np, Nq)
         assert gs[0] == counts[3] < s_off[0]
         _assert_sums(gs, cs, cabs, "rejection %s" % (kw,))
-        T, r = ctx.refine(_motion(0.5, 0.003) @ T_gt, metric="symmetric", max_iterations=3)
+        T, r = ctx.refine(H.motion(0.5, 0.003) @ T_gt, metric="symmetric", max_iterations=3)
         assert np.all(np.isfinite(T)) and r.n_corr > 0
     ctx.set_rejection()
     assert ctx.symmetric_sums(Tc).tobytes() == s_off.tobytes()
@@ -261,7 +247,7 @@ def _exact_pose_setup(icp, bumpy, n_q=8000):
     ctx.estimate_normals(d)
     Np = ctx.target_normals()
     ctx.close()
-    M = _motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
+    M = H.motion(2.0, 0.01 * extent * np.array([0.6, -0.8, 0.0]))
     Q = (P[pick].astype(np.float64) @ M[:3, :3].T + M[:3, 3]).astype(np.float32)
     Nq = (Np[pick].astype(np.float64) @ M[:3, :3].T).astype(np.float32)
     return P, Q, Np, Nq, np.linalg.inv(M), d
@@ -272,7 +258,7 @@ def test_symm_is_deterministic_and_torch_agrees(icp, bumpy):
     order_source on and off see the same correspondences."""
     import torch
     P, Q, Np, Nq, T_true, d = _exact_pose_setup(icp, bumpy)
-    T0 = _motion(1.0, 0.002) @ T_true
+    T0 = H.motion(1.0, 0.002) @ T_true
     ctx = icp.ICP(0)
     ctx.set_target(P, d); ctx.set_source(Q)
     ctx.set_target_normals(Np); ctx.set_source_normals(Nq * 2.5)
@@ -320,7 +306,7 @@ def _trajectory(icp, cpu, case, T0, T_gt, what):
     Tc, its, status, hist = SH.cpu_refine_symm(cpu, icp.solve_symmetric, Pc, Qc, Np, Nq, c, T0, D_BUMPY)
     print("symmetric trajectory, %s: gpu %d its (%s) rmse %.6g; cpu %d its (%s) |dT| %.2g; rot err %.4g -> %.4g deg"
           % (what, r.iterations, icp.STATUS_NAMES[r.status], r.rmse, its, icp.STATUS_NAMES[status], np.max(np.abs(T - Tc)),
-             _rot_err_deg(T0, T_gt), _rot_err_deg(T, T_gt)))
+             H.rot_err_deg(T0, T_gt), H.rot_err_deg(T, T_gt)))
     assert r.iterations == its and r.status == status
     assert np.max(np.abs(T - Tc)) <= 1e-5
     k = min(r.history_len, len(hist))
@@ -332,7 +318,7 @@ def test_symm_refine_trajectory_equals_the_cpu_loop(icp, cpu, bumpy, trajectory_
     """The CPU restatement of the symmetric sums plus s4p_icp_solve_symmetric, from 1.5 degrees off the generator's pose:
     same iterations and status, |T - T_cpu| <= 1e-5, the rmse history within rtol 1e-9."""
     T_gt = bumpy[2]
-    _trajectory(icp, cpu, trajectory_case, _motion(1.5, 0.004) @ T_gt, T_gt, "1.5 degrees")
+    _trajectory(icp, cpu, trajectory_case, H.motion(1.5, 0.004) @ T_gt, T_gt, "1.5 degrees")
 
 
 @pytest.fixture(scope="module")
@@ -372,7 +358,7 @@ def test_symm_refine_trajectory_where_the_plane_loop_needs_twice_the_iterations(
     T_gt = bumpy[2]
     chosen = None
     for ang in SLOW_PLANE_STARTS:
-        T0 = _motion(ang, 0.004) @ T_gt
+        T0 = H.motion(ang, 0.004) @ T_gt
         _, its_s, st_s, _ = SH.cpu_refine_symm(cpu, icp.solve_symmetric, Pc, Qc, Np, Nq, c, T0, D_BUMPY)
         _, its_p, st_p, _ = PH.cpu_refine_plane(cpu, icp.solve_plane, Pc, Qc, Np, c, T0, D_BUMPY)
         print("start %g degrees: cpu symmetric %d its (%s), cpu plane %d its (%s)"
@@ -385,14 +371,14 @@ def test_symm_refine_trajectory_where_the_plane_loop_needs_twice_the_iterations(
     T, r = _trajectory(icp, cpu, knn_normals_case, T0, T_gt, "%g degrees" % ang)
     Tp, rp = ctx.refine(T0, metric="plane")
     print("from %g degrees on the device: symmetric %d its (%s), rot err %.4g deg; plane %d its (%s), rot err %.4g deg"
-          % (ang, r.iterations, icp.STATUS_NAMES[r.status], _rot_err_deg(T, T_gt), rp.iterations, icp.STATUS_NAMES[rp.status],
-             _rot_err_deg(Tp, T_gt)))
+          % (ang, r.iterations, icp.STATUS_NAMES[r.status], H.rot_err_deg(T, T_gt), rp.iterations, icp.STATUS_NAMES[rp.status],
+             H.rot_err_deg(Tp, T_gt)))
 
 
 def test_symm_refine_reaches_an_exact_pose(icp, bumpy):
     """A rigidly moved subset of P with the same normals on both clouds, from 1 degree off: back to 1e-5, fitness 1."""
     P, Q, Np, Nq, T_true, d = _exact_pose_setup(icp, bumpy)
-    T0 = _motion(1.0, 0.002) @ T_true
+    T0 = H.motion(1.0, 0.002) @ T_true
     ctx = icp.ICP(0)
     ctx.set_target(P, d); ctx.set_source(Q)
     ctx.set_target_normals(Np); ctx.set_source_normals(Nq)
@@ -409,7 +395,7 @@ def test_symm_planar_target_is_degenerate(icp, cpu):
     rng = np.random.default_rng(8)
     P = np.column_stack([rng.uniform(-1, 1, (20_000, 2)), np.zeros(20_000)]).astype(np.float32)
     Q = P[rng.choice(len(P), 8_000, replace=False)] + np.array([0, 0, 0.01], np.float32)
-    T0 = _motion(0.5, np.array([0.01, -0.02, 0.0]), axis=(0, 0, 1))
+    T0 = H.motion(0.5, np.array([0.01, -0.02, 0.0]), axis=(0, 0, 1))
     up = np.array([0, 0, 1], np.float32)
     Np, Nq = np.tile(up, (len(P), 1)), np.tile(up, (len(Q), 1))
     ctx = icp.ICP(0)
@@ -491,35 +477,17 @@ def test_symm_state_and_argument_errors(icp, bumpy):
     ctx.close()
 
 
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
-
 def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built):
-    """The hippo fixture through MatchSuper4PCS + RefineICP(Symmetric) (tests/icp_symm_app), through
+    """The hippo fixture through MatchSuper4PCS + RefineICP(Symmetric) (tests/icp_facade_app), through
     `Super4PCS ... --icp 10 --icp-metric symmetric -m`, and through icp.refine from the same Super4PCS result."""
     from super4pcs_amd import build as B
     g = np.load(os.path.join(ROOT, "tests", "golden", "hippo_config1.npz"))
     Ps, Qu = g["Ps"].astype(np.float32), g["Qu"].astype(np.float32)
     delta, overlap, n_s = 0.01, 0.7, 200
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_symm_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "icp_symm_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
-    np.savetxt(tmp_path / "P.xyz", Ps, fmt="%.9g"); np.savetxt(tmp_path / "Q.xyz", Qu, fmt="%.9g")
-    out = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(delta), str(overlap), str(n_s), "10"],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
-    rows = {ln.split()[0]: np.array([float(v) for v in ln.split()[1:17]], np.float32).reshape(4, 4)
-            for ln in out.stdout.splitlines() if ln.startswith(("registered", "refined"))}
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS)
+    rows, _ = apps.run_icp_app(exe, Ps, Qu, delta, overlap, n_s, "--metric", "symmetric", "--max-iterations", 10)
     M, Mf = rows["registered"].astype(np.float64), rows["registered"]
-    x, y, z = Qu[:, 0], Qu[:, 1], Qu[:, 2]
-    Qm = np.stack([((Mf[k, 0] * x + Mf[k, 1] * y) + Mf[k, 2] * z) + Mf[k, 3] for k in range(3)], 1).astype(np.float32)
+    Qm = apps.move_f32(Mf, Qu)
     dT, r = icp.refine(Ps, Qm, np.eye(4), max_distance=np.float32(4.0 * delta), metric="symmetric", max_iterations=10)
     want = icp.compose(dT, M).astype(np.float32)
     print("hippo symmetric: facade == icp.py max diff %.2g, %d iterations (%s), rmse %.4g"
@@ -528,15 +496,13 @@ def test_facade_cli_and_binding_agree_on_the_hippo(icp, tmp_path, s4p_lib_built)
     assert np.max(np.abs(rows["refined"] - Mf)) > 0
     # command line
     cli = B.build_cli()
-    _write_obj(tmp_path / "P.obj", Ps); _write_obj(tmp_path / "Q.obj", Qu)
-    base = [cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
-            "-n", str(n_s), "--icp", "10", "--icp-metric", "symmetric", "-m", str(tmp_path / "mat.txt")]
-    rc = subprocess.run(base, capture_output=True, text=True, timeout=300)
-    assert rc.returncode == 0, rc.stderr
-    lines = (tmp_path / "mat.txt").read_text().splitlines()
-    got = np.array([[float(v) for v in ln.split()] for ln in lines[2:6]])
+    apps.write_obj(tmp_path / "P.obj", Ps); apps.write_obj(tmp_path / "Q.obj", Qu)
+    args = ["--icp", "10", "--icp-metric", "symmetric"]
+    got, _ = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s, args)
     assert np.max(np.abs(got - want)) <= 1e-6
-    rc = subprocess.run(base + ["--icp-loss", "huber"], capture_output=True, text=True, timeout=60)
+    rc = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-t", "1000",
+                         "-n", str(n_s)] + args + ["-m", str(tmp_path / "mat.txt"), "--icp-loss", "huber"],
+                        capture_output=True, text=True, timeout=60)
     assert rc.returncode == 1 and "Usage:" in rc.stderr
 
 

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import helpers as H
 from tests import normals_helpers as NH
 
@@ -28,10 +29,6 @@ def nrm():
 @pytest.fixture(scope="module")
 def cpu(tmp_path_factory):
     return NH.build_cpu(tmp_path_factory.mktemp("normals_cpu"))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _clouds():
@@ -74,7 +71,7 @@ def test_normals_equal_the_restatement_bit_for_bit(nrm, cpu, clouds, contexts, n
         for r in (None, radius):
             G = ctx.estimate(k, r)
             C = cpu.normals(X, k, r, queries=X[sample], threads=16)
-            diff = np.flatnonzero((_bits(G[sample]) != _bits(C)).any(1))
+            diff = np.flatnonzero((NH.bits(G[sample]) != NH.bits(C)).any(1))
             assert len(diff) == 0, (name, k, r, diff[:5], G[sample][diff[:3]], C[diff[:3]])
             zero = ~C.any(1)
             assert zero.mean() < 0.5 and (r is not None or k > 3 or zero.mean() < 0.5)
@@ -102,7 +99,7 @@ def test_normals_at_multi_trip_sizes_equal_the_restatement_bit_for_bit(nrm, cpu,
         for r in (None, radius):
             G = ctx.estimate(k, r)
             C = cpu.normals(X, k, r, queries=X[sample], threads=16)
-            diff = np.flatnonzero((_bits(G[sample]) != _bits(C)).any(1))
+            diff = np.flatnonzero((NH.bits(G[sample]) != NH.bits(C)).any(1))
             assert len(diff) == 0, (n, k, r, diff[:5], G[sample][diff[:3]], C[diff[:3]])
             zero = ~C.any(1)
             assert zero.mean() < 0.5
@@ -120,11 +117,11 @@ def test_estimate_at_equals_the_restatement(nrm, cpu, clouds, contexts):
         for r in (None, np.float32(0.02)):
             G = ctx.estimate_at(Q, k, r)
             C = cpu.normals(X, k, r, queries=Q, threads=16)
-            assert np.array_equal(_bits(G), _bits(C)), (k, r)
+            assert np.array_equal(NH.bits(G), NH.bits(C)), (k, r)
             assert not G[-2:].any()
     # queries that are the cloud's own points give estimate()'s answer
     idx = rng.integers(0, len(X), 1000)
-    assert np.array_equal(_bits(ctx.estimate_at(X[idx], 16)), _bits(ctx.estimate(16)[idx]))
+    assert np.array_equal(NH.bits(ctx.estimate_at(X[idx], 16)), NH.bits(ctx.estimate(16)[idx]))
 
 
 def test_two_calls_and_numpy_torch_agree(nrm, clouds, contexts):
@@ -132,16 +129,16 @@ def test_two_calls_and_numpy_torch_agree(nrm, clouds, contexts):
     X = clouds["lidar"]
     ctx = contexts["lidar"]
     a = ctx.estimate(16)
-    assert np.array_equal(_bits(a), _bits(ctx.estimate(16)))
+    assert np.array_equal(NH.bits(a), NH.bits(ctx.estimate(16)))
     Xt = torch.from_numpy(X).cuda()
     t = nrm.estimate_normals(Xt, k=16)
     assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (len(X), 3)
-    assert np.array_equal(_bits(t.cpu().numpy()), _bits(a))
-    assert np.array_equal(_bits(nrm.estimate_normals(X, k=16)), _bits(a))
+    assert np.array_equal(NH.bits(t.cpu().numpy()), NH.bits(a))
+    assert np.array_equal(NH.bits(nrm.estimate_normals(X, k=16)), NH.bits(a))
     Q = X[:777] + np.float32(0.01)
     qn = nrm.estimate_normals(X, k=8, radius=0.5, queries=Q)
     qt = nrm.estimate_normals(Xt, k=8, radius=0.5, queries=torch.from_numpy(Q).cuda())
-    assert np.array_equal(_bits(qt.cpu().numpy()), _bits(qn))
+    assert np.array_equal(NH.bits(qt.cpu().numpy()), NH.bits(qn))
 
 
 def test_plane_sphere_and_zero_normals(nrm):
@@ -211,19 +208,12 @@ def test_registration_parity_with_estimated_normals(nrm, oracle_mod, s4p_lib_bui
     assert gi.pairs_total < gm0.info().pairs_total
 
 
-def _write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
-
 
 def test_cli_estimate_normals_matches_the_python_path(nrm, s4p_lib_built, tmp_path):
     from super4pcs_amd import build as B, capi
     delta, overlap, n_s = 0.01, 0.6, 200
     P, Q, _ = H.small_pair(8000, delta=delta, seed=33)
-    _write_obj(tmp_path / "P.obj", P); _write_obj(tmp_path / "Q.obj", Q)
+    apps.write_obj(tmp_path / "P.obj", P); apps.write_obj(tmp_path / "Q.obj", Q)
     Pr = np.loadtxt(tmp_path / "P.obj", comments="#", usecols=(1, 2, 3), dtype=np.float32)      # the file's float values
     Qr = np.loadtxt(tmp_path / "Q.obj", comments="#", usecols=(1, 2, 3), dtype=np.float32)
     assert np.array_equal(Pr, P) and np.array_equal(Qr, Q)

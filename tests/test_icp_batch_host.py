@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import apps
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -122,10 +124,7 @@ def test_python_argument_checks_need_no_device(icp_lib):
 
 
 def _build_app(outdir, extra=()):
-    exe = os.path.join(str(outdir), "icp_batch_app" + ("_san" if extra else ""))
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + list(extra) +
-                          [os.path.join(ROOT, "tests", "icp_batch_app", "main.cpp"), "-ldl", "-o", exe])
-    return exe
+    return apps.build_app(outdir, "icp_batch_app", ("dl",), ("-g", "-Werror") + tuple(extra))
 
 
 @pytest.mark.parametrize("flags", [(), ("-fsanitize=address,undefined", "-fno-sanitize-recover=all")], ids=["plain", "sanitized"])

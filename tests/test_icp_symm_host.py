@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import icp_symm_helpers as SH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -201,7 +202,7 @@ def test_cli_symmetric_metric_parses_and_bad_combinations_exit_with_usage(s4p_li
 
 @pytest.mark.parametrize("eigen", [False, True])
 def test_facade_application_compiles_with_and_without_eigen(icp_lib, tmp_path, eigen):
-    """tests/icp_symm_app builds against the facade either way; the symmetric metric with a loss and in a batch is refused
+    """tests/icp_facade_app builds against the facade either way; the symmetric metric with a loss and in a batch is refused
     before a device is asked for."""
     extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
     probe = tmp_path / "probe.cpp"
@@ -209,16 +210,12 @@ def test_facade_application_compiles_with_and_without_eigen(icp_lib, tmp_path, e
     r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include")] + extra + [str(probe)],
                        capture_output=True, text=True)
     assert re.search(r"#error (have|none)", r.stderr).group(1) == ("have" if eigen else "none"), r.stderr
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "icp_symm_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include")] + extra +
-                          [os.path.join(ROOT, "tests", "icp_symm_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_amd",
-                           "-lsuper4pcs_icp", "-Wl,-rpath," + libdir, "-o", exe])
-    np.savetxt(tmp_path / "P.xyz", np.random.default_rng(1).uniform(size=(8, 3)), fmt="%.9g")
-    for mode, word in (("huber", "symmetric metric takes no loss"), ("batch", "no batch form")):
-        r = subprocess.run([exe, str(tmp_path / "P.xyz"), str(tmp_path / "P.xyz"), "0.01", "0.7", "8", "5", mode],
-                           capture_output=True, text=True)
-        assert r.returncode == 0 and r.stdout.startswith("refused: ") and word in r.stdout, (mode, r.returncode, r.stdout)
+    exe = apps.build_app(tmp_path, "icp_facade_app", apps.ICP_FACADE_LIBS, extra)
+    P = np.random.default_rng(1).uniform(size=(8, 3))
+    for flags, word in ((("--identity", "--loss", "huber"), "symmetric metric takes no loss"), (("--batch",), "no batch form")):
+        r = apps.start_icp_app(exe, P, P, "0.01", "0.7", "8", "--metric", "symmetric", "--max-iterations", "5", *flags)
+        # the program prints "invalid: " and exits with 5 for std::invalid_argument alone
+        assert r.returncode == 5 and r.stdout.splitlines()[-1].startswith("invalid: ") and word in r.stdout, (flags, r.returncode, r.stdout)
 
 
 def test_python_argument_checks_need_no_device(icp_lib):

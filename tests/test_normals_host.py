@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import apps
 from tests import normals_helpers as NH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -159,9 +160,5 @@ def test_cli_valid_command_fails_with_the_device_error_without_a_gpu(tmp_path):
 
 
 def test_facade_header_compiles_in_a_small_app(nrm, tmp_path):
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = str(tmp_path / "normals_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "normals_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_normals",
-                           "-Wl,-rpath," + libdir, "-o", exe])
+    exe = apps.build_app(tmp_path, "normals_app", ("super4pcs_normals",), ("-Werror",))
     assert os.path.exists(exe)

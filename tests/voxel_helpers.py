@@ -9,14 +9,13 @@ import subprocess
 
 import numpy as np
 
+from tests import apps
+from tests.normals_helpers import bits
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "voxel_cpu", "voxel_cpu.cpp")
 MAX_EXTENT = 1 << 21
 BLOCK = 64
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 class ExtentError(ValueError):
@@ -214,22 +213,12 @@ def assert_same(got, want, what):
         assert len(bad) == 0, (what, "attrs", bad[:5], ga[bad[:3]], wa[bad[:3]], wc[bad[:3]])
 
 
-def write_obj(path, pts):
-    with open(path, "w") as f:
-        f.write("# points\n")
-        for p in pts:
-            f.write("v %.9g %.9g %.9g\n" % (p[0], p[1], p[2]))
-        f.write("# End of File\n")
+write_obj = apps.write_obj
 
 
 def build_app(outdir, extra=()):
     """tests/voxel_app/main.cpp against the facade header and libsuper4pcs_normals.so."""
-    libdir = os.path.join(ROOT, "super4pcs_amd", "lib")
-    exe = os.path.join(str(outdir), "voxel_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include")] + list(extra) +
-                          [os.path.join(ROOT, "tests", "voxel_app", "main.cpp"), "-L" + libdir, "-lsuper4pcs_normals",
-                           "-Wl,-rpath," + libdir, "-o", exe])
-    return exe
+    return apps.build_app(outdir, "voxel_app", ("super4pcs_normals",), ("-Werror",) + tuple(extra))
 
 
 def write_table(path, rows):
