@@ -9,7 +9,7 @@
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
 //             [--estimate-normals k] [--estimate-normals-radius r]
 //             [--remove-outliers k] [--remove-outliers-std ratio]
-//             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K]
+//             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K] [--icp-information file]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -38,14 +38,20 @@
 // greatest LCP follow; RefineICPBatch keeps the pose with the most correspondences on the full clouds (then the least rmse), so
 // the outcome never has fewer correspondences than --icp alone.  Point and plane metrics only, no --icp-loss, no pair
 // rejection.  With --icp-scales the batch runs on the coarsest level's clouds and the other levels follow from its pose.
+// --icp-information file (needs --icp) writes, next to what -m writes, the final pose T (the printed matrix, widened to double),
+// the 6x6 information matrix of algorithms/icp_information.h for the second input in its own frame under T (after
+// --remove-outliers / --voxel-size; --icp-dist and the pair rejection flags hold), the matched count and the rmse, every number
+// as %.17g: the edge of this pair in a pose graph (algorithms/posegraph.h), so that a graph can be assembled from pairwise runs.
 // -x (the legacy 4PCS matcher, algorithms/4pcs.cc) is outside this library and is refused.
 #include <cstdio>
 #include <exception>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "super4pcs/algorithms/icp.h"
 #include "super4pcs/algorithms/icp_batch.h"
+#include "super4pcs/algorithms/icp_information.h"
 #include "super4pcs/algorithms/icp_multiscale.h"
 #include "super4pcs/algorithms/normals.h"
 #include "super4pcs/algorithms/outliers.h"
@@ -181,6 +187,8 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
     }
     std::vector<Point3D> Q0;                                // the second input in its own frame: the matcher moves Q.points
     if (opt.icp_iterations > 0 && !opt.icp_scales.empty()) Q0 = Q.points;
+    std::vector<Point3D> Qown;                              // --icp-information: the same, kept as it is
+    if (!opt.icp_information.empty()) Qown = Q.points;
     const double icp_distance = opt.icp_distance > 0 ? opt.icp_distance : 4.0 * opt.delta;
     MatchSuper4PCS matcher(mopt, log);
     log.Log<Utils::Verbose>("Use Super4PCS");
@@ -270,6 +278,23 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
         ICPResult res;
         RefineICP(P.points, &Q.points, mat, icp, &res);
         log.Log<Utils::Verbose>("ICP: ", res.iterations, " iterations, rmse ", res.rmse, ", fitness ", res.fitness);
+      }
+      if (!opt.icp_information.empty()) {
+        double T16[16], info[36], rmse = 0.0;
+        int64_t n = 0;
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T16[4 * r + c] = double(mat(r, c));
+        ICPInformation(P.points, Qown, T16, icp, info, &n, &rmse);
+        log.Log<Utils::Verbose>("Exporting Information matrix to ", opt.icp_information.c_str(), " (", n, " matched points) ...");
+        FILE* f = std::fopen(opt.icp_information.c_str(), "w");
+        if (!f) throw std::runtime_error("--icp-information: cannot write " + opt.icp_information);
+        std::fprintf(f, "VERSION\t=\t1\nPOSE\t=\n");
+        for (int r = 0; r < 4; ++r) std::fprintf(f, "%.17g %.17g %.17g %.17g\n", T16[4 * r], T16[4 * r + 1], T16[4 * r + 2], T16[4 * r + 3]);
+        std::fprintf(f, "INFORMATION\t=\n");
+        for (int r = 0; r < 6; ++r)
+          std::fprintf(f, "%.17g %.17g %.17g %.17g %.17g %.17g\n", info[6 * r], info[6 * r + 1], info[6 * r + 2], info[6 * r + 3], info[6 * r + 4],
+                       info[6 * r + 5]);
+        std::fprintf(f, "CORRESPONDENCES\t=\t%lld\nRMSE\t=\t%.17g\n", (long long)n, rmse);
+        std::fclose(f);
       }
     }
   } catch (const std::exception& e) {

@@ -41,6 +41,7 @@ struct Options {
   bool icp_reciprocal = false;                               // --icp-reciprocal  keep reciprocal pairs only (needs --icp)
   double icp_normal_angle = -1;                              // --icp-normal-angle deg  reject pairs whose normals differ by more (needs --icp)
   bool icp_normal_angle_set = false;
+  std::string icp_information;                               // --icp-information file  the refined pose's 6x6 information matrix (needs --icp)
   int normals_k = 0;                                         // --estimate-normals k  normals of both inputs on the device (0: off)
   double normals_radius = -1;                                // --estimate-normals-radius r  (default: unbounded)
   bool normals_radius_set = false;
@@ -139,6 +140,10 @@ inline const Flag* flag_table(size_t* n) {
          o.icp_normal_angle_set = true;
          if (end == v[0] || *end != '\0' || !(a >= 0) || !(a <= 90)) o.bad_value = true; else o.icp_normal_angle = a;
        }},
+      {"--icp-information", 1, [](Options& o, char** v) {
+         o.icp_information = v[0];
+         if (o.icp_information.empty()) o.bad_value = true;
+       }},
       {"--estimate-normals", 1, [](Options& o, char** v) {
          char* end = nullptr;
          const long k = std::strtol(v[0], &end, 10);
@@ -225,6 +230,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.icp_scales_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-scales needs --icp
   if ((o.icp_reciprocal || o.icp_normal_angle_set) && o.icp_iterations == 0) return Parse::Bad;    // pair rejection needs --icp
   if (o.icp_starts_set && o.icp_iterations == 0) return Parse::Bad;    // --icp-starts needs --icp
+  if (!o.icp_information.empty() && o.icp_iterations == 0) return Parse::Bad;    // --icp-information needs --icp
   // the batch refines point and plane only, without a loss and without pair rejection
   if (o.icp_starts_set && (o.icp_loss != 0 || o.icp_gicp || o.icp_symm || o.icp_color || o.icp_reciprocal || o.icp_normal_angle_set)) return Parse::Bad;
   // neither geometry nor matrix requested: write the registered geometry under the reference's default name
@@ -252,6 +258,8 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t[ --icp-loss-scale s (huber, tukey; estimated) ]  (robust ICP)\n");
   std::fprintf(stderr, "\t[ --icp-reciprocal ] [ --icp-normal-angle deg (in [0, 90]; off) ]  (pair rejection, needs --icp, any metric and loss:\n");
   std::fprintf(stderr, "\t    keep a pair only when it is nearest in both directions / when its normals, up to sign, differ by at most deg)\n");
+  std::fprintf(stderr, "\t[ --icp-information file (needs --icp: the final pose in double, its 6x6 information matrix over the matched points of\n");
+  std::fprintf(stderr, "\t    input1, their count and the rmse; the edge of this pair in a pose graph) ]\n");
   std::fprintf(stderr, "\t[ --estimate-normals k (3..32; off) ] [ --estimate-normals-radius r (needs k; unbounded) ]\n");
   std::fprintf(stderr, "\t    (kNN normals of both inputs on the device, replacing the files' normals, before matching: -a filters on\n");
   std::fprintf(stderr, "\t     them and --icp-metric plane / gicp / symmetric / color use P's (gicp, symmetric: Q's too) when all are nonzero)\n");

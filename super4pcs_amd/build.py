@@ -111,13 +111,13 @@ ICP_SOURCES = ["s4p_icp.hip"]
 
 
 def build_icp(force=False, verbose=False):
-    """lib/libsuper4pcs_icp.so: ICP refinement (icp_src/, include/s4p_icp.h, s4p_icp_plane.h, s4p_icp_robust.h, s4p_icp_gicp.h, s4p_icp_symm.h, s4p_icp_color.h, s4p_icp_reject.h, s4p_icp_batch.h), a library of its own
+    """lib/libsuper4pcs_icp.so: ICP refinement (icp_src/, include/s4p_icp.h, s4p_icp_plane.h, s4p_icp_robust.h, s4p_icp_gicp.h, s4p_icp_symm.h, s4p_icp_color.h, s4p_icp_reject.h, s4p_icp_batch.h, s4p_icp_info.h, s4p_icp_posegraph.h), a library of its own
     so that the main library's sources and kernels stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off).
     One translation unit: s4p_icp.hip includes s4p_icp_k_common / _k_build / _k_pass.hip.hpp (kernels) and s4p_icp_solve / _ctx / _pass /
-    _abi.inc (host), then s4p_icp_k_batch.hip.hpp and s4p_icp_batch.inc; a change to any file under icp_src/ rebuilds."""
+    _abi.inc (host), then s4p_icp_k_batch.hip.hpp, s4p_icp_batch.inc and s4p_icp_posegraph.inc (host only); a change to any file under icp_src/ rebuilds."""
     deps = [os.path.join(ICP_SRC, f) for f in os.listdir(ICP_SRC)] + [os.path.join(ROOT, "include", h)
                                                                        for h in ("s4p_icp.h", "s4p_icp_plane.h", "s4p_icp_robust.h", "s4p_icp_gicp.h", "s4p_icp_symm.h", "s4p_icp_color.h",
-                                                                                 "s4p_icp_reject.h", "s4p_icp_batch.h")]
+                                                                                 "s4p_icp_reject.h", "s4p_icp_batch.h", "s4p_icp_info.h", "s4p_icp_posegraph.h")]
     if not force and os.path.exists(ICP_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(ICP_LIB) for d in deps):
         return ICP_LIB
     os.makedirs(LIBDIR, exist_ok=True)
@@ -175,6 +175,7 @@ def build_cli(force=False):
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "voxelgrid.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp_multiscale.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp_batch.h"),
+            os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp_information.h"),
             os.path.join(ROOT, "include", "super4pcs", "io", "io.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "match4pcsBase.h")]
     if not force and os.path.exists(CLI) and all(os.path.getmtime(d) <= os.path.getmtime(CLI) for d in deps):

@@ -1,5 +1,6 @@
 """ctypes binding of include/s4p_icp.h, include/s4p_icp_plane.h, include/s4p_icp_robust.h, include/s4p_icp_gicp.h,
-include/s4p_icp_symm.h, include/s4p_icp_color.h, include/s4p_icp_reject.h and include/s4p_icp_batch.h (libsuper4pcs_icp.so):
+include/s4p_icp_symm.h, include/s4p_icp_color.h, include/s4p_icp_reject.h, include/s4p_icp_batch.h and include/s4p_icp_info.h
+(libsuper4pcs_icp.so):
 point-to-point, point-to-plane, generalized (plane-to-plane), symmetric and coloured ICP refinement on the full-resolution clouds, with optional robust
 losses for the first two, optional correspondence rejection (reciprocal pairs, normal angle) for all of them, and batched
 multi-start refinement (many start poses in one pass, ranked on the full clouds) for the first two.
@@ -13,6 +14,7 @@ multi-start refinement (many start poses in one pass, ranked on the full clouds)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, metric="color", target_intensity=rgbP, source_intensity=rgbQ)
     T, res = icp.refine(P, Q, T0, max_distance=4 * delta, reciprocal=True, normal_angle=60)   # pair rejection, any metric / loss
     T, res, i = icp.refine_best(P, Q, T0s, max_distance=4 * delta)          # up to 64 starts side by side; the best by n_corr, rmse
+    info, n, rmse = icp.information(P, Q, T, max_distance=4 * delta)        # the 6x6 weight of this pair in a pose graph
 
 Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tensors on the context's GPU (they enter
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
@@ -79,6 +81,13 @@ BATCH_SYMBOLS = [                                          # include/s4p_icp_bat
     "s4p_icp_sums_batch", "s4p_icp_refine_batch", "s4p_icp_rank_batch",
 ]
 BATCH_MAX = 64                                             # S4P_ICP_BATCH_MAX
+INFO_SYMBOLS = [                                           # include/s4p_icp_info.h
+    "s4p_icp_information_sums", "s4p_icp_information_from_sums", "s4p_icp_information",
+]
+INFO_NSUMS = 11                                            # S4P_ICP_INFO_NSUMS
+POSEGRAPH_SYMBOLS = [                                      # include/s4p_icp_posegraph.h (bound in super4pcs_amd.posegraph)
+    "s4p_icp_posegraph_default_params", "s4p_icp_posegraph_cost", "s4p_icp_posegraph_optimize",
+]
 NORMALS_OFF, NORMALS_UNORIENTED, NORMALS_ORIENTED = 0, 1, 2         # S4P_ICP_REJECT_NORMALS_*
 WHY_KEPT, WHY_UNMATCHED, WHY_NORMALS, WHY_RECIPROCITY = 0, 1, 2, 3  # S4P_ICP_WHY_*
 
@@ -215,6 +224,14 @@ def load_library():
     L.s4p_icp_refine_batch.argtypes = [vp, C.POINTER(BatchParams), C.c_int32, dp, C.POINTER(Result), ip]
     L.s4p_icp_rank_batch.restype = C.c_int32
     L.s4p_icp_rank_batch.argtypes = [C.POINTER(Result), C.c_int32, ip]
+    L.s4p_icp_information_sums.restype = C.c_int32
+    L.s4p_icp_information_sums.argtypes = [vp, fp, dp]
+    L.s4p_icp_information_from_sums.restype = C.c_int32
+    L.s4p_icp_information_from_sums.argtypes = [dp, fp, dp, C.POINTER(C.c_int64), dp]
+    L.s4p_icp_information.restype = C.c_int32
+    L.s4p_icp_information.argtypes = [vp, dp, dp, C.POINTER(C.c_int64), dp]
+    from super4pcs_amd import posegraph
+    posegraph.bind(L)
     _LIB = L
     return L
 
@@ -651,6 +668,25 @@ class ICP:
         self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
         return T.reshape(4, 4), r
 
+    def information_sums(self, T):
+        """The 11 information sums for a float T in the centred frame (layout in include/s4p_icp_info.h): n, sum d2,
+        sum p', the upper triangle of sum p' p'^T over the matched target points; the context's rejection holds."""
+        T = self._t32(T)
+        out = np.empty(INFO_NSUMS, np.float64)
+        self._chk(self.L.s4p_icp_information_sums(self.h, _fp(T), _dp(out)))
+        return out
+
+    def information(self, T):
+        """(info float64 6x6, n, rmse) of the pose T (caller frame, float64 4x4; include/s4p_icp_info.h): info = sum G^T G
+        over the matched target points p, G = [-[p]x | I], rotation block first -- the weight of this pair's edge in a
+        pose graph (super4pcs_amd.posegraph).  No match: zeros, 0, 0."""
+        T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(16))
+        info = np.empty(36, np.float64)
+        n = C.c_int64(0)
+        rmse = C.c_double(0.0)
+        self._chk(self.L.s4p_icp_information(self.h, _dp(T), _dp(info), C.byref(n), C.byref(rmse)))
+        return info.reshape(6, 6), int(n.value), float(rmse.value)
+
     def sums_batch(self, Ts, metric="point"):
         """float64 (B, 17) for "point" or (B, 31) for "plane": row b holds the bits of sums(Ts[b]) / plane_sums(Ts[b]), from
         one launch over all B float transforms in the centred frame (include/s4p_icp_batch.h)."""
@@ -760,5 +796,49 @@ def refine_best(P, Q, T0s, max_distance=None, device=0, metric="point", target_n
         Ts, results, order = ctx.refine_batch(T0s, metric=metric, **params)
         i = int(order[0])
         return Ts[i], results[i], i
+    finally:
+        ctx.close()
+
+
+def information_from_sums(sums, c):
+    """(info 6x6, n, rmse) from the 11 information sums and the frame c (3 floats): the host half of ICP.information
+    (s4p_icp_information_from_sums, no device)."""
+    L = load_library()
+    s = np.ascontiguousarray(sums, np.float64).reshape(INFO_NSUMS)
+    c = np.ascontiguousarray(c, np.float32).reshape(3)
+    info = np.empty(36, np.float64)
+    n = C.c_int64(0)
+    rmse = C.c_double(0.0)
+    rc = L.s4p_icp_information_from_sums(_dp(s), _fp(c), _dp(info), C.byref(n), C.byref(rmse))
+    if rc != 0:
+        raise ICPError(rc, "information_from_sums: bad argument")
+    return info.reshape(6, 6), int(n.value), float(rmse.value)
+
+
+def information(P, Q, T, max_distance=None, device=0, reciprocal=False, normal_angle=None, normals_oriented=False,
+                target_normals=None, normal_radius=None, source_normals=None, normal_k=16):
+    """(info 6x6, n, rmse): the information matrix of the pose T (maps Q onto P, caller frame) over the pairs within
+    max_distance, on one context (ICP.information).  reciprocal / normal_angle / normals_oriented set the pair rejection as
+    for refine; with normal_angle the normals follow refine's rules (given, else estimated)."""
+    if max_distance is None:
+        raise ValueError("max_distance is required (4 * delta after a registration at delta)")
+    rej = reject_params(reciprocal, normal_angle, normals_oriented)
+    by_normals = rej.normal_mode != NORMALS_OFF
+    if by_normals and source_normals is None:
+        from super4pcs_amd import normals
+        source_normals = normals.estimate_normals(Q, k=normal_k)
+    ctx = ICP(device)
+    try:
+        ctx.set_target(P, max_distance)
+        ctx.set_source(Q)
+        if by_normals:
+            if target_normals is not None:
+                ctx.set_target_normals(target_normals)
+            else:
+                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
+            ctx.set_source_normals(source_normals)
+        if rej.reciprocal or by_normals:
+            ctx._chk(ctx.L.s4p_icp_set_rejection(ctx.h, C.byref(rej)))
+        return ctx.information(T)
     finally:
         ctx.close()

@@ -21,6 +21,8 @@
 //   coloured     (include/s4p_icp_color.h) target intensities in cell order (k_gather_target_intensity), their tangent-plane
 //                gradients (k_color_gradient, k_normals' walk), source intensities in the order of the source
 //                (k_gather_source_intensity); per iteration k_search, k_color_sum (31 joint sums) + k_final_plane, host solve.
+//   information  (include/s4p_icp_info.h) one call: k_search, k_info_sum (11 double sums over the winners streamed from the
+//                slots) + k_final_info, one read-back; the 6x6 matrix on the host.
 //   rejection    (include/s4p_icp_reject.h) a state of the context: a second grid over the source (set_target's plan and
 //                build), and k_reject between k_search and the sum kernel of every split pass: it clears the slot and key of
 //                a pair that fails the normal test or the reverse search.  Off: nothing of it is launched.
@@ -44,6 +46,8 @@
 #include "s4p_icp_color.h"
 #include "s4p_icp_reject.h"
 #include "s4p_icp_batch.h"
+#include "s4p_icp_info.h"
+#include "s4p_icp_posegraph.h"
 
 
 // The parts, in dependency order ("ICP sources: layout"):
@@ -68,3 +72,5 @@
 //   s4p_icp_batch.inc          the batch's buffers, the batched pass, the refine loop over an active list, the ranking
 #include "s4p_icp_k_batch.hip.hpp"
 #include "s4p_icp_batch.inc"
+// pose-graph optimisation (include/s4p_icp_posegraph.h): host only, no kernel
+#include "s4p_icp_posegraph.inc"

@@ -487,4 +487,48 @@ int32_t s4p_icp_rejection_counts(const s4p_icp_ctx* h, int64_t counts[4]) {
   return S4P_ICP_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// the information matrix of a pairwise pose (include/s4p_icp_info.h)
+
+int32_t s4p_icp_information_sums(s4p_icp_ctx* h, const float* T16_centred, double* sums) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16_centred || !sums) return fail(h, S4P_ICP_ERR_BAD_ARG, "information_sums: null argument");
+  return info_call(h, centred_from_float16(T16_centred), sums);
+}
+
+int32_t s4p_icp_information_from_sums(const double* s, const float* c3, double* info36, int64_t* n_corr, double* rmse) {
+  if (!s || !c3 || !info36) return S4P_ICP_ERR_BAD_ARG;
+  // include/s4p_icp_info.h's order of operations
+  const double n = s[0], c[3] = {double(c3[0]), double(c3[1]), double(c3[2])};
+  std::memset(info36, 0, 36 * sizeof(double));
+  if (n_corr) *n_corr = int64_t(n);
+  if (rmse) *rmse = n > 0.0 ? std::sqrt(s[1] / n) : 0.0;
+  if (!(n > 0.0)) return S4P_ICP_OK;
+  double S[3], P[3][3];
+  for (int a = 0; a < 3; ++a) S[a] = s[2 + a] + n * c[a];
+  for (int a = 0, o = 5; a < 3; ++a)
+    for (int b = a; b < 3; ++b, ++o) P[a][b] = P[b][a] = (s[o] + (s[2 + a] * c[b] + c[a] * s[2 + b])) + n * (c[a] * c[b]);
+  const double tr = (P[0][0] + P[1][1]) + P[2][2];
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) info36[6 * a + b] = a == b ? tr - P[a][a] : -P[a][b];
+  const double X[3][3] = {{0.0, -S[2], S[1]}, {S[2], 0.0, -S[0]}, {-S[1], S[0], 0.0}};
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) {
+      info36[6 * a + 3 + b] = X[a][b];
+      info36[6 * (3 + a) + b] = X[b][a];              // -[S]x
+      info36[6 * (3 + a) + 3 + b] = a == b ? n : 0.0;
+    }
+  return S4P_ICP_OK;
+}
+
+int32_t s4p_icp_information(s4p_icp_ctx* h, const double* T16, double* info36, int64_t* n_corr, double* rmse) {
+  if (!h) return S4P_ICP_ERR_BAD_ARG;
+  if (!T16 || !info36) return fail(h, S4P_ICP_ERR_BAD_ARG, "information: null argument");
+  if (!h->has_target || !h->has_source) return fail(h, S4P_ICP_ERR_STATE, "set_target and set_source first");
+  double Tc[16], s[S4P_ICP_INFO_NSUMS];
+  to_centred(T16, h->c, Tc);
+  if (int32_t rc = info_call(h, to_float(Tc), s)) return rc;
+  return s4p_icp_information_from_sums(s, h->c, info36, n_corr, rmse);
+}
+
 }  // extern "C"

@@ -95,7 +95,7 @@ namespace {
 
 std::string g_create_error;
 constexpr int kSumsCap = S4P_ICP_PLANE_NSUMS;       // dsum / hsum hold the 17 point or the 31 plane sums
-static_assert(S4P_ICP_PLANE_NSUMS >= S4P_ICP_NSUMS, "sum buffers");
+static_assert(S4P_ICP_PLANE_NSUMS >= S4P_ICP_NSUMS && S4P_ICP_PLANE_NSUMS >= S4P_ICP_INFO_NSUMS, "sum buffers");
 
 int32_t fail(s4p_icp_ctx* h, int32_t code, const std::string& msg) {
   h->err = msg;

@@ -1,5 +1,5 @@
 // s4p_icp_k_pass.hip.hpp -- the kernels of a pass: the fused k_match / k_match_plane, and the split passes' k_search,
-// k_reject, the selection (k_key_hist, k_key_digit), the sum kernels (k_wsum, k_gicp_sum, k_symm_sum, k_color_sum), the final sums and
+// k_reject, the selection (k_key_hist, k_key_digit), the sum kernels (k_wsum, k_gicp_sum, k_symm_sum, k_info_sum, k_color_sum), the final sums and
 // k_reject_out.  Every sum kernel ends in block_row and every final sum is slab_total's order (s4p_icp_k_common.hip.hpp).
 //
 // The measured kernels are pinned instruction for instruction ("ICP sources: layout").  What a change here can
@@ -291,6 +291,50 @@ __global__ __launch_bounds__(kBlock) void k_symm_sum(SymmArgs A) {
     for (int i = 0; i < 6; ++i) s[25 + i] += a[i] * r;
   }
   block_row<NS, kPlanePitch>(s, A.slab);
+}
+
+struct InfoArgs {
+  Tf T;
+  const float4* src;
+  const float4* tgt;        // cell order: the winner of lane j is tgt[slot[j]]
+  uint64_t n;
+  const uint32_t* slot;     // k_search's
+  double* slab;             // one kPlanePitch row per workgroup (11 used)
+};
+
+// The information sums, term by term as include/s4p_icp_info.h states them: n, sum d2, sum p', the upper triangle of
+// sum p' p'^T over the winners.  No search: the winner comes from k_search's slot; q^ is recomputed for the contract's d2.
+__global__ __launch_bounds__(kBlock) void k_info_sum(InfoArgs A) {
+  constexpr int NS = S4P_ICP_INFO_NSUMS;
+  double s[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) s[k] = 0.0;
+  for (uint64_t j = blockIdx.x * (uint64_t)kBlock + threadIdx.x; j < A.n; j += (uint64_t)gridDim.x * kBlock) {
+    const uint32_t sl = A.slot[j];
+    if (sl == kNoSlot) continue;
+    const float4 q = A.src[j];
+    float x, y, z;
+    apply_t(A.T, q.x, q.y, q.z, x, y, z);
+    const float4 p = A.tgt[sl];
+    const float d2 = winner_d2(x, y, z, p);
+    const double pd[3] = {double(p.x), double(p.y), double(p.z)};
+    s[0] += 1.0;
+    s[1] += double(d2);
+    int o = 5;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      s[2 + a] += pd[a];
+#pragma unroll
+      for (int b = a; b < 3; ++b) s[o++] += pd[a] * pd[b];                  // exact products (24 + 24 bits)
+    }
+  }
+  block_row<NS, kPlanePitch>(s, A.slab);
+}
+
+// the plane slab's nb rows -> 11 information sums, in a fixed order: 23 parts per column (rows part, part + 23, ...), then
+// the parts in order
+__global__ __launch_bounds__(kBlock) void k_final_info(const double* slab, int nb, double* out) {
+  slab_total<S4P_ICP_INFO_NSUMS, kPlanePitch>(slab, nb, out);
 }
 
 // correspondence rejection (include/s4p_icp_reject.h): the per-point answers of s4p_icp_rejection, from the lanes of a

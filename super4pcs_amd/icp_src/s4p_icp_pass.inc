@@ -36,14 +36,14 @@ int32_t robust_cfg(s4p_icp_ctx* h, int32_t metric, const s4p_icp_robust* R, Robu
 }
 
 // What a sums call or a refine minimises: the metric, its parameter, and for the robust variants the validated loss.
-enum Metric { kPoint = 0, kPlane = 1, kGicp = 2, kColor = 3, kSymm = 4 };
+enum Metric { kPoint = 0, kPlane = 1, kGicp = 2, kColor = 3, kSymm = 4, kInfo = 5 };   // kInfo: the information sums, no refine
 struct PassKind {
   int metric = kPoint;
   double param = 0.0;       // generalized: epsilon; coloured: lambda
   bool robust = false;      // point / plane on the weighted sums of cfg
   RobustCfg cfg;
   bool plane() const { return metric != kPoint; }                                  // the 31 sums and their 6x6 solve
-  int nsums() const { return plane() ? S4P_ICP_PLANE_NSUMS : S4P_ICP_NSUMS; }
+  int nsums() const { return metric == kInfo ? S4P_ICP_INFO_NSUMS : (plane() ? S4P_ICP_PLANE_NSUMS : S4P_ICP_NSUMS); }
 };
 
 // the sums of one pass on the host; n: the correspondence count (sums[0], or the robust count with w > 0)
@@ -57,6 +57,7 @@ int32_t ready_for(s4p_icp_ctx* h, const PassKind& K) {
   if (K.metric == kGicp) return gicp_ready(h, K.param);
   if (K.metric == kColor) return color_ready(h, K.param);
   if (K.metric == kSymm) return symm_ready(h);
+  if (K.metric == kInfo) return ready(h);
   return K.plane() ? plane_ready(h) : ready(h);
 }
 
@@ -80,14 +81,16 @@ bool weighted(const s4p_icp_ctx* h, const PassKind& K) { return K.robust || (h->
 int32_t prepare(s4p_icp_ctx* h, const float4* src, const PassKind* K) {
   // gicp: a metric that reads the source normals (generalized, symmetric)
   const bool rej = h->rej_on || !K, gicp = K && (K->metric == kGicp || K->metric == kSymm), color = K && K->metric == kColor;
+  const bool info = K && K->metric == kInfo;
   const bool nm = rej && h->rej.normal_mode != S4P_ICP_REJECT_NORMALS_OFF;
   if (nm && !h->has_normals) return fail(h, S4P_ICP_ERR_STATE, "rejection by normals: target normals first (set_target_normals or estimate_normals)");
   if (nm && !h->has_src_normals) return fail(h, S4P_ICP_ERR_STATE, "rejection by normals: source normals first (set_source_normals)");
-  if (rej || gicp || color || (K && K->robust)) {            // a split pass: k_search's slots and keys
+  if (rej || gicp || color || info || (K && K->robust)) {            // a split pass: k_search's slots and keys
     ICP_HIP(h->rslot.ensure(size_t(h->n_q)));
     ICP_HIP(h->rkey.ensure(size_t(h->n_q)));
   }
-  if (rej || (K && K->plane())) if (int32_t rc = plane_slab(h)) return rc;
+  // the information pass writes its 11 sums into rows of the plane slab (kInfo also counts as plane() below: metric != kPoint)
+  if (rej || info || (K && K->plane())) if (int32_t rc = plane_slab(h)) return rc;
   if (K && weighted(h, *K)) {
     constexpr int kOut = S4P_ICP_PLANE_NSUMS + S4P_ICP_ROBUST_NINFO;
     ICP_HIP(h->rhist.ensure(kDigits * kBins));
@@ -229,6 +232,26 @@ int32_t color_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double lambda
   ICP_LAUNCH(k_color_sum, nb, A);
   ICP_LAUNCH(k_final_plane, 1, h->pslab, nb, h->dsum);
   return finish_pass(h, h->dsum, h->hsum, S4P_ICP_COLOR_NSUMS, out);
+}
+
+// one information pass (include/s4p_icp_info.h): the search, the 11 sums streamed from the slots
+int32_t info_pass(s4p_icp_ctx* h, const Tf& T, const float4* src, double* out) {
+  if (int32_t rc = launch_search(h, T, src, false)) return rc;
+  InfoArgs A;
+  A.T = T; A.src = src; A.tgt = h->g.tgt; A.n = uint64_t(h->n_q); A.slot = h->rslot; A.slab = h->pslab;
+  const int nb = blocks_for(h->n_q);
+  ICP_LAUNCH(k_info_sum, nb, A);
+  ICP_LAUNCH(k_final_info, 1, h->pslab, nb, h->dsum);
+  return finish_pass(h, h->dsum, h->hsum, S4P_ICP_INFO_NSUMS, out);
+}
+
+// The information sums of the source as uploaded for T: readiness, prepare, one pass.
+int32_t info_call(s4p_icp_ctx* h, const Tf& T, double* sums) {
+  PassKind K;
+  K.metric = kInfo;
+  if (int32_t rc = ready_for(h, K)) return rc;
+  if (int32_t rc = prepare(h, h->src, &K)) return rc;
+  return info_pass(h, T, h->src, sums);
 }
 
 // The fused passes come last of the passes: template kernels are emitted in the order of their first launch in this file,
