@@ -7,7 +7,7 @@
 //             [--icp iterations] [--icp-dist max_distance] [--icp-metric point|plane|gicp|symmetric|color] [--icp-normal-radius r]
 //             [--icp-gicp-epsilon e] [--icp-color-lambda l]
 //             [--icp-loss none|trimmed|huber|tukey] [--icp-trim fraction] [--icp-loss-scale s]
-//             [--estimate-normals k] [--estimate-normals-radius r]
+//             [--estimate-normals k] [--estimate-normals-radius r] [--orient-normals k] [--orient-viewpoint x,y,z]
 //             [--remove-outliers k] [--remove-outliers-std ratio]
 //             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K] [--icp-information file]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
@@ -23,6 +23,10 @@
 // --estimate-normals k gives both inputs k-nearest-neighbour normals (algorithms/normals.h, within r if given) before the
 // matcher runs, replacing the normals read from the files for matching only (-r writes the files' own): -a then filters on
 // them, and --icp-metric plane uses P's when all of them are nonzero.
+// --orient-normals k (needs --estimate-normals) gives the estimated normals of each input one consistent sign
+// (algorithms/normals.h, OrientNormals: include/s4p_normals_orient.h) right after the estimation: outward, or, with
+// --orient-viewpoint x,y,z, facing that position, taken in each file's own coordinates (scans taken from the origin).  With it
+// an --icp-normal-angle filter compares the normals with their sign (ICPOptions::normals_oriented).
 // --remove-outliers k removes the statistical outliers of both inputs (algorithms/outliers.h: mean distance to the k nearest
 // other points above mean + ratio * stddev, ratio --remove-outliers-std, default 2) right after loading, before
 // --estimate-normals, the matcher and ICP; -r then writes the filtered, registered second input.  Faces index the vertex
@@ -185,6 +189,15 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       EstimateNormals(Q.points, nopt);
       log.Log<Utils::Verbose>("Estimated normals: k ", opt.normals_k, ", radius ", opt.normals_radius);
     }
+    if (opt.orient_k > 0) {
+      NormalOrientationOptions oopt;
+      oopt.k = opt.orient_k;
+      oopt.use_viewpoint = opt.orient_viewpoint_set;
+      for (int a = 0; a < 3; ++a) oopt.viewpoint[a] = opt.orient_viewpoint[a];
+      const size_t fp = OrientNormals(P.points, oopt), fq = OrientNormals(Q.points, oopt);
+      log.Log<Utils::Verbose>("Oriented normals: k ", opt.orient_k, opt.orient_viewpoint_set ? ", towards the viewpoint: " : ", outward: ", fp,
+                              " of input1 flipped, ", fq, " of input2");
+    }
     std::vector<Point3D> Q0;                                // the second input in its own frame: the matcher moves Q.points
     if (opt.icp_iterations > 0 && !opt.icp_scales.empty()) Q0 = Q.points;
     std::vector<Point3D> Qown;                              // --icp-information: the same, kept as it is
@@ -222,6 +235,7 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       icp.loss_scale = opt.icp_loss_scale;
       icp.reciprocal = opt.icp_reciprocal;
       icp.normal_angle_deg = opt.icp_normal_angle;
+      icp.normals_oriented = opt.orient_k > 0;
       if (!opt.icp_scales.empty()) {
         std::vector<ICPLevel> levels;
         for (double v : opt.icp_scales) {

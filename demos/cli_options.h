@@ -45,6 +45,9 @@ struct Options {
   int normals_k = 0;                                         // --estimate-normals k  normals of both inputs on the device (0: off)
   double normals_radius = -1;                                // --estimate-normals-radius r  (default: unbounded)
   bool normals_radius_set = false;
+  int orient_k = 0;                                          // --orient-normals k  consistent orientation of the estimated normals (0: off)
+  bool orient_viewpoint_set = false;                         // --orient-viewpoint x,y,z  (needs --orient-normals; default: outward)
+  double orient_viewpoint[3] = {0, 0, 0};
   int outliers_k = 0;                                        // --remove-outliers k  statistical outlier removal of both inputs (0: off)
   double outliers_std = 2.0;                                 // --remove-outliers-std ratio  (needs k)
   bool outliers_std_set = false;
@@ -155,6 +158,23 @@ inline const Flag* flag_table(size_t* n) {
          o.normals_radius_set = true;
          if (end == v[0] || *end != '\0' || !(r > 0) || !(r < 3.0e38)) o.bad_value = true; else o.normals_radius = r;
        }},
+      {"--orient-normals", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long k = std::strtol(v[0], &end, 10);
+         if (end == v[0] || *end != '\0' || k < 1 || k > 32) o.bad_value = true; else o.orient_k = int(k);
+       }},
+      {"--orient-viewpoint", 1, [](Options& o, char** v) {
+         // x,y,z: three finite numbers that fit a float
+         o.orient_viewpoint_set = true;
+         const char* p = v[0];
+         for (int a = 0; a < 3; ++a) {
+           char* end = nullptr;
+           const double c = std::strtod(p, &end);
+           if (end == p || *end != (a < 2 ? ',' : '\0') || !std::isfinite(c) || !(std::fabs(c) < 3.0e38)) { o.bad_value = true; return; }
+           o.orient_viewpoint[a] = c;
+           p = end + 1;
+         }
+       }},
       {"--remove-outliers", 1, [](Options& o, char** v) {
          char* end = nullptr;
          const long k = std::strtol(v[0], &end, 10);
@@ -220,6 +240,8 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.bad_value) return Parse::Bad;
   if (o.normals_radius_set && o.normals_k == 0) return Parse::Bad;    // the radius needs --estimate-normals
   if (o.outliers_std_set && o.outliers_k == 0) return Parse::Bad;      // the ratio needs --remove-outliers
+  if (o.orient_k > 0 && o.normals_k == 0) return Parse::Bad;           // --orient-normals needs --estimate-normals
+  if (o.orient_viewpoint_set && o.orient_k == 0) return Parse::Bad;    // --orient-viewpoint needs --orient-normals
   if (o.icp_trim_set && o.icp_loss != 1) return Parse::Bad;            // --icp-trim needs --icp-loss trimmed
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
@@ -278,6 +300,11 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t    (multi-start ICP: the matcher's K best distinct poses, its own result first, refined in one batch; the one with\n");
   std::fprintf(stderr, "\t     the most correspondences on the full clouds, then the least rmse, is kept; --icp-metric point or plane only, no\n");
   std::fprintf(stderr, "\t     --icp-loss, no pair rejection; with --icp-scales the batch is the coarsest level)\n");
+  std::fprintf(stderr, "\t[ --orient-normals k (1..32, needs --estimate-normals; off) ] [ --orient-viewpoint x,y,z (needs --orient-normals; outward) ]\n");
+  std::fprintf(stderr, "\t    (one consistent sign for the estimated normals of each input, right after the estimation: signs spread over the\n");
+  std::fprintf(stderr, "\t     graph of the k nearest neighbours from an anchor that faces away from the centre of the input's bounds, or faces\n");
+  std::fprintf(stderr, "\t     the viewpoint, the same coordinates in each file's own frame: that suits scans taken from the origin; then\n");
+  std::fprintf(stderr, "\t     --icp-normal-angle compares the normals with their sign, in [0, 90] degrees)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -8,6 +8,7 @@
 //               the cloud as cell-ordered float4 and the [begin, end) of every cell.
 //   lists and outlier removal (include/s4p_knn.h): s4p_knn.inc, on the same cloud and grid.
 //   voxel-grid downsampling (include/s4p_voxel.h): s4p_voxel.inc, of a cloud passed per call, on the context's stream.
+//   normal orientation (include/s4p_normals_orient.h): s4p_orient.inc, a minimum spanning forest over the lists' graph.
 //   estimate    queries in cell order (the cloud itself, or k_cell_keys + sort + k_gather of the caller's queries) ->
 //               k_knn_normals<K>: one lane per query, ring search with conservative box pruning, the k best (d2, index)
 //               sorted in registers, covariance in double, 3x3 Jacobi, the normal scattered to the caller's order.
@@ -333,6 +334,7 @@ struct s4p_normals_ctx {
   GridDev g{};
   uint64_t ncell = 0;
   double spacing = 0.0;
+  float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};      // the cloud's bounds (s4p_orient.inc: the outward centre)
   float4* pos = nullptr;             // caller order
   float4* pts = nullptr;             // cell order
   uint2* range = nullptr;
@@ -493,6 +495,7 @@ int32_t set_cloud_impl(s4p_normals_ctx* h, const float* x, const float* y, const
     hh *= 1.25;
   }
   h->spacing = spacing;
+  for (int a = 0; a < 3; ++a) { h->lo[a] = lo[a]; h->hi[a] = hi[a]; }
   h->g.ox = lo[0]; h->g.oy = lo[1]; h->g.oz = lo[2];
   h->g.nx = dims[0]; h->g.ny = dims[1]; h->g.nz = dims[2];
   uint32_t *keys, *vals, *keys2, *vals2;
@@ -594,6 +597,7 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
 
 #include "s4p_knn.inc"                   // include/s4p_knn.h: neighbour lists and outlier removal on the same context
 #include "s4p_voxel.inc"                 // include/s4p_voxel.h: voxel-grid downsampling on the context's stream and arena
+#include "s4p_orient.inc"                // include/s4p_normals_orient.h: consistent normal orientation on the lists of s4p_knn.inc
 
 extern "C" {
 
