@@ -39,8 +39,8 @@
 #include "s4p_icp_symm.h"
 #include "s4p_icp_color.h"
 #include "s4p_icp_reject.h"
-#include "s4p_normals.h"
 #include "super4pcs/algorithms/match4pcsBase.h"
+#include "super4pcs/algorithms/normals_handle.h"
 
 namespace GlobalRegistration {
 
@@ -91,8 +91,42 @@ struct ICPResult {
 
 namespace detail {
 
+// One s4p_icp context; every message starts with "<who> (MI355X): ".
+struct IcpHandle {
+  s4p_icp_ctx* h = nullptr;
+  const char* who;
+  explicit IcpHandle(const char* w, int device) : who(w) {
+    if (s4p_icp_create(device, &h) != S4P_ICP_OK) throw std::runtime_error(std::string(who) + " (MI355X): " + s4p_icp_last_error(nullptr));
+  }
+  IcpHandle(const IcpHandle&) = delete;
+  IcpHandle& operator=(const IcpHandle&) = delete;
+  ~IcpHandle() { s4p_icp_destroy(h); }
+  void check(int32_t rc) const {
+    if (rc != S4P_ICP_OK) throw std::runtime_error(std::string(who) + " (MI355X): " + s4p_icp_last_error(h));
+  }
+};
+
+inline void icp_set_target(const IcpHandle& H, const std::vector<float> (&p)[3], double max_distance) {
+  H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(p[0].size()), float(max_distance)));
+}
+
+inline void icp_set_source(const IcpHandle& H, const std::vector<float> (&q)[3]) {
+  H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(q[0].size())));
+}
+
+// the cloud's own normals as SoA when every point has a nonzero one
+inline bool icp_own_normals(const std::vector<Point3D>& pts, std::vector<float> (&n)[3]) {
+  for (const Point3D& pt : pts) {
+    const auto& nv = pt.normal();
+    if (!(nv(0) != 0 || nv(1) != 0 || nv(2) != 0)) return false;
+  }
+  for (int k = 0; k < 3; ++k) n[k].resize(pts.size());
+  for (size_t i = 0; i < pts.size(); ++i) for (int k = 0; k < 3; ++k) n[k][i] = float(pts[i].normal()(k));
+  return true;
+}
+
 // EstimateNormals' computation (k nearest neighbours, no radius) on SoA positions, with libsuper4pcs_normals.so bound at run
-// time: out = n x 3 floats.
+// time: out = n x 3 floats.  Its messages say RefineICP whoever calls.
 inline void icp_knn_normals(const std::vector<float> (&c)[3], int k, int device, std::vector<float>* out) {
   void* lib = nullptr;
   auto sym = [&lib](const char* name) -> void* {
@@ -120,6 +154,135 @@ inline void icp_knn_normals(const std::vector<float> (&c)[3], int k, int device,
   if (rc != S4P_NORMALS_OK) throw std::runtime_error("RefineICP (MI355X): " + err);
 }
 
+// the radius of the target's estimated normals and colour gradients
+inline double icp_normal_radius(const ICPOptions& o) { return o.normal_radius > 0 ? o.normal_radius : o.max_distance; }
+
+// Target normals: P's own, else estimated on the device with at least 6 neighbours.  RegisterMultiway does not come here: it
+// never reads a scan's own normals and always estimates.
+inline void icp_target_normals(const IcpHandle& H, const std::vector<Point3D>& P, const ICPOptions& o) {
+  std::vector<float> n[3];
+  if (icp_own_normals(P, n)) H.check(s4p_icp_set_target_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(P.size())));
+  else H.check(s4p_icp_estimate_normals(H.h, float(icp_normal_radius(o)), 6));
+}
+
+// icp_knn_normals' n x 3 floats as the source normals
+inline void icp_set_knn_normals(const IcpHandle& H, const std::vector<float>& est) {
+  const size_t nq = est.size() / 3;
+  std::vector<float> n[3];
+  for (int k = 0; k < 3; ++k) n[k].resize(nq);
+  for (size_t i = 0; i < nq; ++i) for (int k = 0; k < 3; ++k) n[k][i] = est[3 * i + size_t(k)];
+  H.check(s4p_icp_set_source_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(nq)));
+}
+
+// Source normals: Q's own, else the 16-nearest-neighbour ones of the positions q.  rot (row-major 3x3, or null) rotates the
+// own ones, in double as (m0 * x + m1 * y) + m2 * z and then rounded to float: RefineICP passes the linear part of the
+// pose Q was moved by, ICPInformation passes null because the library rotates them with its T.
+inline void icp_source_normals(const IcpHandle& H, const std::vector<Point3D>& Q, const std::vector<float> (&q)[3], int device,
+                               const double* rot) {
+  std::vector<float> n[3];
+  if (!icp_own_normals(Q, n)) {
+    std::vector<float> est;
+    icp_knn_normals(q, 16, device, &est);
+    icp_set_knn_normals(H, est);
+    return;
+  }
+  for (size_t i = 0; rot && i < Q.size(); ++i) {
+    const double x = double(n[0][i]), y = double(n[1][i]), z = double(n[2][i]);
+    for (int a = 0; a < 3; ++a) n[a][i] = float((rot[3 * a] * x + rot[3 * a + 1] * y) + rot[3 * a + 2] * z);
+  }
+  H.check(s4p_icp_set_source_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(Q.size())));
+}
+
+// The rejection flags as the library takes them; true when one is set.  Throws for an angle out of range, so where it is
+// called decides which error a caller without a device sees: RefineICP calls it after its uploads (the device's),
+// ICPInformation and RegisterMultiway before they ask for a device (the angle's).
+inline bool icp_rejection(const ICPOptions& o, s4p_icp_reject* rej, const char* who) {
+  const bool by_normals = o.normal_angle_deg >= 0;
+  if (by_normals && !(o.normal_angle_deg <= (o.normals_oriented ? 180.0 : 90.0)))
+    throw std::invalid_argument(std::string(who) + ": normal_angle_deg must be at most 90 (oriented normals: 180)");
+  s4p_icp_reject_defaults(rej);
+  rej->reciprocal = o.reciprocal ? 1 : 0;
+  if (by_normals) {
+    rej->normal_mode = o.normals_oriented ? S4P_ICP_REJECT_NORMALS_ORIENTED : S4P_ICP_REJECT_NORMALS_UNORIENTED;
+    const double c = std::cos(o.normal_angle_deg * (3.14159265358979323846 / 180.0));
+    const double lo = o.normals_oriented ? -1.0 : 0.0;
+    rej->normal_cos = c < lo ? lo : (c > 1.0 ? 1.0 : c);
+  }
+  return o.reciprocal || by_normals;
+}
+
+// rgb() as the coloured metric's intensity
+inline void icp_intensity(const std::vector<Point3D>& pts, std::vector<float>* out) {
+  out->resize(pts.size());
+  for (size_t i = 0; i < pts.size(); ++i) {
+    const auto& c = pts[i].rgb();
+    if (c(0) < 0) throw std::invalid_argument("RefineICP: the coloured metric needs a colour at every point of P and Q");
+    (*out)[i] = float(((double(c(0)) + double(c(1))) + double(c(2))) / 765.0);
+  }
+}
+
+inline s4p_icp_params icp_params(const ICPOptions& o) {
+  s4p_icp_params prm;
+  s4p_icp_default_params(&prm);
+  prm.max_iterations = o.max_iterations;
+  prm.min_correspondences = o.min_correspondences;
+  prm.rel_tol = o.rel_tol;
+  return prm;
+}
+
+inline ICPResult icp_result(const s4p_icp_result& r) {
+  ICPResult o;
+  o.iterations = r.iterations; o.status = r.status; o.n_corr = r.n_corr; o.rmse = r.rmse; o.fitness = r.fitness;
+  o.rmse_history.assign(r.history_rmse, r.history_rmse + r.history_len);
+  return o;
+}
+
+// The refine of o.metric and o.loss from the pose T16 (row-major, refined in place).
+inline s4p_icp_result icp_refine(const IcpHandle& H, const ICPOptions& o, double* T16) {
+  const s4p_icp_params prm = icp_params(o);
+  const bool plane = o.metric == ICPMetric::PointToPlane;
+  s4p_icp_result r;
+  if (o.loss != ICPLoss::None) {
+    const int32_t loss = o.loss == ICPLoss::Trimmed ? S4P_ICP_LOSS_TRIMMED : (o.loss == ICPLoss::Huber ? S4P_ICP_LOSS_HUBER : S4P_ICP_LOSS_TUKEY);
+    s4p_icp_robust rob;
+    s4p_icp_robust_defaults(&rob, loss);
+    rob.trim_fraction = o.trim_fraction;
+    rob.scale = o.loss_scale;
+    H.check(s4p_icp_refine_robust(H.h, &prm, plane ? S4P_ICP_METRIC_PLANE : S4P_ICP_METRIC_POINT, &rob, T16, &r, nullptr));
+  } else if (o.metric == ICPMetric::Generalized) H.check(s4p_icp_refine_gicp(H.h, &prm, o.gicp_epsilon, T16, &r));
+  else if (o.metric == ICPMetric::Symmetric) H.check(s4p_icp_refine_symm(H.h, &prm, T16, &r));
+  else if (o.metric == ICPMetric::Colored) H.check(s4p_icp_refine_color(H.h, &prm, o.color_lambda, T16, &r));
+  else H.check(plane ? s4p_icp_refine_plane(H.h, &prm, T16, &r) : s4p_icp_refine(H.h, &prm, T16, &r));
+  return r;
+}
+
+// Moves the SoA positions q by T16 on the device (k_apply's rounding order) and writes them into Q.
+inline void icp_apply(const IcpHandle& H, const double* T16, std::vector<float> (&q)[3], std::vector<Point3D>* Q) {
+  H.check(s4p_icp_apply(H.h, T16, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
+  for (size_t i = 0; i < Q->size(); ++i) { (*Q)[i].x() = q[0][i]; (*Q)[i].y() = q[1][i]; (*Q)[i].z() = q[2][i]; }
+}
+
+// C = A B for row-major 4x4 doubles, every entry summed over k = 0..3 from the left.  The one product of the facade: the
+// poses that RefineICP, Compose, TopPoses::StartsAfter and RegisterMultiway compose have the same bits.  C is neither A nor B.
+inline void icp_product16(const double* A, const double* B, double* C) {
+  for (int a = 0; a < 4; ++a)
+    for (int b = 0; b < 4; ++b) {
+      double v = 0.0;
+      for (int k = 0; k < 4; ++k) v += A[4 * a + k] * B[4 * k + b];
+      C[4 * a + b] = v;
+    }
+}
+
+template <typename Matrix>
+inline void icp_to16(const Matrix& M, double* out) {
+  for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) out[4 * a + b] = double(M(a, b));
+}
+
+template <typename Matrix>
+inline void icp_from16(const double* v, Matrix& M) {
+  for (int a = 0; a < 4; ++a) for (int b = 0; b < 4; ++b) M(a, b) = Match4PCSBase::Scalar(v[4 * a + b]);
+}
+
 }  // namespace detail
 
 // Q as it stands after ComputeTransformation (already moved).  Finds dT, moves Q in place (in k_apply's rounding order)
@@ -128,6 +291,7 @@ inline void icp_knn_normals(const std::vector<float> (&c)[3], int k, int device,
 // the generalized, symmetric or coloured metric, or the coloured metric on a cloud with a point that has no colour.
 inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, Match4PCSBase::MatrixRef transformation,
                        const ICPOptions& options, ICPResult* result = nullptr) {
+  // What is refused before a device is asked for, in this order: the empty cloud, the three "takes no loss", the colours.
   if (Q == nullptr || P.empty() || Q->empty()) throw std::invalid_argument("RefineICP: empty cloud");
   const bool gicp = options.metric == ICPMetric::Generalized;
   if (gicp && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the generalized metric takes no loss");
@@ -137,134 +301,39 @@ inline float RefineICP(const std::vector<Point3D>& P, std::vector<Point3D>* Q, M
   if (colored && options.loss != ICPLoss::None) throw std::invalid_argument("RefineICP: the coloured metric takes no loss");
   std::vector<float> ip, iq;
   if (colored) {
-    auto intensity = [](const std::vector<Point3D>& pts, std::vector<float>* out) {
-      out->resize(pts.size());
-      for (size_t i = 0; i < pts.size(); ++i) {
-        const auto& c = pts[i].rgb();
-        if (c(0) < 0) throw std::invalid_argument("RefineICP: the coloured metric needs a colour at every point of P and Q");
-        (*out)[i] = float(((double(c(0)) + double(c(1))) + double(c(2))) / 765.0);
-      }
-    };
-    intensity(P, &ip);
-    intensity(*Q, &iq);
+    detail::icp_intensity(P, &ip);
+    detail::icp_intensity(*Q, &iq);
   }
-  struct Handle {
-    s4p_icp_ctx* h = nullptr;
-    ~Handle() { s4p_icp_destroy(h); }
-    void check(int32_t rc) const {
-      if (rc != S4P_ICP_OK) throw std::runtime_error(std::string("RefineICP (MI355X): ") + s4p_icp_last_error(h));
-    }
-  } H;
-  if (s4p_icp_create(options.device, &H.h) != S4P_ICP_OK)
-    throw std::runtime_error(std::string("RefineICP (MI355X): ") + s4p_icp_last_error(nullptr));
-  auto soa = [](const std::vector<Point3D>& pts, std::vector<float> (&c)[3]) {
-    for (int k = 0; k < 3; ++k) c[k].resize(pts.size());
-    for (size_t i = 0; i < pts.size(); ++i) { c[0][i] = pts[i].x(); c[1][i] = pts[i].y(); c[2][i] = pts[i].z(); }
-  };
+  const detail::IcpHandle H("RefineICP", options.device);
   std::vector<float> p[3], q[3];
-  soa(P, p);
-  soa(*Q, q);
-  H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
-  H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
-  const bool plane = options.metric == ICPMetric::PointToPlane;
+  detail::cloud_soa(P, p);
+  detail::cloud_soa(*Q, q);
+  detail::icp_set_target(H, p, options.max_distance);
+  detail::icp_set_source(H, q);
+  // The angle's range is checked here, after the device and the uploads (ICPInformation and RegisterMultiway check it first):
+  // without a device RefineICP reports the device, not the angle.
+  s4p_icp_reject rej;
+  const bool reject = detail::icp_rejection(options, &rej, "RefineICP");
   const bool by_normals = options.normal_angle_deg >= 0;
-  if (by_normals && !(options.normal_angle_deg <= (options.normals_oriented ? 180.0 : 90.0)))
-    throw std::invalid_argument("RefineICP: normal_angle_deg must be at most 90 (oriented normals: 180)");
-  if (plane || gicp || symm || colored || by_normals) {
-    bool all = true;
-    for (const Point3D& pt : P) {
-      const auto& nv = pt.normal();
-      if (!(nv(0) != 0 || nv(1) != 0 || nv(2) != 0)) { all = false; break; }
-    }
-    if (all) {
-      std::vector<float> n[3];
-      for (int k = 0; k < 3; ++k) n[k].resize(P.size());
-      for (size_t i = 0; i < P.size(); ++i) for (int k = 0; k < 3; ++k) n[k][i] = float(P[i].normal()(k));
-      H.check(s4p_icp_set_target_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(P.size())));
-    } else {
-      const double r = options.normal_radius > 0 ? options.normal_radius : options.max_distance;
-      H.check(s4p_icp_estimate_normals(H.h, float(r), 6));
-    }
-  }
-  if (gicp || symm || by_normals) {
-    bool all = true;
-    for (const Point3D& pt : *Q) {
-      const auto& nv = pt.normal();
-      if (!(nv(0) != 0 || nv(1) != 0 || nv(2) != 0)) { all = false; break; }
-    }
-    std::vector<float> n[3];
-    for (int k = 0; k < 3; ++k) n[k].resize(Q->size());
-    if (all) {                                     // Q's own, rotated into the frame Q was moved to
-      double m[3][3];
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) m[a][b] = double(transformation(a, b));
-      for (size_t i = 0; i < Q->size(); ++i) {
-        const auto& nv = (*Q)[i].normal();
-        const double x = double(nv(0)), y = double(nv(1)), z = double(nv(2));
-        for (int a = 0; a < 3; ++a) n[a][i] = float((m[a][0] * x + m[a][1] * y) + m[a][2] * z);
-      }
-    } else {
-      std::vector<float> est;
-      detail::icp_knn_normals(q, 16, options.device, &est);
-      for (size_t i = 0; i < Q->size(); ++i) for (int k = 0; k < 3; ++k) n[k][i] = est[3 * i + k];
-    }
-    H.check(s4p_icp_set_source_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(Q->size())));
+  double T[16];
+  detail::icp_to16(transformation, T);
+  if (options.metric != ICPMetric::PointToPoint || by_normals) detail::icp_target_normals(H, P, options);
+  if (gicp || symm || by_normals) {                // Q's own normals are in the file's frame: rotated into the one Q was moved to
+    const double rot[9] = {T[0], T[1], T[2], T[4], T[5], T[6], T[8], T[9], T[10]};
+    detail::icp_source_normals(H, *Q, q, options.device, rot);
   }
   if (colored) {
     H.check(s4p_icp_set_target_intensity(H.h, ip.data(), int64_t(P.size())));
     H.check(s4p_icp_set_source_intensity(H.h, iq.data(), int64_t(Q->size())));
-    const double r = options.normal_radius > 0 ? options.normal_radius : options.max_distance;
-    H.check(s4p_icp_estimate_color_gradients(H.h, float(r), 6));
+    H.check(s4p_icp_estimate_color_gradients(H.h, float(detail::icp_normal_radius(options)), 6));
   }
-  if (options.reciprocal || by_normals) {
-    s4p_icp_reject rej;
-    s4p_icp_reject_defaults(&rej);
-    rej.reciprocal = options.reciprocal ? 1 : 0;
-    if (by_normals) {
-      rej.normal_mode = options.normals_oriented ? S4P_ICP_REJECT_NORMALS_ORIENTED : S4P_ICP_REJECT_NORMALS_UNORIENTED;
-      const double c = std::cos(options.normal_angle_deg * (3.14159265358979323846 / 180.0));
-      const double lo = options.normals_oriented ? -1.0 : 0.0;
-      rej.normal_cos = c < lo ? lo : (c > 1.0 ? 1.0 : c);
-    }
-    H.check(s4p_icp_set_rejection(H.h, &rej));
-  }
-  s4p_icp_params prm;
-  s4p_icp_default_params(&prm);
-  prm.max_iterations = options.max_iterations;
-  prm.min_correspondences = options.min_correspondences;
-  prm.rel_tol = options.rel_tol;
-  double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  s4p_icp_result r;
-  if (options.loss == ICPLoss::None) {
-    if (gicp) H.check(s4p_icp_refine_gicp(H.h, &prm, options.gicp_epsilon, dT, &r));
-    else if (symm) H.check(s4p_icp_refine_symm(H.h, &prm, dT, &r));
-    else if (colored) H.check(s4p_icp_refine_color(H.h, &prm, options.color_lambda, dT, &r));
-    else H.check(plane ? s4p_icp_refine_plane(H.h, &prm, dT, &r) : s4p_icp_refine(H.h, &prm, dT, &r));
-  } else {
-    const int32_t loss = options.loss == ICPLoss::Trimmed ? S4P_ICP_LOSS_TRIMMED
-                         : (options.loss == ICPLoss::Huber ? S4P_ICP_LOSS_HUBER : S4P_ICP_LOSS_TUKEY);
-    s4p_icp_robust rob;
-    s4p_icp_robust_defaults(&rob, loss);
-    rob.trim_fraction = options.trim_fraction;
-    rob.scale = options.loss_scale;
-    H.check(s4p_icp_refine_robust(H.h, &prm, plane ? S4P_ICP_METRIC_PLANE : S4P_ICP_METRIC_POINT, &rob, dT, &r, nullptr));
-  }
-  H.check(s4p_icp_apply(H.h, dT, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
-  for (size_t i = 0; i < Q->size(); ++i) { (*Q)[i].x() = q[0][i]; (*Q)[i].y() = q[1][i]; (*Q)[i].z() = q[2][i]; }
-  double M[16];
-  for (int a = 0; a < 4; ++a)
-    for (int b = 0; b < 4; ++b) {
-      double v = 0.0;
-      for (int k = 0; k < 4; ++k) v += dT[4 * a + k] * double(transformation(k, b));
-      M[4 * a + b] = v;
-    }
-  using Scalar = Match4PCSBase::Scalar;
-  for (int a = 0; a < 4; ++a)
-    for (int b = 0; b < 4; ++b) transformation(a, b) = Scalar(M[4 * a + b]);
-  if (result) {
-    result->iterations = r.iterations; result->status = r.status; result->n_corr = r.n_corr;
-    result->rmse = r.rmse; result->fitness = r.fitness;
-    result->rmse_history.assign(r.history_rmse, r.history_rmse + r.history_len);
-  }
+  if (reject) H.check(s4p_icp_set_rejection(H.h, &rej));
+  double dT[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, M[16];
+  const s4p_icp_result r = detail::icp_refine(H, options, dT);
+  detail::icp_apply(H, dT, q, Q);
+  detail::icp_product16(dT, T, M);
+  detail::icp_from16(M, transformation);
+  if (result) *result = detail::icp_result(r);
   return float(r.fitness);
 }
 

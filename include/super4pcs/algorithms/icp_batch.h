@@ -117,7 +117,7 @@ class TopPoses {
   template <typename Matrix>
   std::vector<Match4PCSBase::MatrixType> StartsAfter(const Matrix& result) const {
     double R[16], Ri[16];
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) R[4 * r + c] = double(result(r, c));
+    detail::icp_to16(result, R);
     for (int k = 0; k < 16; ++k) Ri[k] = k == 15 ? 1.0 : 0.0;
     for (int r = 0; r < 3; ++r) {
       for (int c = 0; c < 3; ++c) Ri[4 * r + c] = R[4 * c + r];
@@ -130,13 +130,10 @@ class TopPoses {
     for (const Entry& e : entries_) {
       if (out.size() >= size_t(K_)) break;
       if (Same(e.M, R)) continue;
+      double S16[16];
+      detail::icp_product16(e.M, Ri, S16);
       Match4PCSBase::MatrixType S;
-      for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) {
-          double v = 0.0;
-          for (int k = 0; k < 4; ++k) v += e.M[4 * r + k] * Ri[4 * k + c];
-          S(r, c) = Match4PCSBase::Scalar(v);
-        }
+      detail::icp_from16(S16, S);
       out.push_back(S);
     }
     return out;
@@ -155,13 +152,12 @@ class TopPoses {
 
 // A * B for two facade matrices, in RefineICP's order (double, sum over k left to right)
 inline Match4PCSBase::MatrixType Compose(const Match4PCSBase::MatrixType& A, const Match4PCSBase::MatrixType& B) {
+  double a[16], b[16], c[16];
+  detail::icp_to16(A, a);
+  detail::icp_to16(B, b);
+  detail::icp_product16(a, b, c);
   Match4PCSBase::MatrixType C;
-  for (int a = 0; a < 4; ++a)
-    for (int b = 0; b < 4; ++b) {
-      double v = 0.0;
-      for (int k = 0; k < 4; ++k) v += double(A(a, k)) * double(B(k, b));
-      C(a, b) = Match4PCSBase::Scalar(v);
-    }
+  detail::icp_from16(c, C);
   return C;
 }
 
@@ -181,66 +177,33 @@ inline std::pair<Match4PCSBase::MatrixType, int> RefineICPBatch(const std::vecto
     throw std::invalid_argument("RefineICPBatch: point-to-point and point-to-plane only (the generalized, symmetric and coloured metrics have no batch form)");
   if (options.loss != ICPLoss::None) throw std::invalid_argument("RefineICPBatch: robust losses have no batch form");
   if (options.reciprocal || options.normal_angle_deg >= 0) throw std::invalid_argument("RefineICPBatch: pair rejection has no batch form");
-  struct Handle {
-    s4p_icp_ctx* h = nullptr;
-    ~Handle() { s4p_icp_destroy(h); }
-    void check(int32_t rc) const {
-      if (rc != S4P_ICP_OK) throw std::runtime_error(std::string("RefineICPBatch (MI355X): ") + s4p_icp_last_error(h));
-    }
-  } H;
-  if (s4p_icp_create(options.device, &H.h) != S4P_ICP_OK)
-    throw std::runtime_error(std::string("RefineICPBatch (MI355X): ") + s4p_icp_last_error(nullptr));
+  // all of the above is refused before a device is asked for
+  const detail::IcpHandle H("RefineICPBatch", options.device);
   std::vector<float> p[3], q[3];
-  for (int k = 0; k < 3; ++k) { p[k].resize(P.size()); q[k].resize(Q->size()); }
-  for (size_t i = 0; i < P.size(); ++i) { p[0][i] = P[i].x(); p[1][i] = P[i].y(); p[2][i] = P[i].z(); }
-  for (size_t i = 0; i < Q->size(); ++i) { q[0][i] = (*Q)[i].x(); q[1][i] = (*Q)[i].y(); q[2][i] = (*Q)[i].z(); }
-  H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(P.size()), float(options.max_distance)));
-  H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
-  if (plane) {                                     // RefineICP's rule: P's normals when all are nonzero, else estimated
-    bool all = true;
-    for (const Point3D& pt : P) {
-      const auto& nv = pt.normal();
-      if (!(nv(0) != 0 || nv(1) != 0 || nv(2) != 0)) { all = false; break; }
-    }
-    if (all) {
-      std::vector<float> n[3];
-      for (int k = 0; k < 3; ++k) n[k].resize(P.size());
-      for (size_t i = 0; i < P.size(); ++i) for (int k = 0; k < 3; ++k) n[k][i] = float(P[i].normal()(k));
-      H.check(s4p_icp_set_target_normals(H.h, n[0].data(), n[1].data(), n[2].data(), int64_t(P.size())));
-    } else {
-      const double r = options.normal_radius > 0 ? options.normal_radius : options.max_distance;
-      H.check(s4p_icp_estimate_normals(H.h, float(r), 6));
-    }
-  }
+  detail::cloud_soa(P, p);
+  detail::cloud_soa(*Q, q);
+  detail::icp_set_target(H, p, options.max_distance);
+  detail::icp_set_source(H, q);
+  if (plane) detail::icp_target_normals(H, P, options);
   s4p_icp_batch_params prm;
-  s4p_icp_default_params(&prm.icp);
-  prm.icp.max_iterations = options.max_iterations;
-  prm.icp.min_correspondences = options.min_correspondences;
-  prm.icp.rel_tol = options.rel_tol;
+  prm.icp = detail::icp_params(options);
   prm.metric = plane ? S4P_ICP_METRIC_PLANE : S4P_ICP_METRIC_POINT;
-  prm.reserved = 0;
+  prm.reserved = 0;                                // s4p_icp_default_params does not reach the batch's own fields
   const int B = int(starts.size());
   const size_t nB = starts.size();
   std::vector<double> T(nB * 16);
-  for (int b = 0; b < B; ++b)
-    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) T[size_t(b) * 16 + 4 * r + c] = double(starts[size_t(b)](r, c));
+  for (size_t b = 0; b < nB; ++b) detail::icp_to16(starts[b], &T[b * 16]);
   std::vector<s4p_icp_result> res(nB);
   std::vector<int32_t> order(nB);
   H.check(s4p_icp_refine_batch(H.h, &prm, B, T.data(), res.data(), order.data()));
   const int best = order[0];
-  H.check(s4p_icp_apply(H.h, &T[size_t(best) * 16], q[0].data(), q[1].data(), q[2].data(), int64_t(Q->size())));
-  for (size_t i = 0; i < Q->size(); ++i) { (*Q)[i].x() = q[0][i]; (*Q)[i].y() = q[1][i]; (*Q)[i].z() = q[2][i]; }
+  detail::icp_apply(H, &T[size_t(best) * 16], q, Q);
   if (results) {
-    results->assign(nB, ICPResult());
-    for (int b = 0; b < B; ++b) {
-      const s4p_icp_result& r = res[size_t(b)];
-      ICPResult& o = (*results)[size_t(b)];
-      o.iterations = r.iterations; o.status = r.status; o.n_corr = r.n_corr; o.rmse = r.rmse; o.fitness = r.fitness;
-      o.rmse_history.assign(r.history_rmse, r.history_rmse + r.history_len);
-    }
+    results->clear();
+    for (const s4p_icp_result& r : res) results->push_back(detail::icp_result(r));
   }
   Match4PCSBase::MatrixType M;
-  for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) M(r, c) = Match4PCSBase::Scalar(T[size_t(best) * 16 + 4 * r + c]);
+  detail::icp_from16(&T[size_t(best) * 16], M);
   return std::make_pair(M, best);
 }
 

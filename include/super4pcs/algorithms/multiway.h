@@ -58,15 +58,10 @@ inline Pose rigid_inverse(const Pose& X) {
   return o;
 }
 
-// A B, the sum over k = 0..3 from the left (Compose's order)
+// A B in the facade's one order (detail::icp_product16)
 inline Pose pose_product(const Pose& A, const Pose& B) {
   Pose o;
-  for (size_t a = 0; a < 4; ++a)
-    for (size_t b = 0; b < 4; ++b) {
-      double v = 0.0;
-      for (size_t k = 0; k < 4; ++k) v += A[4 * a + k] * B[4 * k + b];
-      o[4 * a + b] = v;
-    }
+  icp_product16(A.data(), B.data(), o.data());
   return o;
 }
 
@@ -93,20 +88,15 @@ inline MultiwayReport RegisterMultiway(const std::vector<std::vector<Point3D>>& 
   for (int i = 0; i + 1 < N; ++i)
     if (std::find(pairs.begin(), pairs.end(), std::make_pair(i, i + 1)) == pairs.end())
       throw std::invalid_argument("RegisterMultiway: pairs must hold every (i, i + 1)");
-  s4p_icp_reject rej;
+  s4p_icp_reject rej;                              // the angle is checked before a device is asked for (RefineICP: after)
   const bool reject = detail::icp_rejection(icp, &rej, "RegisterMultiway");
   const bool pair_normals = icp.metric == ICPMetric::Generalized || icp.metric == ICPMetric::Symmetric || icp.normal_angle_deg >= 0;
   const bool target_normals = pair_normals || icp.metric == ICPMetric::PointToPlane;
   const int min_corr = icp.min_correspondences > 1 ? icp.min_correspondences : 1;
   MultiwayReport rep;
   rep.graph.poses = *poses;
-  detail::IcpHandle H("RegisterMultiway", icp.device);
+  const detail::IcpHandle H("RegisterMultiway", icp.device);
   if (reject) H.check(s4p_icp_set_rejection(H.h, &rej));
-  s4p_icp_params prm;
-  s4p_icp_default_params(&prm);
-  prm.max_iterations = icp.max_iterations;
-  prm.min_correspondences = icp.min_correspondences;
-  prm.rel_tol = icp.rel_tol;
   std::vector<std::vector<float>> src_normals(static_cast<size_t>(N));         // 3 n floats per source that needs them, filled once
   for (int i = 0; i + 1 < N; ++i) {
     std::vector<int> sources;
@@ -114,29 +104,22 @@ inline MultiwayReport RegisterMultiway(const std::vector<std::vector<Point3D>>& 
     if (sources.empty()) continue;
     std::sort(sources.begin(), sources.end());
     std::vector<float> p[3];
-    detail::icp_soa(scans[size_t(i)], p);
-    H.check(s4p_icp_set_target(H.h, p[0].data(), p[1].data(), p[2].data(), int64_t(p[0].size()), float(icp.max_distance)));
-    if (target_normals) H.check(s4p_icp_estimate_normals(H.h, float(icp.normal_radius > 0 ? icp.normal_radius : icp.max_distance), 6));
+    detail::cloud_soa(scans[size_t(i)], p);
+    detail::icp_set_target(H, p, icp.max_distance);
+    // a scan's own normals are never read: always estimated here, and always the cached knn estimate for a source
+    if (target_normals) H.check(s4p_icp_estimate_normals(H.h, float(detail::icp_normal_radius(icp)), 6));
     const Pose Xi_inv = detail::rigid_inverse((*poses)[size_t(i)]);
     for (int j : sources) {
       std::vector<float> q[3];
-      detail::icp_soa(scans[size_t(j)], q);
-      const int64_t nq = int64_t(q[0].size());
-      H.check(s4p_icp_set_source(H.h, q[0].data(), q[1].data(), q[2].data(), nq));
+      detail::cloud_soa(scans[size_t(j)], q);
+      detail::icp_set_source(H, q);
       if (pair_normals) {
         std::vector<float>& est = src_normals[size_t(j)];
         if (est.empty()) detail::icp_knn_normals(q, 16, icp.device, &est);
-        std::vector<float> nv[3];
-        for (int k = 0; k < 3; ++k) nv[k].resize(size_t(nq));
-        for (size_t a = 0; a < size_t(nq); ++a) for (int k = 0; k < 3; ++k) nv[k][a] = est[3 * a + size_t(k)];
-        H.check(s4p_icp_set_source_normals(H.h, nv[0].data(), nv[1].data(), nv[2].data(), nq));
+        detail::icp_set_knn_normals(H, est);
       }
       Pose T = detail::pose_product(Xi_inv, (*poses)[size_t(j)]);
-      s4p_icp_result r;
-      if (icp.metric == ICPMetric::Generalized) H.check(s4p_icp_refine_gicp(H.h, &prm, icp.gicp_epsilon, T.data(), &r));
-      else if (icp.metric == ICPMetric::Symmetric) H.check(s4p_icp_refine_symm(H.h, &prm, T.data(), &r));
-      else if (icp.metric == ICPMetric::PointToPlane) H.check(s4p_icp_refine_plane(H.h, &prm, T.data(), &r));
-      else H.check(s4p_icp_refine(H.h, &prm, T.data(), &r));
+      const s4p_icp_result r = detail::icp_refine(H, icp, T.data());
       PoseGraphEdge e;
       int64_t n = 0;
       double rmse = 0.0;

@@ -17,12 +17,10 @@
 
 #include <cstdint>
 #include <stdexcept>
-#include <string>
 #include <vector>
 
-#include "s4p_normals.h"
 #include "s4p_normals_orient.h"
-#include "super4pcs/shared4pcs.h"
+#include "super4pcs/algorithms/normals_handle.h"
 
 namespace GlobalRegistration {
 
@@ -39,19 +37,8 @@ inline void EstimateNormals(std::vector<Point3D>& cloud, const NormalEstimationO
   if (cloud.empty()) return;
   if (options.k < S4P_NORMALS_MIN_K || options.k > S4P_NORMALS_MAX_K) throw std::invalid_argument("EstimateNormals: k must be in [3, 32]");
   if (!(options.radius == options.radius) || options.radius > 3.0e38) throw std::invalid_argument("EstimateNormals: radius must be finite");
-  struct Handle {
-    s4p_normals_ctx* h = nullptr;
-    ~Handle() { s4p_normals_destroy(h); }
-    void check(int32_t rc) const {
-      if (rc != S4P_NORMALS_OK) throw std::runtime_error(std::string("EstimateNormals (MI355X): ") + s4p_normals_last_error(h));
-    }
-  } H;
-  if (s4p_normals_create(options.device, &H.h) != S4P_NORMALS_OK)
-    throw std::runtime_error(std::string("EstimateNormals (MI355X): ") + s4p_normals_last_error(nullptr));
-  std::vector<float> c[3];
-  for (int a = 0; a < 3; ++a) c[a].resize(cloud.size());
-  for (size_t i = 0; i < cloud.size(); ++i) { c[0][i] = cloud[i].x(); c[1][i] = cloud[i].y(); c[2][i] = cloud[i].z(); }
-  H.check(s4p_normals_set_cloud(H.h, c[0].data(), c[1].data(), c[2].data(), int64_t(cloud.size())));
+  const detail::NormalsHandle H("EstimateNormals", options.device);
+  H.set_cloud(cloud);
   std::vector<float> out(3 * cloud.size());
   H.check(s4p_normals_estimate(H.h, options.k, float(options.radius), out.data()));
   for (size_t i = 0; i < cloud.size(); ++i) {
@@ -81,23 +68,11 @@ inline size_t OrientNormals(std::vector<Point3D>& cloud, const NormalOrientation
       throw std::invalid_argument("OrientNormals: the viewpoint must be finite");
     v[a] = float(options.viewpoint[a]);
   }
-  struct Handle {
-    s4p_normals_ctx* h = nullptr;
-    ~Handle() { s4p_normals_destroy(h); }
-    void check(int32_t rc) const {
-      if (rc != S4P_NORMALS_OK) throw std::runtime_error(std::string("OrientNormals (MI355X): ") + s4p_normals_last_error(h));
-    }
-  } H;
-  if (s4p_normals_create(options.device, &H.h) != S4P_NORMALS_OK)
-    throw std::runtime_error(std::string("OrientNormals (MI355X): ") + s4p_normals_last_error(nullptr));
+  const detail::NormalsHandle H("OrientNormals", options.device);
   const size_t n = cloud.size();
-  std::vector<float> c[3], nrm(3 * n);
-  for (int a = 0; a < 3; ++a) c[a].resize(n);
-  for (size_t i = 0; i < n; ++i) {
-    c[0][i] = cloud[i].x(); c[1][i] = cloud[i].y(); c[2][i] = cloud[i].z();
-    for (int a = 0; a < 3; ++a) nrm[3 * i + a] = cloud[i].normal()(a);
-  }
-  H.check(s4p_normals_set_cloud(H.h, c[0].data(), c[1].data(), c[2].data(), int64_t(n)));
+  std::vector<float> nrm(3 * n);
+  for (size_t i = 0; i < n; ++i) for (int a = 0; a < 3; ++a) nrm[3 * i + a] = cloud[i].normal()(a);
+  H.set_cloud(cloud);
   std::vector<uint8_t> flipped(n);
   H.check(s4p_orient_consistent(H.h, options.k, float(options.radius), options.use_viewpoint ? S4P_ORIENT_VIEWPOINT : S4P_ORIENT_OUTWARD,
                                 v, nrm.data(), flipped.data(), nullptr, nullptr));

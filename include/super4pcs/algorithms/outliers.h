@@ -12,12 +12,11 @@
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "s4p_knn.h"
-#include "super4pcs/shared4pcs.h"
+#include "super4pcs/algorithms/normals_handle.h"
 
 namespace GlobalRegistration {
 
@@ -45,19 +44,8 @@ inline size_t RemoveOutliers(std::vector<Point3D>& cloud, const OutlierRemovalOp
   }
   if (kept) kept->clear();
   if (cloud.empty()) return 0;
-  struct Handle {
-    s4p_normals_ctx* h = nullptr;
-    ~Handle() { s4p_normals_destroy(h); }
-    void check(int32_t rc) const {
-      if (rc != S4P_NORMALS_OK) throw std::runtime_error(std::string("RemoveOutliers (MI355X): ") + s4p_normals_last_error(h));
-    }
-  } H;
-  if (s4p_normals_create(options.device, &H.h) != S4P_NORMALS_OK)
-    throw std::runtime_error(std::string("RemoveOutliers (MI355X): ") + s4p_normals_last_error(nullptr));
-  std::vector<float> c[3];
-  for (int a = 0; a < 3; ++a) c[a].resize(cloud.size());
-  for (size_t i = 0; i < cloud.size(); ++i) { c[0][i] = cloud[i].x(); c[1][i] = cloud[i].y(); c[2][i] = cloud[i].z(); }
-  H.check(s4p_normals_set_cloud(H.h, c[0].data(), c[1].data(), c[2].data(), int64_t(cloud.size())));
+  const detail::NormalsHandle H("RemoveOutliers", options.device);
+  H.set_cloud(cloud);
   std::vector<uint8_t> keep(cloud.size());
   if (statistical) H.check(s4p_outliers_statistical(H.h, options.k, options.std_ratio, nullptr, keep.data(), nullptr));
   else H.check(s4p_outliers_radius(H.h, float(options.radius), options.min_neighbours, keep.data()));

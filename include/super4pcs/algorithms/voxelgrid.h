@@ -11,11 +11,10 @@
 #include <cstddef>
 #include <cstdint>
 #include <stdexcept>
-#include <string>
 #include <vector>
 
 #include "s4p_voxel.h"
-#include "super4pcs/shared4pcs.h"
+#include "super4pcs/algorithms/normals_handle.h"
 
 namespace GlobalRegistration {
 
@@ -35,15 +34,7 @@ inline size_t VoxelDownsample(std::vector<Point3D>& cloud, const VoxelGridOption
     throw std::invalid_argument("VoxelDownsample: voxel_size must be finite and > 0");
   if (voxel_of) voxel_of->clear();
   if (cloud.empty()) return 0;
-  struct Handle {
-    s4p_normals_ctx* h = nullptr;
-    ~Handle() { s4p_normals_destroy(h); }
-    void check(int32_t rc) const {
-      if (rc != S4P_NORMALS_OK) throw std::runtime_error(std::string("VoxelDownsample (MI355X): ") + s4p_normals_last_error(h));
-    }
-  } H;
-  if (s4p_normals_create(options.device, &H.h) != S4P_NORMALS_OK)
-    throw std::runtime_error(std::string("VoxelDownsample (MI355X): ") + s4p_normals_last_error(nullptr));
+  const detail::NormalsHandle H("VoxelDownsample", options.device);
   const size_t n = cloud.size();
   bool normals = true, colours = true;
   for (const Point3D& pt : cloud) {
@@ -54,9 +45,8 @@ inline size_t VoxelDownsample(std::vector<Point3D>& cloud, const VoxelGridOption
   const int nattr = (normals ? 3 : 0) + (colours ? 3 : 0);
   const int rgb_at = normals ? 3 : 0;
   std::vector<float> c[3], attr(n * size_t(nattr));
-  for (int a = 0; a < 3; ++a) c[a].resize(n);
+  detail::cloud_soa(cloud, c);
   for (size_t i = 0; i < n; ++i) {
-    c[0][i] = cloud[i].x(); c[1][i] = cloud[i].y(); c[2][i] = cloud[i].z();
     if (normals) for (int k = 0; k < 3; ++k) attr[i * nattr + k] = float(cloud[i].normal()(k));
     if (colours) for (int k = 0; k < 3; ++k) attr[i * nattr + rgb_at + k] = float(cloud[i].rgb()(k));
   }

@@ -172,6 +172,7 @@ def build_cli(force=False):
     deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB, ICP_LIB, NORMALS_LIB,
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "normals.h"),
+            os.path.join(ROOT, "include", "super4pcs", "algorithms", "normals_handle.h"),
             os.path.join(ROOT, "include", "s4p_normals_orient.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "outliers.h"),
             os.path.join(ROOT, "include", "super4pcs", "algorithms", "voxelgrid.h"),

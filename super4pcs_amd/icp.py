@@ -20,6 +20,7 @@ Clouds are (N, 3) float32 numpy arrays, or contiguous (N, 3) float32 torch tenso
 through the *_device entry points, device to device).  There is no CPU fallback: without a device, ICP() raises
 ICPError with code -2.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -244,40 +245,33 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _host_solve(name, nsums, sums, refused=None):
+    """s4p_icp_<name>(sums, dT) on the host: the 4x4 dT, or ICPError with `refused` (default: degenerate system / bad argument)."""
+    fn = getattr(load_library(), "s4p_icp_" + name)
+    s = np.ascontiguousarray(sums, np.float64).reshape(nsums)
+    out = np.empty(16, np.float64)
+    rc = fn(_dp(s), _dp(out))
+    if rc != 0:
+        raise ICPError(rc, refused or name + (": degenerate system" if rc == ERR_DEGENERATE else ": bad argument"))
+    return out.reshape(4, 4)
+
+
 def solve(sums):
     """Horn's closed form on the 17 sums (host only, no device): the 4x4 dT mapping q^ onto p'."""
-    L = load_library()
-    s = np.ascontiguousarray(sums, np.float64).reshape(NSUMS)
-    out = np.empty(16, np.float64)
-    rc = L.s4p_icp_solve(_dp(s), _dp(out))
-    if rc != 0:
-        raise ICPError(rc, "solve: n < 1")
-    return out.reshape(4, 4)
+    return _host_solve("solve", NSUMS, sums, "solve: n < 1")
 
 
 def solve_plane(sums):
     """The point-to-plane step on the 31 plane sums (host only, no device): dT = [Rodrigues(omega) | t] with A (omega, t) = b.
     Raises ICPError with code ERR_DEGENERATE when n_plane < 6 or A is not safely positive definite."""
-    L = load_library()
-    s = np.ascontiguousarray(sums, np.float64).reshape(PLANE_NSUMS)
-    out = np.empty(16, np.float64)
-    rc = L.s4p_icp_solve_plane(_dp(s), _dp(out))
-    if rc != 0:
-        raise ICPError(rc, "solve_plane: degenerate system" if rc == ERR_DEGENERATE else "solve_plane: bad argument")
-    return out.reshape(4, 4)
+    return _host_solve("solve_plane", PLANE_NSUMS, sums)
 
 
 def solve_symmetric(sums):
     """The symmetric step on the 31 symmetric sums (host only, no device; include/s4p_icp_symm.h): with A (a, t) = b solved
     as solve_plane solves it and Rh the rotation by atan |a| about a, dT = [Rh Rh | Rh (cos(atan |a|) t)].  Raises ICPError
     with code ERR_DEGENERATE where solve_plane does."""
-    L = load_library()
-    s = np.ascontiguousarray(sums, np.float64).reshape(SYMM_NSUMS)
-    out = np.empty(16, np.float64)
-    rc = L.s4p_icp_solve_symmetric(_dp(s), _dp(out))
-    if rc != 0:
-        raise ICPError(rc, "solve_symmetric: degenerate system" if rc == ERR_DEGENERATE else "solve_symmetric: bad argument")
-    return out.reshape(4, 4)
+    return _host_solve("solve_symmetric", SYMM_NSUMS, sums)
 
 
 def robust_params(loss, trim_fraction=None, scale=None, c=None):
@@ -473,6 +467,19 @@ class ICP:
         T = np.ascontiguousarray(np.asarray(T).reshape(4, 4), np.float32).reshape(16)
         return T
 
+    def _read3(self, fn, n):
+        """float32 (n, 3): the three columns that fn(h, x, y, z) fills."""
+        cols = [np.empty(n, np.float32) for _ in range(3)]
+        self._chk(fn(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
+        return np.stack(cols, axis=1)
+
+    def _sums(self, fn, T, n, *scalar):
+        """float64 (n,): fn(h, float T, [scalar,] out) for a T in the centred frame."""
+        T = self._t32(T)
+        out = np.empty(n, np.float64)
+        self._chk(fn(self.h, _fp(T), *scalar, _dp(out)))
+        return out
+
     def set_target_normals(self, N):
         """One normal per target point (N, 3), in the uploaded order: normalised in double, zero / non-finite -> 0."""
         suf, ptr, n, keep = self._cols(N)
@@ -485,17 +492,11 @@ class ICP:
 
     def target_normals(self):
         """float32 (n_P, 3): the current target normals, in the uploaded order."""
-        n = self.n_p
-        cols = [np.empty(n, np.float32) for _ in range(3)]
-        self._chk(self.L.s4p_icp_target_normals(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
-        return np.stack(cols, axis=1)
+        return self._read3(self.L.s4p_icp_target_normals, self.n_p)
 
     def plane_sums(self, T):
         """The 31 plane sums for a float T in the centred frame (layout in include/s4p_icp_plane.h)."""
-        T = self._t32(T)
-        out = np.empty(PLANE_NSUMS, np.float64)
-        self._chk(self.L.s4p_icp_plane_sums(self.h, _fp(T), _dp(out)))
-        return out
+        return self._sums(self.L.s4p_icp_plane_sums, T, PLANE_NSUMS)
 
     def set_source_normals(self, N):
         """One normal per source point (N, 3), in the uploaded order and the frame of the source as uploaded (the library
@@ -506,24 +507,15 @@ class ICP:
 
     def source_normals(self):
         """float32 (n_Q, 3): the stored source normals, in the uploaded order."""
-        n = self.n_q
-        cols = [np.empty(n, np.float32) for _ in range(3)]
-        self._chk(self.L.s4p_icp_source_normals(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
-        return np.stack(cols, axis=1)
+        return self._read3(self.L.s4p_icp_source_normals, self.n_q)
 
     def gicp_sums(self, T, epsilon=GICP_EPSILON):
         """The 31 generalized sums for a float T in the centred frame (layout in include/s4p_icp_gicp.h)."""
-        T = self._t32(T)
-        out = np.empty(GICP_NSUMS, np.float64)
-        self._chk(self.L.s4p_icp_gicp_sums(self.h, _fp(T), float(epsilon), _dp(out)))
-        return out
+        return self._sums(self.L.s4p_icp_gicp_sums, T, GICP_NSUMS, float(epsilon))
 
     def symmetric_sums(self, T):
         """The 31 symmetric sums for a float T in the centred frame (layout in include/s4p_icp_symm.h)."""
-        T = self._t32(T)
-        out = np.empty(SYMM_NSUMS, np.float64)
-        self._chk(self.L.s4p_icp_symm_sums(self.h, _fp(T), _dp(out)))
-        return out
+        return self._sums(self.L.s4p_icp_symm_sums, T, SYMM_NSUMS)
 
     def _scalars(self, v):
         """(entry-point suffix, pointer, n, keep-alive) of one float per point: numpy, or a torch tensor on the GPU."""
@@ -558,17 +550,11 @@ class ICP:
 
     def target_color_gradients(self):
         """float32 (n_P, 3): the current gradients, in the uploaded order."""
-        n = self.n_p
-        cols = [np.empty(n, np.float32) for _ in range(3)]
-        self._chk(self.L.s4p_icp_target_color_gradients(self.h, _fp(cols[0]), _fp(cols[1]), _fp(cols[2])))
-        return np.stack(cols, axis=1)
+        return self._read3(self.L.s4p_icp_target_color_gradients, self.n_p)
 
     def color_sums(self, T, color_lambda=COLOR_LAMBDA):
         """The 31 joint sums for a float T in the centred frame (layout in include/s4p_icp_color.h)."""
-        T = self._t32(T)
-        out = np.empty(COLOR_NSUMS, np.float64)
-        self._chk(self.L.s4p_icp_color_sums(self.h, _fp(T), float(color_lambda), _dp(out)))
-        return out
+        return self._sums(self.L.s4p_icp_color_sums, T, COLOR_NSUMS, float(color_lambda))
 
     def set_rejection(self, reciprocal=False, normal_angle=None, oriented=False, normal_cos=None):
         """The context's pair rejection (include/s4p_icp_reject.h): reciprocal keeps a pair only if the source point is the
@@ -609,10 +595,7 @@ class ICP:
 
     def sums(self, T):
         """The 17 double sums for a float T in the centred frame: n, sum q^, sum p', sum q^ p'^T (row-major), sum d2."""
-        T = self._t32(T)
-        out = np.empty(NSUMS, np.float64)
-        self._chk(self.L.s4p_icp_sums(self.h, _fp(T), _dp(out)))
-        return out
+        return self._sums(self.L.s4p_icp_sums, T, NSUMS)
 
     def robust_sums(self, T, metric, loss, trim_fraction=None, scale=None, c=None):
         """(sums, info) for a float T in the centred frame: the weighted 17 (point) or 31 (plane) sums and the 8 info
@@ -649,32 +632,24 @@ class ICP:
         p.max_iterations, p.rel_tol, p.min_correspondences = int(max_iterations), float(rel_tol), int(min_correspondences)
         p.order_source = int(bool(order_source))
         r = Result()
+        inf = np.zeros(ROBUST_NINFO, np.float64)
+        # (function, its arguments between the parameters and T, those after the Result)
         if rob is not None:
-            inf = np.zeros(ROBUST_NINFO, np.float64)
-            self._chk(self.L.s4p_icp_refine_robust(self.h, C.byref(p), METRICS.index(metric), C.byref(rob), _dp(T), C.byref(r), _dp(inf)))
-            if info is not None:
-                info[:] = inf
-            return T.reshape(4, 4), r
-        if metric == "gicp":
-            self._chk(self.L.s4p_icp_refine_gicp(self.h, C.byref(p), float(gicp_epsilon), _dp(T), C.byref(r)))
-            return T.reshape(4, 4), r
-        if metric == "symmetric":
-            self._chk(self.L.s4p_icp_refine_symm(self.h, C.byref(p), _dp(T), C.byref(r)))
-            return T.reshape(4, 4), r
-        if metric == "color":
-            self._chk(self.L.s4p_icp_refine_color(self.h, C.byref(p), float(color_lambda), _dp(T), C.byref(r)))
-            return T.reshape(4, 4), r
-        fn = self.L.s4p_icp_refine_plane if metric == "plane" else self.L.s4p_icp_refine
-        self._chk(fn(self.h, C.byref(p), _dp(T), C.byref(r)))
+            fn, before, after = self.L.s4p_icp_refine_robust, (METRICS.index(metric), C.byref(rob)), (_dp(inf),)
+        else:
+            fn, scalar = {"point": (self.L.s4p_icp_refine, ()), "plane": (self.L.s4p_icp_refine_plane, ()),
+                          "gicp": (self.L.s4p_icp_refine_gicp, (gicp_epsilon,)), "symmetric": (self.L.s4p_icp_refine_symm, ()),
+                          "color": (self.L.s4p_icp_refine_color, (color_lambda,))}[metric]
+            before, after = tuple(float(v) for v in scalar), ()
+        self._chk(fn(self.h, C.byref(p), *before, _dp(T), C.byref(r), *after))
+        if rob is not None and info is not None:
+            info[:] = inf
         return T.reshape(4, 4), r
 
     def information_sums(self, T):
         """The 11 information sums for a float T in the centred frame (layout in include/s4p_icp_info.h): n, sum d2,
         sum p', the upper triangle of sum p' p'^T over the matched target points; the context's rejection holds."""
-        T = self._t32(T)
-        out = np.empty(INFO_NSUMS, np.float64)
-        self._chk(self.L.s4p_icp_information_sums(self.h, _fp(T), _dp(out)))
-        return out
+        return self._sums(self.L.s4p_icp_information_sums, T, INFO_NSUMS)
 
     def information(self, T):
         """(info float64 6x6, n, rmse) of the pose T (caller frame, float64 4x4; include/s4p_icp_info.h): info = sum G^T G
@@ -724,6 +699,34 @@ class ICP:
         return np.stack(cols, axis=1)
 
 
+@contextlib.contextmanager
+def _session(P, Q, max_distance, device, target=False, source=False, target_normals=None, normal_radius=None,
+             source_normals=None, normal_k=16, rej=None):
+    """One context for one convenience call, closed on every path: target P, source Q; with `target` the target normals
+    (given, else estimated within normal_radius, default max_distance); with `source` the source normals (given, else the
+    normal_k-nearest-neighbour normals of Q, estimated before the context is created); the rejection rej when it has a
+    filter on."""
+    if source and source_normals is None:
+        from super4pcs_amd import normals
+        source_normals = normals.estimate_normals(Q, k=normal_k)
+    ctx = ICP(device)
+    try:
+        ctx.set_target(P, max_distance)
+        ctx.set_source(Q)
+        if target:
+            if target_normals is not None:
+                ctx.set_target_normals(target_normals)
+            else:
+                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
+        if source:
+            ctx.set_source_normals(source_normals)
+        if rej is not None and (rej.reciprocal or rej.normal_mode != NORMALS_OFF):
+            ctx._chk(ctx.L.s4p_icp_set_rejection(ctx.h, C.byref(rej)))
+        yield ctx
+    finally:
+        ctx.close()
+
+
 def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None,
            source_normals=None, normal_k=16, target_intensity=None, source_intensity=None, color_radius=None,
            reciprocal=False, normal_angle=None, normals_oriented=False, **params):
@@ -747,30 +750,15 @@ def refine(P, Q, T0=None, max_distance=None, device=0, metric="point", target_no
         raise ValueError("target_intensity / source_intensity / color_radius need metric \"color\"")
     rej = reject_params(reciprocal, normal_angle, normals_oriented)       # validates before any device work
     by_normals = rej.normal_mode != NORMALS_OFF
-    if (metric in NORMAL_PAIR_METRICS or by_normals) and source_normals is None:
-        from super4pcs_amd import normals
-        source_normals = normals.estimate_normals(Q, k=normal_k)
-    ctx = ICP(device)
-    try:
-        ctx.set_target(P, max_distance)
-        ctx.set_source(Q)
-        if metric in ("plane", "gicp", "symmetric", "color") or by_normals:
-            if target_normals is not None:
-                ctx.set_target_normals(target_normals)
-            else:
-                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
-        if metric in NORMAL_PAIR_METRICS or by_normals:
-            ctx.set_source_normals(source_normals)
-        if rej.reciprocal or by_normals:
-            ctx._chk(ctx.L.s4p_icp_set_rejection(ctx.h, C.byref(rej)))
+    with _session(P, Q, max_distance, device, target=metric != "point" or by_normals, source=metric in NORMAL_PAIR_METRICS or by_normals,
+                  target_normals=target_normals, normal_radius=normal_radius, source_normals=source_normals, normal_k=normal_k,
+                  rej=rej) as ctx:                         # the rejection is set only when reciprocal or by_normals
         if metric == "color":
             ctx.set_target_intensity(target_intensity)
             ctx.set_source_intensity(source_intensity)
             r_n = max_distance if normal_radius is None else normal_radius
             ctx.estimate_color_gradients(r_n if color_radius is None else color_radius)
         return ctx.refine(T0, metric=metric, **params)
-    finally:
-        ctx.close()
 
 
 def refine_best(P, Q, T0s, max_distance=None, device=0, metric="point", target_normals=None, normal_radius=None, **params):
@@ -782,22 +770,12 @@ def refine_best(P, Q, T0s, max_distance=None, device=0, metric="point", target_n
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
     _batch_metric(metric)
     T0s = _batch_transforms(T0s, np.float64)
-    if metric != "plane" and (target_normals is not None or normal_radius is not None):
+    if metric != "plane" and (target_normals is not None or normal_radius is not None):        # refine takes them for any metric
         raise ValueError("target_normals / normal_radius need metric \"plane\"")
-    ctx = ICP(device)
-    try:
-        ctx.set_target(P, max_distance)
-        ctx.set_source(Q)
-        if metric == "plane":
-            if target_normals is not None:
-                ctx.set_target_normals(target_normals)
-            else:
-                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
+    with _session(P, Q, max_distance, device, target=metric == "plane", target_normals=target_normals, normal_radius=normal_radius) as ctx:
         Ts, results, order = ctx.refine_batch(T0s, metric=metric, **params)
         i = int(order[0])
         return Ts[i], results[i], i
-    finally:
-        ctx.close()
 
 
 def information_from_sums(sums, c):
@@ -824,21 +802,6 @@ def information(P, Q, T, max_distance=None, device=0, reciprocal=False, normal_a
         raise ValueError("max_distance is required (4 * delta after a registration at delta)")
     rej = reject_params(reciprocal, normal_angle, normals_oriented)
     by_normals = rej.normal_mode != NORMALS_OFF
-    if by_normals and source_normals is None:
-        from super4pcs_amd import normals
-        source_normals = normals.estimate_normals(Q, k=normal_k)
-    ctx = ICP(device)
-    try:
-        ctx.set_target(P, max_distance)
-        ctx.set_source(Q)
-        if by_normals:
-            if target_normals is not None:
-                ctx.set_target_normals(target_normals)
-            else:
-                ctx.estimate_normals(max_distance if normal_radius is None else normal_radius)
-            ctx.set_source_normals(source_normals)
-        if rej.reciprocal or by_normals:
-            ctx._chk(ctx.L.s4p_icp_set_rejection(ctx.h, C.byref(rej)))
+    with _session(P, Q, max_distance, device, target=by_normals, source=by_normals, target_normals=target_normals,
+                  normal_radius=normal_radius, source_normals=source_normals, normal_k=normal_k, rej=rej) as ctx:
         return ctx.information(T)
-    finally:
-        ctx.close()

@@ -13,11 +13,12 @@ TIMEOUT = 300
 ICP_FACADE_LIBS = ("super4pcs_amd", "super4pcs_icp")        # not the normals library: RefineICP binds it at run time
 
 
-def build_app(outdir, name, libs, extra=()):
+def build_app(outdir, name, libs, extra=(), include=None):
     """tests/<name>/main.cpp against the facade headers and the libraries `libs` of super4pcs_amd/lib; extra: further
-    compiler flags (-Werror, -g, -D..., sanitizers).  Returns the program's path under outdir."""
+    compiler flags (-Werror, -g, -D..., sanitizers); include: another include/ tree than this one's (the recorders under
+    tests/golden pin an earlier tree's headers with it).  Returns the program's path under outdir."""
     exe = os.path.join(str(outdir), name)
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include")] + list(extra) +
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-I" + (include or os.path.join(ROOT, "include"))] + list(extra) +
                           [os.path.join(ROOT, "tests", name, "main.cpp"), "-L" + LIBDIR] + ["-l" + lib for lib in libs] +
                           ["-Wl,-rpath," + LIBDIR, "-o", exe])
     return exe

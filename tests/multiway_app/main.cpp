@@ -3,6 +3,7 @@
 // -lsuper4pcs_icp (tests/apps.py).
 //   multiway_app poses.txt max_distance min_fitness scan0.xyz scan1.xyz ...   (poses.txt: N + 1 lines of 16 numbers: the N
 //                start poses, world <- scan i, row-major, then T for the information of scan 1 onto scan 0)
+//     --metric gicp   RegisterMultiway with ICPMetric::Generalized (default: PointToPlane)
 //     --check      no device: OptimizePoseGraph on the chain built from the poses file (edges i + 1 -> i that agree with the
 //                  poses, unit information), prints its status
 // Prints "pose i" + 16 numbers per scan, "edge source target uncertain n rmse fitness l" per edge, "graph iterations a b
@@ -54,10 +55,11 @@ static void print16(const char* what, int i, const double* v, int count) {
 
 int main(int argc, char** argv) {
   if (argc < 4) return 2;
-  bool check = false;
+  bool check = false, gicp = false;
   std::vector<const char*> files;
   for (int a = 4; a < argc; ++a) {
     if (!std::strcmp(argv[a], "--check")) check = true;
+    else if (!std::strcmp(argv[a], "--metric") && a + 1 < argc) gicp = !std::strcmp(argv[++a], "gicp");
     else files.push_back(argv[a]);
   }
   std::vector<Pose> poses = load_poses(argv[1]);
@@ -96,7 +98,7 @@ int main(int argc, char** argv) {
     poses.pop_back();
     MultiwayOptions o;
     o.icp.max_distance = std::atof(argv[2]);
-    o.icp.metric = ICPMetric::PointToPlane;
+    o.icp.metric = gicp ? ICPMetric::Generalized : ICPMetric::PointToPlane;
     o.min_fitness = std::atof(argv[3]);
     const MultiwayReport rep = RegisterMultiway(scans, &poses, o);
     for (size_t i = 0; i < poses.size(); ++i) { print16("pose", int(i), poses[i].data(), 16); std::printf("\n"); }
