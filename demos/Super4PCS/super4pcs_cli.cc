@@ -10,6 +10,7 @@
 //             [--estimate-normals k] [--estimate-normals-radius r] [--orient-normals k] [--orient-viewpoint x,y,z]
 //             [--remove-outliers k] [--remove-outliers-std ratio]
 //             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K] [--icp-information file]
+//             [--cluster-eps e] [--cluster-min-points m] [--cluster-keep K]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -34,6 +35,11 @@
 // --voxel-size v replaces both inputs by the means of their occupied voxels of edge v (algorithms/voxelgrid.h) after
 // --remove-outliers and before --estimate-normals, the matcher and ICP; normals and colours are averaged when every point
 // has one; -r then writes the downsampled, registered second input.  An input with faces is refused (exit status 254).
+// --cluster-eps e keeps the --cluster-keep K (default 1) largest density clusters of both inputs (algorithms/cluster.h:
+// DBSCAN with the radius e and --cluster-min-points m, default 10) after --voxel-size, where the density is even and e is
+// easiest to choose, and before --estimate-normals, the matcher and ICP: a dense fragment away from the surface goes, which
+// --remove-outliers keeps; -r then writes the filtered, registered second input.  An input with faces, or one left with no
+// cluster, is refused (exit status 254).
 // --icp-scales v1,v2,... (needs --icp) refines coarse to fine (algorithms/icp_multiscale.h): one level per voxel size, both
 // inputs downsampled at it (the second in its own frame; 0, allowed last, takes them as they are), the level's distance
 // max(--icp-dist, 3 v) and --icp iterations per level; every --icp-metric and --icp-loss applies to every level.
@@ -53,6 +59,7 @@
 #include <string>
 #include <vector>
 
+#include "super4pcs/algorithms/cluster.h"
 #include "super4pcs/algorithms/icp.h"
 #include "super4pcs/algorithms/icp_batch.h"
 #include "super4pcs/algorithms/icp_information.h"
@@ -87,15 +94,26 @@ struct Mesh {                                    // everything IOManager returns
     const size_t before = points.size();
     std::vector<uint8_t> kept;
     const size_t removed = RemoveOutliers(points, oopt, &kept);
-    auto compact = [&](auto& list) {
-      if (list.size() != before) return;
-      size_t w = 0;
-      for (size_t i = 0; i < before; ++i)
-        if (kept[i]) list[w++] = list[i];
-      list.resize(w);
-    };
-    compact(normals);
-    compact(tex);
+    compact(normals, kept, before);
+    compact(tex, kept, before);
+    return removed;
+  }
+  // a per-vertex list (one entry per point before the filter) without the entries of the removed points
+  template <class List>
+  static void compact(List& list, const std::vector<uint8_t>& kept, size_t before) {
+    if (list.size() != before) return;
+    size_t w = 0;
+    for (size_t i = 0; i < before; ++i)
+      if (kept[i]) list[w++] = list[i];
+    list.resize(w);
+  }
+  // the largest density clusters of the points; per-vertex normal and texture lists follow the vertices
+  size_t keep_clusters(const ClusterOptions& copt) {
+    const size_t before = points.size();
+    std::vector<uint8_t> kept;
+    const size_t removed = KeepLargestClusters(points, copt, &kept);
+    compact(normals, kept, before);
+    compact(tex, kept, before);
     return removed;
   }
   // voxel-grid downsampling of the points; the per-vertex normal list is rebuilt from the averaged normals when they were
@@ -166,6 +184,10 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
     log.Log<Utils::ErrorReport>("--voxel-size: an input has faces; faces index the vertex list, so only point sets can be downsampled");
     return -2;
   }
+  if (opt.cluster_eps > 0 && (!P.faces.empty() || !Q.faces.empty())) {
+    log.Log<Utils::ErrorReport>("--cluster-eps: an input has faces; faces index the vertex list, so only point sets can be filtered");
+    return -2;
+  }
   try {
     if (opt.outliers_k > 0) {
       OutlierRemovalOptions oopt;
@@ -180,6 +202,18 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       const size_t np = P.points.size(), nq = Q.points.size();
       const size_t mp = P.voxel_downsample(vopt), mq = Q.voxel_downsample(vopt);
       log.Log<Utils::Verbose>("Voxel grid: edge ", opt.voxel_size, ": ", mp, " of ", np, " points of input1, ", mq, " of ", nq, " of input2");
+    }
+    if (opt.cluster_eps > 0) {
+      ClusterOptions copt;
+      copt.eps = opt.cluster_eps;
+      copt.min_points = opt.cluster_min_points;
+      copt.keep = opt.cluster_keep;
+      const size_t rp = P.keep_clusters(copt), rq = Q.keep_clusters(copt);
+      log.Log<Utils::Verbose>("Kept clusters: eps ", opt.cluster_eps, ", min points ", opt.cluster_min_points, ", keep ", opt.cluster_keep, ": removed ",
+                              rp, " of input1, ", rq, " of input2");
+      if (P.points.empty() || Q.points.empty())
+        throw std::runtime_error(std::string("--cluster-eps: no cluster in ") + (P.points.empty() ? "input1" : "input2") +
+                                 " at this eps and --cluster-min-points; nothing is left to register");
     }
     if (opt.normals_k > 0) {
       NormalEstimationOptions nopt;

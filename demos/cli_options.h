@@ -56,7 +56,11 @@ struct Options {
   bool icp_scales_set = false;
   int icp_starts = 0;                                        // --icp-starts K  refine the matcher's K best distinct poses in one batch (needs --icp)
   bool icp_starts_set = false;
-  bool bad_value = false;                                    // a flag's value does not parse
+  double cluster_eps = -1;                                   // --cluster-eps e  keep the largest density clusters of both inputs (off)
+  int cluster_min_points = 10;                               // --cluster-min-points m  (needs eps)
+  int cluster_keep = 1;                                      // --cluster-keep K  (needs eps)
+  bool cluster_min_points_set = false, cluster_keep_set = false;
+  bool bad_value = false;                                   // a flag's value does not parse
 };
 
 enum class Parse { Run, Help, Bad };
@@ -216,6 +220,24 @@ inline const Flag* flag_table(size_t* n) {
          o.icp_starts_set = true;
          if (end == v[0] || *end != '\0' || k < 1 || k > 64) o.bad_value = true; else o.icp_starts = int(k);
        }},
+      {"--cluster-eps", 1, [](Options& o, char** v) {
+         // finite, > 0, and with a square that is a finite float
+         char* end = nullptr;
+         const double e = std::strtod(v[0], &end);
+         if (end == v[0] || *end != '\0' || !(e > 0) || !(e < 1.8e19) || !(float(e) > 0.f)) o.bad_value = true; else o.cluster_eps = e;
+       }},
+      {"--cluster-min-points", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long m = std::strtol(v[0], &end, 10);
+         o.cluster_min_points_set = true;
+         if (end == v[0] || *end != '\0' || m < 1 || m > 2147483647L) o.bad_value = true; else o.cluster_min_points = int(m);
+       }},
+      {"--cluster-keep", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long k = std::strtol(v[0], &end, 10);
+         o.cluster_keep_set = true;
+         if (end == v[0] || *end != '\0' || k < 1 || k > 2147483647L) o.bad_value = true; else o.cluster_keep = int(k);
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -242,6 +264,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.outliers_std_set && o.outliers_k == 0) return Parse::Bad;      // the ratio needs --remove-outliers
   if (o.orient_k > 0 && o.normals_k == 0) return Parse::Bad;           // --orient-normals needs --estimate-normals
   if (o.orient_viewpoint_set && o.orient_k == 0) return Parse::Bad;    // --orient-viewpoint needs --orient-normals
+  if ((o.cluster_min_points_set || o.cluster_keep_set) && !(o.cluster_eps > 0)) return Parse::Bad;    // both need --cluster-eps
   if (o.icp_trim_set && o.icp_loss != 1) return Parse::Bad;            // --icp-trim needs --icp-loss trimmed
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
@@ -305,6 +328,11 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t     graph of the k nearest neighbours from an anchor that faces away from the centre of the input's bounds, or faces\n");
   std::fprintf(stderr, "\t     the viewpoint, the same coordinates in each file's own frame: that suits scans taken from the origin; then\n");
   std::fprintf(stderr, "\t     --icp-normal-angle compares the normals with their sign, in [0, 90] degrees)\n");
+  std::fprintf(stderr, "\t[ --cluster-eps e (> 0; off) ] [ --cluster-min-points m (needs e; 10, >= 1) ] [ --cluster-keep K (needs e; 1, >= 1) ]\n");
+  std::fprintf(stderr, "\t    (density clustering of both inputs on the device, after --voxel-size and before --estimate-normals: a point with\n");
+  std::fprintf(stderr, "\t     at least m points within e, itself included, is a core point, core points within e of each other share a\n");
+  std::fprintf(stderr, "\t     cluster, and the K largest clusters stay: a dense fragment away from the surface goes, which\n");
+  std::fprintf(stderr, "\t     --remove-outliers keeps; point sets only, -r writes the filtered input2)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

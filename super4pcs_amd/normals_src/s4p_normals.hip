@@ -9,6 +9,7 @@
 //   lists and outlier removal (include/s4p_knn.h): s4p_knn.inc, on the same cloud and grid.
 //   voxel-grid downsampling (include/s4p_voxel.h): s4p_voxel.inc, of a cloud passed per call, on the context's stream.
 //   normal orientation (include/s4p_normals_orient.h): s4p_orient.inc, a minimum spanning forest over the lists' graph.
+//   density clustering (include/s4p_cluster.h): s4p_cluster.inc, a fixed-radius walk on a grid of edge eps and a union-find.
 //   estimate    queries in cell order (the cloud itself, or k_cell_keys + sort + k_gather of the caller's queries) ->
 //               k_knn_normals<K>: one lane per query, ring search with conservative box pruning, the k best (d2, index)
 //               sorted in registers, covariance in double, 3x3 Jacobi, the normal scattered to the caller's order.
@@ -376,13 +377,63 @@ int end_bit(uint64_t max_key) {
   return b;
 }
 
+int32_t sort_pairs_bytes(s4p_normals_ctx* h, uint64_t n, uint64_t max_key, size_t* bytes) {
+  uint32_t* none = nullptr;
+  *bytes = 0;
+  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (const uint32_t*)none, none, (const uint32_t*)none, none, int(n), 0,
+                                             end_bit(max_key), h->st));
+  return S4P_NORMALS_OK;
+}
+
 int32_t sort_pairs(s4p_normals_ctx* h, Scratch& S, const uint32_t* keys, uint32_t* keys_out, const uint32_t* vals, uint32_t* vals_out,
                    uint64_t n, uint64_t max_key) {
   size_t bytes = 0;
-  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
+  if (int32_t rc = sort_pairs_bytes(h, n, max_key, &bytes)) return rc;
   void* tmp = nullptr;
   NRM_HIP(S.alloc(&tmp, bytes));
   NRM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
+  return S4P_NORMALS_OK;
+}
+
+// The dense grid over [lo, hi] with the cell edge hh, enlarged x 1.25 until it fits the cell cap: origin, edge, dims.
+int32_t fit_grid(s4p_normals_ctx* h, const char* what, const float lo[3], const float hi[3], double hh, uint64_t un, GridDev* g,
+                 uint64_t* ncell) {
+  const uint64_t cap = std::min<uint64_t>(kMaxCells, std::max<uint64_t>(1ull << 20, 4 * un));
+  int dims[3];
+  for (int guard = 0;; ++guard) {
+    const double inv = 1.0 / hh;
+    bool ok = true;
+    uint64_t nc = 1;
+    for (int a = 0; a < 3; ++a) {
+      const double cc = cell_coord(hi[a], double(lo[a]), inv);
+      if (!(cc < 1.0e9)) { ok = false; break; }
+      dims[a] = int(cc) + 1;
+      nc *= uint64_t(dims[a]);
+      if (nc > cap) { ok = false; break; }
+    }
+    if (ok) { g->h = hh; g->inv_h = inv; *ncell = nc; break; }
+    if (guard > 400) return fail(h, S4P_NORMALS_ERR_BAD_ARG, std::string(what) + ": no grid fits the cloud's extent");
+    hh *= 1.25;
+  }
+  g->ox = lo[0]; g->oy = lo[1]; g->oz = lo[2];
+  g->nx = dims[0]; g->ny = dims[1]; g->nz = dims[2];
+  return S4P_NORMALS_OK;
+}
+
+// The cloud pos on the grid g: cell keys, the radix sort of (cell, index), then the [begin, end) of every cell into range
+// (ncell entries) and the cloud in cell order into pts.  keys .. vals2 hold un words each, tmp the sort's work memory.
+int32_t fill_grid(s4p_normals_ctx* h, const float4* pos, uint64_t un, const GridDev& g, uint64_t ncell, uint32_t* keys, uint32_t* vals,
+                  uint32_t* keys2, uint32_t* vals2, void* tmp, size_t tmp_bytes, uint2* range, float4* pts) {
+  const int nb = blocks_for(int64_t(un));
+  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, pos, un, g, keys, vals);
+  NRM_HIP(hipGetLastError());
+  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, (const uint32_t*)keys, keys2, (const uint32_t*)vals, vals2, int(un), 0,
+                                             end_bit(ncell - 1), h->st));
+  NRM_HIP(hipMemsetAsync(range, 0, ncell * sizeof(uint2), h->st));
+  hipLaunchKernelGGL(k_cell_ranges, dim3(nb), dim3(kBlock), 0, h->st, (const uint32_t*)keys2, un, range);
+  NRM_HIP(hipGetLastError());
+  hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, pos, (const uint32_t*)vals2, un, pts);
+  NRM_HIP(hipGetLastError());
   return S4P_NORMALS_OK;
 }
 
@@ -477,40 +528,19 @@ int32_t set_cloud_impl(s4p_normals_ctx* h, const float* x, const float* y, const
   double ext = 0.0;
   for (int a = 0; a < 3; ++a) ext = std::max(ext, double(hi[a]) - double(lo[a]));
   double hh = ext > 0.0 ? std::max(spacing, ext * 0x1p-20) : 1.0;
-  const uint64_t cap = std::min<uint64_t>(kMaxCells, std::max<uint64_t>(1ull << 20, 4 * un));
-  int dims[3];
-  for (int guard = 0;; ++guard) {
-    const double inv = 1.0 / hh;
-    bool ok = true;
-    uint64_t nc = 1;
-    for (int a = 0; a < 3; ++a) {
-      const double cc = cell_coord(hi[a], double(lo[a]), inv);
-      if (!(cc < 1.0e9)) { ok = false; break; }
-      dims[a] = int(cc) + 1;
-      nc *= uint64_t(dims[a]);
-      if (nc > cap) { ok = false; break; }
-    }
-    if (ok) { h->g.h = hh; h->g.inv_h = inv; h->ncell = nc; break; }
-    if (guard > 400) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: no grid fits the cloud's extent");
-    hh *= 1.25;
-  }
+  if (int32_t rc = fit_grid(h, "set_cloud", lo, hi, hh, un, &h->g, &h->ncell)) return rc;
   h->spacing = spacing;
   for (int a = 0; a < 3; ++a) { h->lo[a] = lo[a]; h->hi[a] = hi[a]; }
-  h->g.ox = lo[0]; h->g.oy = lo[1]; h->g.oz = lo[2];
-  h->g.nx = dims[0]; h->g.ny = dims[1]; h->g.nz = dims[2];
   uint32_t *keys, *vals, *keys2, *vals2;
   NRM_HIP(S.alloc((void**)&keys, un * 4)); NRM_HIP(S.alloc((void**)&vals, un * 4));
   NRM_HIP(S.alloc((void**)&keys2, un * 4)); NRM_HIP(S.alloc((void**)&vals2, un * 4));
-  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->pos, un, h->g, keys, vals);
-  NRM_HIP(hipGetLastError());
-  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, un, h->ncell - 1)) return rc;
+  size_t sort_bytes = 0;
+  if (int32_t rc = sort_pairs_bytes(h, un, h->ncell - 1, &sort_bytes)) return rc;
+  void* tmp = nullptr;
+  NRM_HIP(S.alloc(&tmp, sort_bytes));
   NRM_HIP(hipMalloc((void**)&h->range, h->ncell * sizeof(uint2)));
   NRM_HIP(hipMalloc((void**)&h->pts, un * sizeof(float4)));
-  NRM_HIP(hipMemsetAsync(h->range, 0, h->ncell * sizeof(uint2), h->st));
-  hipLaunchKernelGGL(k_cell_ranges, dim3(nb), dim3(kBlock), 0, h->st, (const uint32_t*)keys2, un, h->range);
-  NRM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->pos, (const uint32_t*)vals2, un, h->pts);
-  NRM_HIP(hipGetLastError());
+  if (int32_t rc = fill_grid(h, h->pos, un, h->g, h->ncell, keys, vals, keys2, vals2, tmp, sort_bytes, h->range, h->pts)) return rc;
   NRM_HIP(hipStreamSynchronize(h->st));          // the scratch is freed on return
   h->g.pts = h->pts;
   h->g.range = h->range;
@@ -598,6 +628,7 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
 #include "s4p_knn.inc"                   // include/s4p_knn.h: neighbour lists and outlier removal on the same context
 #include "s4p_voxel.inc"                 // include/s4p_voxel.h: voxel-grid downsampling on the context's stream and arena
 #include "s4p_orient.inc"                // include/s4p_normals_orient.h: consistent normal orientation on the lists of s4p_knn.inc
+#include "s4p_cluster.inc"               // include/s4p_cluster.h: density clustering on a grid of its own, on the same stream and arena
 
 extern "C" {
 
