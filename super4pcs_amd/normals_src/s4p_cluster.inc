@@ -22,6 +22,7 @@
 
 namespace s4p_nrm {
 
+static_assert(S4P_CLUSTER_ERR_INTERNAL == kErrInternal, "arena_layout fails with the family's internal code");
 enum ClusterMode { kCount = 0, kCore = 1 };
 enum ClusterWord { kClCore = 0, kClBorder = 1, kClNoise = 2, kClClusters = 3, kClOverrun = 4, kClWords = 8 };
 constexpr uint32_t kNoCore = 0xFFFFFFFFu;       // nearest-core word of a point without a core neighbour
@@ -226,7 +227,16 @@ struct ClusterGrid {
   GridDev g{};
   uint64_t ncell = 0;
   size_t sort_bytes = 0;
-  size_t bytes = 0;             // of the arena pieces build takes
+  uint32_t *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr;      // the arena pieces of build
+  void* tmp = nullptr;
+  uint2* range = nullptr;
+  float4* pts = nullptr;
+  void take(Arena& ar, uint64_t un) {
+    keys = ar.take<uint32_t>(un); vals = ar.take<uint32_t>(un); keys2 = ar.take<uint32_t>(un); vals2 = ar.take<uint32_t>(un);
+    tmp = ar.take<char>(sort_bytes);
+    range = ar.take<uint2>(ncell);
+    pts = ar.take<float4>(un);
+  }
 };
 
 int32_t cluster_grid_plan(s4p_normals_ctx* h, const char* what, float eps, ClusterGrid* G) {
@@ -236,22 +246,14 @@ int32_t cluster_grid_plan(s4p_normals_ctx* h, const char* what, float eps, Clust
   const double hh = std::max(double(eps) * kClusterEdgeMargin, ext * 0x1p-20);
   if (int32_t rc = fit_grid(h, what, h->lo, h->hi, hh, un, &G->g, &G->ncell)) return rc;
   if (int32_t rc = sort_pairs_bytes(h, un, G->ncell - 1, &G->sort_bytes)) return rc;
-  G->bytes = 4 * arena_round(un * 4) + arena_round(G->sort_bytes) + arena_round(G->ncell * sizeof(uint2)) + arena_round(un * sizeof(float4));
   return S4P_NORMALS_OK;
 }
 
-int32_t cluster_grid_build(s4p_normals_ctx* h, Arena& ar, ClusterGrid* G) {
-  const uint64_t un = uint64_t(h->n);
-  uint32_t* keys = ar.take<uint32_t>(un);
-  uint32_t* vals = ar.take<uint32_t>(un);
-  uint32_t* keys2 = ar.take<uint32_t>(un);
-  uint32_t* vals2 = ar.take<uint32_t>(un);
-  void* tmp = ar.take<char>(G->sort_bytes);
-  uint2* range = ar.take<uint2>(G->ncell);
-  float4* pts = ar.take<float4>(un);
-  if (int32_t rc = fill_grid(h, h->pos, un, G->g, G->ncell, keys, vals, keys2, vals2, tmp, G->sort_bytes, range, pts)) return rc;
-  G->g.pts = pts;
-  G->g.range = range;
+int32_t cluster_grid_build(s4p_normals_ctx* h, ClusterGrid* G) {
+  if (int32_t rc = fill_grid(h, h->pos, uint64_t(h->n), G->g, G->ncell, G->keys, G->vals, G->keys2, G->vals2, G->tmp, G->sort_bytes,
+                             G->range, G->pts)) return rc;
+  G->g.pts = G->pts;
+  G->g.range = G->range;
   return S4P_NORMALS_OK;
 }
 
@@ -263,12 +265,15 @@ int32_t density_impl(s4p_normals_ctx* h, float radius, int32_t* count, bool devi
   const uint64_t un = uint64_t(h->n);
   ClusterGrid G;
   if (int32_t rc = cluster_grid_plan(h, "cluster_density", radius, &G)) return rc;
-  Arena ar;
-  if (int32_t rc = arena_reserve(h, G.bytes + (device ? 0 : arena_round(un * 4)), &ar)) return rc;
-  if (int32_t rc = cluster_grid_build(h, ar, &G)) return rc;
+  int32_t* dcount = count;
+  if (int32_t rc = arena_layout(h, "cluster_density", [&](Arena& ar) {
+        G.take(ar, un);
+        if (!device) dcount = ar.take<int32_t>(un);
+      })) return rc;
+  if (int32_t rc = cluster_grid_build(h, &G)) return rc;
   ClusterArgs A{};
   A.g = G.g; A.n = un; A.r2 = radius * radius; A.min_points = 0;
-  A.count = device ? count : ar.take<int32_t>(un);
+  A.count = dcount;
   hipLaunchKernelGGL(k_cluster_walk<kCount>, dim3(blocks_for(h->n)), dim3(kBlock), 0, h->st, A);
   NRM_HIP(hipGetLastError());
   if (!device) NRM_HIP(hipMemcpyAsync(count, A.count, un * 4, hipMemcpyDeviceToHost, h->st));
@@ -290,21 +295,25 @@ int32_t dbscan_impl(s4p_normals_ctx* h, float eps, int32_t min_points, int32_t* 
   size_t scan_bytes = 0;
   uint32_t* none = nullptr;
   NRM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const uint32_t*)none, none, int(un), h->st));
-  Arena ar;
-  const size_t need = G.bytes + arena_round(kClWords * 8) + 2 * arena_round(un) + 5 * arena_round(un * 4) + arena_round(scan_bytes) +
-                      (device ? 0 : arena_round(un * 4));
-  if (int32_t rc = arena_reserve(h, need, &ar)) return rc;
-  if (int32_t rc = cluster_grid_build(h, ar, &G)) return rc;
-  unsigned long long* words = ar.take<unsigned long long>(kClWords);
-  uint8_t* core = ar.take<uint8_t>(un);
-  uint8_t* dkind = ar.take<uint8_t>(un);
-  uint32_t* parent = ar.take<uint32_t>(un);
-  uint32_t* near = ar.take<uint32_t>(un);
-  uint32_t* root = ar.take<uint32_t>(un);
-  uint32_t* flag = ar.take<uint32_t>(un);
-  uint32_t* rank = ar.take<uint32_t>(un);
-  void* scan_tmp = ar.take<char>(scan_bytes);
-  int32_t* dlabel = device ? label : ar.take<int32_t>(un);
+  unsigned long long* words = nullptr;
+  uint8_t *core = nullptr, *dkind = nullptr;
+  uint32_t *parent = nullptr, *near = nullptr, *root = nullptr, *flag = nullptr, *rank = nullptr;
+  void* scan_tmp = nullptr;
+  int32_t* dlabel = label;
+  if (int32_t rc = arena_layout(h, "cluster_dbscan", [&](Arena& ar) {
+        G.take(ar, un);
+        words = ar.take<unsigned long long>(kClWords);
+        core = ar.take<uint8_t>(un);
+        dkind = ar.take<uint8_t>(un);
+        parent = ar.take<uint32_t>(un);
+        near = ar.take<uint32_t>(un);
+        root = ar.take<uint32_t>(un);
+        flag = ar.take<uint32_t>(un);
+        rank = ar.take<uint32_t>(un);
+        scan_tmp = ar.take<char>(scan_bytes);
+        if (!device) dlabel = ar.take<int32_t>(un);
+      })) return rc;
+  if (int32_t rc = cluster_grid_build(h, &G)) return rc;
   NRM_HIP(hipMemsetAsync(words, 0, kClWords * 8, h->st));
   ClusterArgs A{};
   A.g = G.g; A.n = un; A.r2 = eps * eps; A.min_points = min_points;

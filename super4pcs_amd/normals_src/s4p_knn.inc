@@ -3,14 +3,16 @@
 // on an s4p_normals_ctx after set_cloud, on its cloud, grid and stream.
 //
 // Device path:
-//   lists        k_knn_search<K, kLists>: k_knn_normals' walk (rings, box pruning, min / max insertion into K 64-bit keys in
-//                registers), then the k keys unpacked into idx / d2 / cnt rows in the caller's order.
+//   lists        k_knn_search<K, kLists>: knn_walk of s4p_normals.hip, the walk k_knn_normals runs (rings, box pruning, min /
+//                max insertion into K 64-bit keys in registers), then the k keys unpacked into idx / d2 / cnt rows in the
+//                caller's order.  knn_search_at orders its queries with QueryStage of s4p_normals.hip, as estimate_at does.
 //   statistical  k_knn_search<K, kMean> (8 bytes per point: the mean neighbour distance, no lists) -> k_sor_rows<0> +
 //                k_sor_reduce (mu) -> k_sor_rows<1> + k_sor_reduce (sigma, t) -> k_sor_mask (keep, integer count).
 //   radius       k_knn_search<K, kFilled>: one byte per point, "all k slots filled".
 // Every double sum has a fixed order (a lane's grid-stride terms in order, an LDS tree per workgroup, the rows of the
 // workgroups by one workgroup in the same way); the only atomic is the integer count of kept points.
-// Work memory comes from the context's arena, which only grows: a call allocates when it needs more than any call before.
+// Work memory comes from the context's arena (Arena and arena_layout of s4p_normals.hip): every entry point states its
+// pieces once, and a call allocates when it needs more than any call before.
 
 namespace s4p_nrm {
 
@@ -29,63 +31,6 @@ struct SearchArgs {
   double* mean;               // kMean: m
   uint8_t* filled;            // kFilled: m
 };
-
-// The walk of k_knn_normals (see there for the list layout and the pruning margins), for the query q into the list L;
-// the candidate of index `skip` is passed over (no candidate has index 0xFFFFFFFF: n <= 2^31 - 2).
-template <int K>
-__device__ __forceinline__ void knn_walk(const GridDev& g, const float4 q, const float r2lim, const uint32_t skip, uint64_t (&L)[K]) {
-  const double eps = 1e-6 * g.h;
-  const double qx = double(q.x), qy = double(q.y), qz = double(q.z);
-  const int cx = int(fmin(fmax(cell_coord(q.x, g.ox, g.inv_h), 0.0), double(g.nx - 1)));
-  const int cy = int(fmin(fmax(cell_coord(q.y, g.oy, g.inv_h), 0.0), double(g.ny - 1)));
-  const int cz = int(fmin(fmax(cell_coord(q.z, g.oz, g.inv_h), 0.0), double(g.nz - 1)));
-  for (int R = 0;; ++R) {
-    if (R > 0) {
-      double lb = INFINITY;
-      bool more = false;
-      const int c3[3] = {cx, cy, cz}, d3[3] = {g.nx, g.ny, g.nz};
-      const double o3[3] = {g.ox, g.oy, g.oz}, q3[3] = {qx, qy, qz};
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const int lo = c3[a] - R + 1, hi = c3[a] + R;
-        if (lo > 0) { more = true; lb = fmin(lb, q3[a] - (o3[a] + lo * g.h)); }
-        if (hi < d3[a]) { more = true; lb = fmin(lb, (o3[a] + hi * g.h) - q3[a]); }
-      }
-      if (!more) break;
-      lb -= eps;
-      if (lb > 0.0 && lb * lb * (1.0 - 1e-5) > double(fminf(r2lim, key_d2(L[K - 1])))) break;
-    }
-    const int z0 = max(cz - R, 0), z1 = min(cz + R, g.nz - 1), y0 = max(cy - R, 0), y1 = min(cy + R, g.ny - 1);
-    const int x0 = max(cx - R, 0), x1 = min(cx + R, g.nx - 1);
-    for (int iz = z0; iz <= z1; ++iz)
-      for (int iy = y0; iy <= y1; ++iy) {
-        const bool face = iz == cz - R || iz == cz + R || iy == cy - R || iy == cy + R;
-        const int step = face ? 1 : 2 * R;
-        for (int ix = face ? x0 : cx - R; ix <= x1; ix += step) {
-          if (ix < 0) continue;
-          const double bx0 = g.ox + ix * g.h, by0 = g.oy + iy * g.h, bz0 = g.oz + iz * g.h;
-          const double ex = fmax(0.0, fmax(bx0 - qx, qx - (bx0 + g.h)) - eps);
-          const double ey = fmax(0.0, fmax(by0 - qy, qy - (by0 + g.h)) - eps);
-          const double ez = fmax(0.0, fmax(bz0 - qz, qz - (bz0 + g.h)) - eps);
-          if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(fminf(r2lim, key_d2(L[K - 1])))) continue;
-          const uint2 rg = g.range[(uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix)];
-          for (uint32_t s = rg.x; s < rg.y; ++s) {
-            const float4 p = g.pts[s];
-            const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-            const float d2 = dx * dx + (dy * dy + dz * dz);
-            uint64_t c = knn_key(d2, __float_as_uint(p.w));
-            if (!(d2 <= r2lim) || !(c < L[K - 1]) || __float_as_uint(p.w) == skip) continue;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-              const uint64_t lo = c < L[t] ? c : L[t], hi = c < L[t] ? L[t] : c;
-              L[t] = lo;
-              c = hi;
-            }
-          }
-        }
-      }
-  }
-}
 
 // One lane per query, as k_knn_normals; MODE picks what is kept of the list.
 template <int K, int MODE>
@@ -197,33 +142,6 @@ __global__ __launch_bounds__(kBlock) void k_sor_mask(const double* v, uint64_t n
 
 namespace {
 
-constexpr size_t kArenaAlign = 256;
-inline size_t arena_round(size_t b) { return (std::max<size_t>(b, 1) + kArenaAlign - 1) / kArenaAlign * kArenaAlign; }
-
-// hands out pieces of the context's arena; reserve() first with the sum of arena_round() of every piece
-struct Arena {
-  char* base;
-  size_t off = 0;
-  template <class T> T* take(size_t count) {
-    T* p = reinterpret_cast<T*>(base + off);
-    off += arena_round(count * sizeof(T));
-    return p;
-  }
-};
-
-int32_t arena_reserve(s4p_normals_ctx* h, size_t bytes, Arena* a) {
-  if (h->arena_bytes < bytes) {
-    NRM_HIP(hipStreamSynchronize(h->st));
-    dfree(h->arena);
-    h->arena = nullptr; h->arena_bytes = 0;
-    NRM_HIP(hipMalloc(&h->arena, bytes));
-    h->arena_bytes = bytes;
-  }
-  a->base = static_cast<char*>(h->arena);
-  a->off = 0;
-  return S4P_NORMALS_OK;
-}
-
 int32_t knn_check(s4p_normals_ctx* h, const char* what, int32_t k) {
   if (!h->has_cloud) return fail(h, S4P_NORMALS_ERR_STATE, std::string(what) + ": set_cloud first");
   if (k < S4P_KNN_MIN_K || k > S4P_KNN_MAX_K) return fail(h, S4P_NORMALS_ERR_BAD_ARG, std::string(what) + ": k must be in [1, 32]");
@@ -243,32 +161,33 @@ int32_t launch_search(s4p_normals_ctx* h, SearchArgs& A, float radius) {
   return S4P_NORMALS_OK;
 }
 
-// lists of m queries (cell order, device) into idx / d2 / cnt: the caller's (device) or arena copies brought back (host)
-int32_t lists_impl(s4p_normals_ctx* h, Arena& ar, const float4* qs, uint64_t m, int32_t k, float radius, bool exclude_self,
+// where a lists call writes: the caller's arrays (device form), or arena copies that are brought back (host form)
+struct ListsDev {
+  int32_t* idx;
+  float* d2;
+  int32_t* cnt;
+  void take(Arena& ar, uint64_t m, int32_t k, bool with_cnt) {
+    idx = ar.take<int32_t>(size_t(m) * size_t(k));
+    d2 = ar.take<float>(size_t(m) * size_t(k));
+    cnt = with_cnt ? ar.take<int32_t>(m) : nullptr;
+  }
+};
+
+// lists of m queries (cell order, device) into D, and from there into idx / d2 / cnt in the host form
+int32_t lists_impl(s4p_normals_ctx* h, const ListsDev& D, const float4* qs, uint64_t m, int32_t k, float radius, bool exclude_self,
                    int32_t* idx, float* d2, int32_t* cnt, bool device) {
   SearchArgs A{};
   A.qs = qs; A.m = m; A.k = k; A.self_mask = exclude_self ? ~0u : 0u;
-  A.idx = idx; A.d2 = d2; A.cnt = cnt;
-  const size_t mk = size_t(m) * size_t(k);
-  if (!device) {
-    A.idx = ar.take<int32_t>(mk);
-    A.d2 = ar.take<float>(mk);
-    A.cnt = cnt ? ar.take<int32_t>(m) : nullptr;
-  }
+  A.idx = D.idx; A.d2 = D.d2; A.cnt = D.cnt;
   if (int32_t rc = launch_search<kLists>(h, A, radius)) return rc;
   if (!device) {
-    NRM_HIP(hipMemcpyAsync(idx, A.idx, mk * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
-    NRM_HIP(hipMemcpyAsync(d2, A.d2, mk * sizeof(float), hipMemcpyDeviceToHost, h->st));
-    if (cnt) NRM_HIP(hipMemcpyAsync(cnt, A.cnt, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    const size_t mk = size_t(m) * size_t(k);
+    NRM_HIP(hipMemcpyAsync(idx, D.idx, mk * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
+    NRM_HIP(hipMemcpyAsync(d2, D.d2, mk * sizeof(float), hipMemcpyDeviceToHost, h->st));
+    if (cnt) NRM_HIP(hipMemcpyAsync(cnt, D.cnt, m * sizeof(int32_t), hipMemcpyDeviceToHost, h->st));
   }
   NRM_HIP(hipStreamSynchronize(h->st));
   return S4P_NORMALS_OK;
-}
-
-size_t lists_bytes(uint64_t m, int32_t k, bool with_cnt, bool device) {
-  if (device) return 0;
-  const size_t mk = size_t(m) * size_t(k);
-  return arena_round(mk * sizeof(int32_t)) + arena_round(mk * sizeof(float)) + (with_cnt ? arena_round(m * sizeof(int32_t)) : 0);
 }
 
 int32_t search_impl(s4p_normals_ctx* h, int32_t k, float radius, int32_t exclude_self, int32_t* idx, float* d2, int32_t* cnt,
@@ -279,10 +198,10 @@ int32_t search_impl(s4p_normals_ctx* h, int32_t k, float radius, int32_t exclude
   if (exclude_self != 0 && exclude_self != 1) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "knn_search: exclude_self must be 0 or 1");
   if (!idx || !d2) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "knn_search: null output");
   NRM_HIP(hipSetDevice(h->device));
-  Arena ar;
   const uint64_t un = uint64_t(h->n);
-  if (int32_t rc = arena_reserve(h, lists_bytes(un, k, cnt != nullptr, device), &ar)) return rc;
-  return lists_impl(h, ar, h->pts, un, k, radius, exclude_self == 1, idx, d2, cnt, device);
+  ListsDev D{idx, d2, cnt};
+  if (int32_t rc = arena_layout(h, "knn_search", [&](Arena& ar) { if (!device) D.take(ar, un, k, cnt != nullptr); })) return rc;
+  return lists_impl(h, D, h->pts, un, k, radius, exclude_self == 1, idx, d2, cnt, device);
 }
 
 int32_t search_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, const float* qz, int64_t m, int32_t k, float radius,
@@ -295,38 +214,15 @@ int32_t search_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, con
   if (!qx || !qy || !qz || !idx || !d2) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "knn_search_at: null argument");
   NRM_HIP(hipSetDevice(h->device));
   const uint64_t um = uint64_t(m);
-  uint32_t* nokey = nullptr;
-  size_t sort_bytes = 0;
-  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t*)nokey, nokey, (const uint32_t*)nokey, nokey, int(um), 0,
-                                             end_bit(h->ncell), h->st));
-  Arena ar;
-  const size_t need = 3 * arena_round(um * sizeof(float)) + 2 * arena_round(um * sizeof(float4)) + 4 * arena_round(um * 4) +
-                      arena_round(sort_bytes) + lists_bytes(um, k, cnt != nullptr, device);
-  if (int32_t rc = arena_reserve(h, need, &ar)) return rc;
-  const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  float* p[3];
-  const float* in[3] = {qx, qy, qz};
-  for (int a = 0; a < 3; ++a) {
-    p[a] = ar.take<float>(um);
-    NRM_HIP(hipMemcpyAsync(p[a], in[a], um * sizeof(float), kind, h->st));
-  }
-  float4* qp = ar.take<float4>(um);
-  float4* qs = ar.take<float4>(um);
-  uint32_t* keys = ar.take<uint32_t>(um);
-  uint32_t* vals = ar.take<uint32_t>(um);
-  uint32_t* keys2 = ar.take<uint32_t>(um);
-  uint32_t* vals2 = ar.take<uint32_t>(um);
-  void* tmp = ar.take<char>(sort_bytes);
-  const int nb = blocks_for(m);
-  hipLaunchKernelGGL(k_pack, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], um, qp);
-  NRM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, um, h->g, keys, vals);
-  NRM_HIP(hipGetLastError());
-  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sort_bytes, (const uint32_t*)keys, keys2, (const uint32_t*)vals, vals2, int(um), 0,
-                                             end_bit(h->ncell), h->st));
-  hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, (const uint32_t*)vals2, um, qs);
-  NRM_HIP(hipGetLastError());
-  return lists_impl(h, ar, qs, um, k, radius, false, idx, d2, cnt, device);
+  QueryStage Q;
+  if (int32_t rc = Q.plan(h, um)) return rc;
+  ListsDev D{idx, d2, cnt};
+  if (int32_t rc = arena_layout(h, "knn_search_at", [&](Arena& ar) {
+        Q.take(ar);
+        if (!device) D.take(ar, um, k, cnt != nullptr);
+      })) return rc;
+  if (int32_t rc = Q.run(h, qx, qy, qz, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) return rc;
+  return lists_impl(h, D, Q.qs, um, k, radius, false, idx, d2, cnt, device);
 }
 
 int32_t statistical_impl(s4p_normals_ctx* h, int32_t k, double std_ratio, double* mean_dist, uint8_t* keep, s4p_outliers_stats* stats,
@@ -340,14 +236,15 @@ int32_t statistical_impl(s4p_normals_ctx* h, int32_t k, double std_ratio, double
   const uint64_t un = uint64_t(h->n);
   const int nb = blocks_for(h->n);
   const bool own_mean = !device || !mean_dist;
-  Arena ar;
-  const size_t need = (own_mean ? arena_round(un * sizeof(double)) : 0) + (device ? 0 : arena_round(un)) +
-                      arena_round(size_t(nb) * sizeof(double)) + arena_round(sizeof(SorDev));
-  if (int32_t rc = arena_reserve(h, need, &ar)) return rc;
-  double* md = own_mean ? ar.take<double>(un) : mean_dist;
-  uint8_t* dkeep = device ? keep : ar.take<uint8_t>(un);
-  double* rows = ar.take<double>(size_t(nb));
-  SorDev* st = ar.take<SorDev>(1);
+  double *md = mean_dist, *rows = nullptr;
+  uint8_t* dkeep = keep;
+  SorDev* st = nullptr;
+  if (int32_t rc = arena_layout(h, "outliers_statistical", [&](Arena& ar) {
+        if (own_mean) md = ar.take<double>(un);
+        if (!device) dkeep = ar.take<uint8_t>(un);
+        rows = ar.take<double>(size_t(nb));
+        st = ar.take<SorDev>(1);
+      })) return rc;
   SearchArgs A{};
   A.qs = h->pts; A.m = un; A.k = k; A.self_mask = ~0u; A.mean = md;
   if (int32_t rc = launch_search<kMean>(h, A, -1.f)) return rc;
@@ -382,9 +279,8 @@ int32_t radius_impl(s4p_normals_ctx* h, float radius, int32_t min_neighbours, ui
   if (!keep) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "outliers_radius: null keep");
   NRM_HIP(hipSetDevice(h->device));
   const uint64_t un = uint64_t(h->n);
-  Arena ar;
-  if (int32_t rc = arena_reserve(h, device ? 0 : arena_round(un), &ar)) return rc;
-  uint8_t* dkeep = device ? keep : ar.take<uint8_t>(un);
+  uint8_t* dkeep = keep;
+  if (int32_t rc = arena_layout(h, "outliers_radius", [&](Arena& ar) { if (!device) dkeep = ar.take<uint8_t>(un); })) return rc;
   SearchArgs A{};
   A.qs = h->pts; A.m = un; A.k = min_neighbours; A.self_mask = ~0u; A.filled = dkeep;
   if (int32_t rc = launch_search<kFilled>(h, A, radius)) return rc;

@@ -10,9 +10,15 @@
 //   voxel-grid downsampling (include/s4p_voxel.h): s4p_voxel.inc, of a cloud passed per call, on the context's stream.
 //   normal orientation (include/s4p_normals_orient.h): s4p_orient.inc, a minimum spanning forest over the lists' graph.
 //   density clustering (include/s4p_cluster.h): s4p_cluster.inc, a fixed-radius walk on a grid of edge eps and a union-find.
-//   estimate    queries in cell order (the cloud itself, or k_cell_keys + sort + k_gather of the caller's queries) ->
-//               k_knn_normals<K>: one lane per query, ring search with conservative box pruning, the k best (d2, index)
-//               sorted in registers, covariance in double, 3x3 Jacobi, the normal scattered to the caller's order.
+//   estimate    queries in cell order (the cloud itself, or QueryStage: k_cell_keys + sort + k_gather of the caller's
+//               queries) -> k_knn_normals<K>: one lane per query, knn_walk (ring search with conservative box pruning, the
+//               k best (d2, index) sorted in registers), covariance in double, 3x3 Jacobi, the normal scattered to the
+//               caller's order.
+// Shared by the files included below, and defined here: knn_walk<K>, the one neighbour walk (k_knn_normals and
+// s4p_knn.inc's k_knn_search call it); QueryStage, the one staging of caller queries (estimate_at and knn_search_at);
+// bounds_rows<SKIP> + cloud_bounds (set_cloud's k_bounds and voxel_downsample's k_voxel_bounds); Arena, arena_reserve and arena_layout, through which
+// every per-call entry point states its work memory once.  set_cloud and grid keep per-call allocations (Scratch): their
+// memory is proportional to the cloud and is freed on return.
 // No float or double atomics: every sum has a fixed order, so two calls return identical bits.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -55,19 +61,22 @@ __global__ __launch_bounds__(kBlock) void k_pack(const float* x, const float* y,
     out[i] = make_float4(x[i], y[i], z[i], __uint_as_float(uint32_t(i)));
 }
 
-// per-block float minima and maxima (rows of 6); NaN propagates through the finiteness check on the host
-__global__ __launch_bounds__(kBlock) void k_bounds(const float4* p, uint64_t n, float* rows) {
+// per-block float minima and maxima (rows of 6).  A point with a non-finite coordinate is skipped (SKIP: a block that saw
+// no finite point leaves +inf / -inf), or poisons the block's row: its first entry is NaN, which the tree and the host
+// fold pass on
+template <bool SKIP>
+__device__ __forceinline__ void bounds_rows(const float4* p, uint64_t n, float* rows) {
   float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
   bool bad = false;
   for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
     const float4 q = p[i];
-    const float c[3] = {q.x, q.y, q.z};
-    for (int a = 0; a < 3; ++a) {
-      bad |= !isfinite(c[a]);
-      v[a] = fminf(v[a], c[a]); v[3 + a] = fmaxf(v[3 + a], c[a]);
-    }
+    const bool fin = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
+    if (SKIP && !fin) continue;
+    bad |= !fin;
+    v[0] = fminf(v[0], q.x); v[1] = fminf(v[1], q.y); v[2] = fminf(v[2], q.z);
+    v[3] = fmaxf(v[3], q.x); v[4] = fmaxf(v[4], q.y); v[5] = fmaxf(v[5], q.z);
   }
-  if (bad) v[0] = NAN;
+  if (!SKIP && bad) v[0] = NAN;
   __shared__ float sh[kBlock];
   for (int k = 0; k < 6; ++k) {
     sh[threadIdx.x] = v[k];
@@ -75,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_bounds(const float4* p, uint64_t n, 
     for (int w = kBlock / 2; w > 0; w >>= 1) {
       if (threadIdx.x < unsigned(w)) {
         const float a = sh[threadIdx.x], b = sh[threadIdx.x + w];
-        sh[threadIdx.x] = (a != a || b != b) ? NAN : (k < 3 ? fminf(a, b) : fmaxf(a, b));
+        sh[threadIdx.x] = (!SKIP && (a != a || b != b)) ? NAN : (k < 3 ? fminf(a, b) : fmaxf(a, b));
       }
       __syncthreads();
     }
@@ -83,6 +92,8 @@ __global__ __launch_bounds__(kBlock) void k_bounds(const float4* p, uint64_t n, 
     __syncthreads();
   }
 }
+__global__ __launch_bounds__(kBlock) void k_bounds(const float4* p, uint64_t n, float* rows) { bounds_rows<false>(p, n, rows); }
+__global__ __launch_bounds__(kBlock) void k_voxel_bounds(const float4* p, uint64_t n, float* rows) { bounds_rows<true>(p, n, rows); }
 
 __global__ __launch_bounds__(64) void k_gather_samples(const float4* p, const uint32_t* idx, int s, float4* out) {
   if (int(threadIdx.x) < s) out[threadIdx.x] = p[idx[threadIdx.x]];
@@ -202,13 +213,84 @@ struct KnnArgs {
 __device__ inline uint64_t knn_key(float d2, uint32_t i) { return (uint64_t(__float_as_uint(d2)) + 1u) << 32 | i; }
 __device__ inline float key_d2(uint64_t key) { return key == ~0ull ? INFINITY : __uint_as_float(uint32_t(key >> 32) - 1u); }
 
-// One lane per query.  The list holds K keys in ascending order: K - k sentinels 0 in front that no candidate passes, then
-// the k best so far, padded with ~0.  Its last entry is the k-th best, the pruning bound.
+// The neighbour walk of every list in this library (k_knn_normals here, k_knn_search in s4p_knn.inc), for the query q into
+// the list L.  The list holds K keys in ascending order: K - k sentinels 0 in front that no candidate passes, then the k
+// best so far, padded with ~0.  Its last entry is the k-th best, the pruning bound.
 // Rings of cells around the query's (clamped) cell are visited in order R = 0, 1, ...; before ring R the search stops
 // when every cell outside the (2R - 1)^3 block already visited is farther than the bound, and inside a ring a cell is
 // skipped when its box is.  Box distances are in double, widened by 1e-6 h for the rounding of the cell location and
 // compared with a (1 - 1e-5) factor that exceeds the rounding of any float d2 (as the ICP library's nearest()): a skipped
 // point can neither enter the list nor tie with its last entry.
+// The walk is one text, S4P_KNN_WALK, expanded twice.  In k_knn_normals it stands in the kernel, because a walk that the
+// kernel calls is compiled on its own first, with the list in memory behind a reference, and the kernel then carries the
+// list twice (156 / 252 VGPRs against 131 / 193, estimate at k = 16 one percent slower).  knn_walk<K>
+// is the same text as a function, as k_knn_search has always called it.  PASS is the test for a candidate p that is
+// passed over: the own index in knn_walk (no candidate has index 0xFFFFFFFF: n <= 2^31 - 2), nothing in k_knn_normals.
+// QX, QY, QZ are the query in double and EPS is 1e-6 h, both computed where the text stands; of the text's own names PASS
+// may use only p, the candidate (index in p.w).
+// Inside: the nearest face of the visited block beyond which cells remain bounds ring R; the insertion is one min / max
+// pass, after which the list is still sorted and its largest key has dropped out.
+#define S4P_KNN_WALK(K, G, Q, QX, QY, QZ, EPS, R2LIM, PASS, L)                                                              \
+  {                                                                                                                         \
+    const int cx = int(fmin(fmax(cell_coord((Q).x, (G).ox, (G).inv_h), 0.0), double((G).nx - 1)));                          \
+    const int cy = int(fmin(fmax(cell_coord((Q).y, (G).oy, (G).inv_h), 0.0), double((G).ny - 1)));                          \
+    const int cz = int(fmin(fmax(cell_coord((Q).z, (G).oz, (G).inv_h), 0.0), double((G).nz - 1)));                          \
+    for (int R = 0;; ++R) {                                                                                                 \
+      if (R > 0) {                                                                                                          \
+        double lb = INFINITY;                                                                                               \
+        bool more = false;                                                                                                  \
+        const int c3[3] = {cx, cy, cz}, d3[3] = {(G).nx, (G).ny, (G).nz};                                                   \
+        const double o3[3] = {(G).ox, (G).oy, (G).oz}, q3[3] = {(QX), (QY), (QZ)};                                          \
+        _Pragma("unroll")                                                                                                   \
+        for (int a = 0; a < 3; ++a) {                                                                                       \
+          const int lo = c3[a] - R + 1, hi = c3[a] + R;                                                                     \
+          if (lo > 0) { more = true; lb = fmin(lb, q3[a] - (o3[a] + lo * (G).h)); }                                         \
+          if (hi < d3[a]) { more = true; lb = fmin(lb, (o3[a] + hi * (G).h) - q3[a]); }                                     \
+        }                                                                                                                   \
+        if (!more) break;                                                                                                   \
+        lb -= (EPS);                                                                                                        \
+        if (lb > 0.0 && lb * lb * (1.0 - 1e-5) > double(fminf((R2LIM), key_d2(L[K - 1])))) break;                           \
+      }                                                                                                                     \
+      const int z0 = max(cz - R, 0), z1 = min(cz + R, (G).nz - 1), y0 = max(cy - R, 0), y1 = min(cy + R, (G).ny - 1);       \
+      const int x0 = max(cx - R, 0), x1 = min(cx + R, (G).nx - 1);                                                          \
+      for (int iz = z0; iz <= z1; ++iz)                                                                                     \
+        for (int iy = y0; iy <= y1; ++iy) {                                                                                 \
+          const bool face = iz == cz - R || iz == cz + R || iy == cy - R || iy == cy + R;                                   \
+          const int step = face ? 1 : 2 * R;                                                                                \
+          for (int ix = face ? x0 : cx - R; ix <= x1; ix += step) {                                                         \
+            if (ix < 0) continue;                                                                                           \
+            const double bx0 = (G).ox + ix * (G).h, by0 = (G).oy + iy * (G).h, bz0 = (G).oz + iz * (G).h;                   \
+            const double ex = fmax(0.0, fmax(bx0 - (QX), (QX) - (bx0 + (G).h)) - (EPS));                                    \
+            const double ey = fmax(0.0, fmax(by0 - (QY), (QY) - (by0 + (G).h)) - (EPS));                                    \
+            const double ez = fmax(0.0, fmax(bz0 - (QZ), (QZ) - (bz0 + (G).h)) - (EPS));                                    \
+            if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(fminf((R2LIM), key_d2(L[K - 1])))) continue;          \
+            const uint2 rg = (G).range[(uint32_t(iz) * uint32_t((G).ny) + uint32_t(iy)) * uint32_t((G).nx) + uint32_t(ix)]; \
+            for (uint32_t s = rg.x; s < rg.y; ++s) {                                                                        \
+              const float4 p = (G).pts[s];                                                                                  \
+              const float dx = p.x - (Q).x, dy = p.y - (Q).y, dz = p.z - (Q).z;                                             \
+              const float d2 = dx * dx + (dy * dy + dz * dz);                                                               \
+              uint64_t c = knn_key(d2, __float_as_uint(p.w));                                                               \
+              if (!(d2 <= (R2LIM)) || !(c < L[K - 1]) || (PASS)) continue;                                                  \
+              _Pragma("unroll")                                                                                             \
+              for (int t = 0; t < K; ++t) {                                                                                 \
+                const uint64_t lo = c < L[t] ? c : L[t], hi = c < L[t] ? L[t] : c;                                          \
+                L[t] = lo;                                                                                                  \
+                c = hi;                                                                                                     \
+              }                                                                                                             \
+            }                                                                                                               \
+          }                                                                                                                 \
+        }                                                                                                                   \
+    }                                                                                                                       \
+  }
+
+template <int K>
+__device__ __forceinline__ void knn_walk(const GridDev& g, const float4 q, const float r2lim, const uint32_t skip, uint64_t (&L)[K]) {
+  const double eps = 1e-6 * g.h;
+  const double qx = double(q.x), qy = double(q.y), qz = double(q.z);
+  S4P_KNN_WALK(K, g, q, qx, qy, qz, eps, r2lim, __float_as_uint(p.w) == skip, L)
+}
+
+// One lane per query: the walk (no candidate is passed over), then the normal of the list.
 template <int K>
 __global__ __launch_bounds__(kBlock) void k_knn_normals(KnnArgs A) {
   const GridDev& g = A.g;
@@ -218,61 +300,10 @@ __global__ __launch_bounds__(kBlock) void k_knn_normals(KnnArgs A) {
     uint64_t L[K];
 #pragma unroll
     for (int t = 0; t < K; ++t) L[t] = t < K - A.k ? 0ull : ~0ull;
+    // tested before the conversion, not in the if: the other order compiles to another kernel, 1 % slower
     const bool finite = isfinite(q.x) && isfinite(q.y) && isfinite(q.z);
     const double qx = double(q.x), qy = double(q.y), qz = double(q.z);
-    if (finite) {
-      const int cx = int(fmin(fmax(cell_coord(q.x, g.ox, g.inv_h), 0.0), double(g.nx - 1)));
-      const int cy = int(fmin(fmax(cell_coord(q.y, g.oy, g.inv_h), 0.0), double(g.ny - 1)));
-      const int cz = int(fmin(fmax(cell_coord(q.z, g.oz, g.inv_h), 0.0), double(g.nz - 1)));
-      for (int R = 0;; ++R) {
-        if (R > 0) {
-          // the nearest face of the visited block beyond which cells remain
-          double lb = INFINITY;
-          bool more = false;
-          const int c3[3] = {cx, cy, cz}, d3[3] = {g.nx, g.ny, g.nz};
-          const double o3[3] = {g.ox, g.oy, g.oz}, q3[3] = {qx, qy, qz};
-#pragma unroll
-          for (int a = 0; a < 3; ++a) {
-            const int lo = c3[a] - R + 1, hi = c3[a] + R;
-            if (lo > 0) { more = true; lb = fmin(lb, q3[a] - (o3[a] + lo * g.h)); }
-            if (hi < d3[a]) { more = true; lb = fmin(lb, (o3[a] + hi * g.h) - q3[a]); }
-          }
-          if (!more) break;
-          lb -= eps;
-          if (lb > 0.0 && lb * lb * (1.0 - 1e-5) > double(fminf(A.r2lim, key_d2(L[K - 1])))) break;
-        }
-        const int z0 = max(cz - R, 0), z1 = min(cz + R, g.nz - 1), y0 = max(cy - R, 0), y1 = min(cy + R, g.ny - 1);
-        const int x0 = max(cx - R, 0), x1 = min(cx + R, g.nx - 1);
-        for (int iz = z0; iz <= z1; ++iz)
-          for (int iy = y0; iy <= y1; ++iy) {
-            const bool face = iz == cz - R || iz == cz + R || iy == cy - R || iy == cy + R;
-            const int step = face ? 1 : 2 * R;
-            for (int ix = face ? x0 : cx - R; ix <= x1; ix += step) {
-              if (ix < 0) continue;
-              const double bx0 = g.ox + ix * g.h, by0 = g.oy + iy * g.h, bz0 = g.oz + iz * g.h;
-              const double ex = fmax(0.0, fmax(bx0 - qx, qx - (bx0 + g.h)) - eps);
-              const double ey = fmax(0.0, fmax(by0 - qy, qy - (by0 + g.h)) - eps);
-              const double ez = fmax(0.0, fmax(bz0 - qz, qz - (bz0 + g.h)) - eps);
-              if ((ex * ex + ey * ey + ez * ez) * (1.0 - 1e-5) > double(fminf(A.r2lim, key_d2(L[K - 1])))) continue;
-              const uint2 rg = g.range[(uint32_t(iz) * uint32_t(g.ny) + uint32_t(iy)) * uint32_t(g.nx) + uint32_t(ix)];
-              for (uint32_t s = rg.x; s < rg.y; ++s) {
-                const float4 p = g.pts[s];
-                const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
-                const float d2 = dx * dx + (dy * dy + dz * dz);
-                uint64_t c = knn_key(d2, __float_as_uint(p.w));
-                if (!(d2 <= A.r2lim) || !(c < L[K - 1])) continue;
-                // insertion by one min / max pass: the list stays sorted and its largest key drops out
-#pragma unroll
-                for (int t = 0; t < K; ++t) {
-                  const uint64_t lo = c < L[t] ? c : L[t], hi = c < L[t] ? L[t] : c;
-                  L[t] = lo;
-                  c = hi;
-                }
-              }
-            }
-          }
-      }
-    }
+    if (finite) S4P_KNN_WALK(K, g, q, qx, qy, qz, eps, A.r2lim, false, L)
     // covariance in double, neighbours in ascending (d2, index) order
     double se[3] = {0.0, 0.0, 0.0}, see[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     int32_t cnt = 0;
@@ -339,7 +370,7 @@ struct s4p_normals_ctx {
   float4* pos = nullptr;             // caller order
   float4* pts = nullptr;             // cell order
   uint2* range = nullptr;
-  void* arena = nullptr;             // work memory of the s4p_knn.h calls: grows, never shrinks
+  void* arena = nullptr;             // work memory of the per-call entry points (Arena below): grows, never shrinks
   size_t arena_bytes = 0;
 };
 
@@ -371,6 +402,54 @@ struct Scratch {
   }
 };
 
+// The context's arena is the work memory of every per-call entry point; it only grows: a call allocates when it needs more
+// than any call before.  An Arena hands out its pieces in order.  Without a base it only measures: take() returns null and
+// off ends as the byte count of the pieces.  On a base, a piece that would end past cap is refused (null, over set).
+constexpr size_t kArenaAlign = 256;
+inline size_t arena_round(size_t b) { return (std::max<size_t>(b, 1) + kArenaAlign - 1) / kArenaAlign * kArenaAlign; }
+
+struct Arena {
+  char* base = nullptr;
+  size_t cap = 0, off = 0;
+  bool over = false;
+  template <class T> T* take(size_t count) {
+    const size_t at = off;
+    off += arena_round(count * sizeof(T));
+    if (base && off > cap) over = true;
+    return base && !over ? reinterpret_cast<T*>(base + at) : nullptr;
+  }
+};
+
+int32_t arena_reserve(s4p_normals_ctx* h, size_t bytes, Arena* a) {
+  if (h->arena_bytes < bytes) {
+    NRM_HIP(hipStreamSynchronize(h->st));
+    dfree(h->arena);
+    h->arena = nullptr; h->arena_bytes = 0;
+    NRM_HIP(hipMalloc(&h->arena, bytes));
+    h->arena_bytes = bytes;
+  }
+  *a = Arena{static_cast<char*>(h->arena), h->arena_bytes};
+  return S4P_NORMALS_OK;
+}
+
+// The code of a failure that no argument explains; S4P_ORIENT_ERR_INTERNAL and S4P_CLUSTER_ERR_INTERNAL are this value.
+// s4p_normals.h, s4p_knn.h and s4p_voxel.h name no internal code and do not document -8; their entry points return it only
+// from arena_layout's check, which a single statement of the layout cannot reach.
+constexpr int32_t kErrInternal = -8;
+
+// An entry point states its arena pieces once, as a function of an Arena that takes them in order: it is run without a
+// base to measure them, the arena is made that large, and it is run again on the arena.  The second run cannot pass the
+// first one's end; if a mistake ever lets it, the call fails here, before anything is launched on a piece.
+template <class Pieces>
+int32_t arena_layout(s4p_normals_ctx* h, const char* what, Pieces&& pieces) {
+  Arena ar;
+  pieces(ar);
+  if (int32_t rc = arena_reserve(h, ar.off, &ar)) return rc;
+  pieces(ar);
+  if (ar.over) return fail(h, kErrInternal, std::string(what) + ": the arena pieces exceed the bytes measured for them");
+  return S4P_NORMALS_OK;
+}
+
 int end_bit(uint64_t max_key) {
   int b = 1;
   while (b < 32 && (max_key >> b) != 0) ++b;
@@ -382,16 +461,6 @@ int32_t sort_pairs_bytes(s4p_normals_ctx* h, uint64_t n, uint64_t max_key, size_
   *bytes = 0;
   NRM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (const uint32_t*)none, none, (const uint32_t*)none, none, int(n), 0,
                                              end_bit(max_key), h->st));
-  return S4P_NORMALS_OK;
-}
-
-int32_t sort_pairs(s4p_normals_ctx* h, Scratch& S, const uint32_t* keys, uint32_t* keys_out, const uint32_t* vals, uint32_t* vals_out,
-                   uint64_t n, uint64_t max_key) {
-  size_t bytes = 0;
-  if (int32_t rc = sort_pairs_bytes(h, n, max_key, &bytes)) return rc;
-  void* tmp = nullptr;
-  NRM_HIP(S.alloc(&tmp, bytes));
-  NRM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, keys_out, vals, vals_out, int(n), 0, end_bit(max_key), h->st));
   return S4P_NORMALS_OK;
 }
 
@@ -438,6 +507,27 @@ int32_t fill_grid(s4p_normals_ctx* h, const float4* pos, uint64_t un, const Grid
 }
 
 constexpr int64_t kMaxPoints = int64_t(0x7FFFFFFE);
+
+// The bounds of pos: k_voxel_bounds (skip) or k_bounds into rows (6 floats per workgroup of blocks_for(n)), brought to the host and folded.
+// SKIP: over the finite points, lo > hi when there is none; otherwise lo[a] is NaN when any coordinate is not finite.
+// Waits for the stream.
+int32_t cloud_bounds(s4p_normals_ctx* h, bool skip, const float4* pos, uint64_t un, float* rows, float lo[3], float hi[3]) {
+  const int nb = blocks_for(int64_t(un));
+  if (skip) hipLaunchKernelGGL(k_voxel_bounds, dim3(nb), dim3(kBlock), 0, h->st, pos, un, rows);
+  else hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(kBlock), 0, h->st, pos, un, rows);
+  NRM_HIP(hipGetLastError());
+  std::vector<float> hr(size_t(nb) * 6);
+  NRM_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(float), hipMemcpyDeviceToHost, h->st));
+  NRM_HIP(hipStreamSynchronize(h->st));
+  for (int a = 0; a < 3; ++a) { lo[a] = INFINITY; hi[a] = -INFINITY; }
+  for (int b = 0; b < nb; ++b)
+    for (int a = 0; a < 3; ++a) {
+      const float l = hr[size_t(b) * 6 + a], u = hr[size_t(b) * 6 + 3 + a];
+      lo[a] = (l != l || lo[a] != lo[a]) ? NAN : std::min(lo[a], l);
+      hi[a] = std::max(hi[a], u);
+    }
+  return S4P_NORMALS_OK;
+}
 
 // The cell edge: the median over kSamples seeded sample points of their distance to the kPlanK-th neighbour (the upper
 // edge of the histogram bin where the count, the point itself included, reaches kPlanK; at most L / 32).
@@ -507,19 +597,8 @@ int32_t set_cloud_impl(s4p_normals_ctx* h, const float* x, const float* y, const
   NRM_HIP(hipGetLastError());
   float* rows;
   NRM_HIP(S.alloc((void**)&rows, size_t(nb) * 6 * sizeof(float)));
-  hipLaunchKernelGGL(k_bounds, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)h->pos, un, rows);
-  NRM_HIP(hipGetLastError());
-  std::vector<float> hr(size_t(nb) * 6);
-  NRM_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(float), hipMemcpyDeviceToHost, h->st));
-  NRM_HIP(hipStreamSynchronize(h->st));
   float lo[3], hi[3];
-  for (int a = 0; a < 3; ++a) { lo[a] = hr[a]; hi[a] = hr[3 + a]; }
-  for (int b = 0; b < nb; ++b)
-    for (int a = 0; a < 3; ++a) {
-      const float l = hr[size_t(b) * 6 + a], u = hr[size_t(b) * 6 + 3 + a];
-      lo[a] = (l != l || lo[a] != lo[a]) ? NAN : std::min(lo[a], l);
-      hi[a] = std::max(hi[a], u);
-    }
+  if (int32_t rc = cloud_bounds(h, false, h->pos, un, rows, lo, hi)) return rc;
   for (int a = 0; a < 3; ++a)
     if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: non-finite coordinates");
   double spacing = 0.0;
@@ -575,15 +654,52 @@ int32_t estimate_impl(s4p_normals_ctx* h, int32_t k, float radius, float* out, b
   if (int32_t rc = check_args(h, k, radius)) return rc;
   if (!out) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate: null output");
   NRM_HIP(hipSetDevice(h->device));
-  Scratch S;
   const uint64_t un = uint64_t(h->n);
   float* dout = out;
-  if (!device_out) NRM_HIP(S.alloc((void**)&dout, 3 * un * sizeof(float)));
+  if (int32_t rc = arena_layout(h, "estimate", [&](Arena& ar) { if (!device_out) dout = ar.take<float>(3 * un); })) return rc;
   if (int32_t rc = run_knn(h, h->pts, un, k, radius, dout)) return rc;
   if (!device_out) NRM_HIP(hipMemcpyAsync(out, dout, 3 * un * sizeof(float), hipMemcpyDeviceToHost, h->st));
   NRM_HIP(hipStreamSynchronize(h->st));
   return S4P_NORMALS_OK;
 }
+
+// Caller queries -> cell-ordered float4 with the output slot in w (what k_knn_normals and k_knn_search read): the SoA
+// copy, k_pack, k_cell_keys on the context's grid, the radix sort of (cell, slot), k_gather.  plan() before the layout,
+// take() in it, run() after it; nothing waits.
+struct QueryStage {
+  uint64_t m = 0;
+  size_t sort_bytes = 0;
+  float* p[3] = {nullptr, nullptr, nullptr};
+  float4 *qp = nullptr, *qs = nullptr;      // caller order, cell order
+  uint32_t *keys = nullptr, *vals = nullptr, *keys2 = nullptr, *vals2 = nullptr;
+  void* tmp = nullptr;
+
+  int32_t plan(s4p_normals_ctx* h, uint64_t um) {
+    m = um;
+    return sort_pairs_bytes(h, m, h->ncell, &sort_bytes);      // keys reach ncell: a non-finite query sorts last
+  }
+  void take(Arena& ar) {
+    for (int a = 0; a < 3; ++a) p[a] = ar.take<float>(m);
+    qp = ar.take<float4>(m); qs = ar.take<float4>(m);
+    keys = ar.take<uint32_t>(m); vals = ar.take<uint32_t>(m); keys2 = ar.take<uint32_t>(m); vals2 = ar.take<uint32_t>(m);
+    tmp = ar.take<char>(sort_bytes);
+  }
+  int32_t run(s4p_normals_ctx* h, const float* qx, const float* qy, const float* qz, hipMemcpyKind kind) const {
+    const float* in[3] = {qx, qy, qz};
+    for (int a = 0; a < 3; ++a) NRM_HIP(hipMemcpyAsync(p[a], in[a], m * sizeof(float), kind, h->st));
+    const int nb = blocks_for(int64_t(m));
+    hipLaunchKernelGGL(k_pack, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], m, qp);
+    NRM_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, m, h->g, keys, vals);
+    NRM_HIP(hipGetLastError());
+    size_t bytes = sort_bytes;
+    NRM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, (const uint32_t*)keys, keys2, (const uint32_t*)vals, vals2, int(m), 0,
+                                               end_bit(h->ncell), h->st));
+    hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, (const uint32_t*)vals2, m, qs);
+    NRM_HIP(hipGetLastError());
+    return S4P_NORMALS_OK;
+  }
+};
 
 int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, const float* qz, int64_t m, int32_t k, float radius,
                          float* out, bool device) {
@@ -593,31 +709,16 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
   if (m == 0) return S4P_NORMALS_OK;
   if (!qx || !qy || !qz || !out) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "estimate_at: null argument");
   NRM_HIP(hipSetDevice(h->device));
-  Scratch S;
   const uint64_t um = uint64_t(m);
-  const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  float* p[3];
-  const float* in[3] = {qx, qy, qz};
-  for (int a = 0; a < 3; ++a) {
-    NRM_HIP(S.alloc((void**)&p[a], um * sizeof(float)));
-    NRM_HIP(hipMemcpyAsync(p[a], in[a], um * sizeof(float), kind, h->st));
-  }
-  float4 *qp, *qs;
-  uint32_t *keys, *vals, *keys2, *vals2;
-  NRM_HIP(S.alloc((void**)&qp, um * sizeof(float4))); NRM_HIP(S.alloc((void**)&qs, um * sizeof(float4)));
-  NRM_HIP(S.alloc((void**)&keys, um * 4)); NRM_HIP(S.alloc((void**)&vals, um * 4));
-  NRM_HIP(S.alloc((void**)&keys2, um * 4)); NRM_HIP(S.alloc((void**)&vals2, um * 4));
-  const int nb = blocks_for(m);
-  hipLaunchKernelGGL(k_pack, dim3(nb), dim3(kBlock), 0, h->st, p[0], p[1], p[2], um, qp);
-  NRM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_cell_keys, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, um, h->g, keys, vals);
-  NRM_HIP(hipGetLastError());
-  if (int32_t rc = sort_pairs(h, S, keys, keys2, vals, vals2, um, h->ncell)) return rc;
-  hipLaunchKernelGGL(k_gather, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)qp, (const uint32_t*)vals2, um, qs);
-  NRM_HIP(hipGetLastError());
+  QueryStage Q;
+  if (int32_t rc = Q.plan(h, um)) return rc;
   float* dout = out;
-  if (!device) NRM_HIP(S.alloc((void**)&dout, 3 * um * sizeof(float)));
-  if (int32_t rc = run_knn(h, qs, um, k, radius, dout)) return rc;
+  if (int32_t rc = arena_layout(h, "estimate_at", [&](Arena& ar) {
+        Q.take(ar);
+        if (!device) dout = ar.take<float>(3 * um);
+      })) return rc;
+  if (int32_t rc = Q.run(h, qx, qy, qz, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) return rc;
+  if (int32_t rc = run_knn(h, Q.qs, um, k, radius, dout)) return rc;
   if (!device) NRM_HIP(hipMemcpyAsync(out, dout, 3 * um * sizeof(float), hipMemcpyDeviceToHost, h->st));
   NRM_HIP(hipStreamSynchronize(h->st));
   return S4P_NORMALS_OK;

@@ -28,6 +28,7 @@
 
 namespace s4p_nrm {
 
+static_assert(S4P_ORIENT_ERR_INTERNAL == kErrInternal, "arena_layout fails with the family's internal code");
 constexpr uint32_t kNoLabel = 0xFFFFFFFFu;      // label word of a point that is no vertex (a parent is at most 2^31 - 3)
 constexpr uint32_t kNoEdge = 0xFFFFFFFFu;       // w bits of a list entry that is no edge (w <= 1.0f = 0x3F800000)
 enum OrientCount { kCntVertices = 0, kCntComponents = 1, kCntFlipped = 2, kCntMerged = 3, kCntChanged = 4, kCntWords = 8 };
@@ -275,29 +276,31 @@ int32_t orient_impl(s4p_normals_ctx* h, int32_t k, float radius, int32_t mode, c
   const uint64_t un = uint64_t(h->n);
   const size_t nk = size_t(un) * size_t(k);
   const int nb = blocks_for(h->n);
-  Arena ar;
-  const size_t need = 3 * arena_round(nk * 4) + 3 * arena_round(un * 4) + arena_round(un * 8) + arena_round(kCntWords * 4) + arena_round(un) +
-                      (device ? 0 : arena_round(3 * un * sizeof(float)) + (flipped ? arena_round(un) : 0) +
-                                        (component ? arena_round(un * 4) : 0));
-  if (int32_t rc = arena_reserve(h, need, &ar)) return rc;
-  int32_t* idx = ar.take<int32_t>(nk);
-  float* d2 = ar.take<float>(nk);
-  uint32_t* wbits = ar.take<uint32_t>(nk);
-  uint32_t* cur = ar.take<uint32_t>(un);
-  uint32_t* nxt = ar.take<uint32_t>(un);
-  uint32_t* besthi = ar.take<uint32_t>(un);
-  unsigned long long* best = ar.take<unsigned long long>(un);
-  uint32_t* cnt = ar.take<uint32_t>(kCntWords);
-  uint8_t* live = ar.take<uint8_t>(un);
+  int32_t* idx = nullptr;
+  float* d2 = nullptr;
+  uint32_t *wbits = nullptr, *cur = nullptr, *nxt = nullptr, *besthi = nullptr, *cnt = nullptr;
+  unsigned long long* best = nullptr;
+  uint8_t* live = nullptr;
   float* dn = normals;
   uint8_t* dfl = flipped;
   int32_t* dco = component;
-  if (!device) {
-    dn = ar.take<float>(3 * un);
-    if (flipped) dfl = ar.take<uint8_t>(un);
-    if (component) dco = ar.take<int32_t>(un);
-    NRM_HIP(hipMemcpyAsync(dn, normals, 3 * un * sizeof(float), hipMemcpyHostToDevice, h->st));
-  }
+  if (int32_t rc = arena_layout(h, "orient_consistent", [&](Arena& ar) {
+        idx = ar.take<int32_t>(nk);
+        d2 = ar.take<float>(nk);
+        wbits = ar.take<uint32_t>(nk);
+        cur = ar.take<uint32_t>(un);
+        nxt = ar.take<uint32_t>(un);
+        besthi = ar.take<uint32_t>(un);
+        best = ar.take<unsigned long long>(un);
+        cnt = ar.take<uint32_t>(kCntWords);
+        live = ar.take<uint8_t>(un);
+        if (!device) {
+          dn = ar.take<float>(3 * un);
+          if (flipped) dfl = ar.take<uint8_t>(un);
+          if (component) dco = ar.take<int32_t>(un);
+        }
+      })) return rc;
+  if (!device) NRM_HIP(hipMemcpyAsync(dn, normals, 3 * un * sizeof(float), hipMemcpyHostToDevice, h->st));
   NRM_HIP(hipMemsetAsync(cnt, 0, kCntWords * 4, h->st));
   SearchArgs A{};
   A.qs = h->pts; A.m = un; A.k = k; A.self_mask = ~0u; A.idx = idx; A.d2 = d2; A.cnt = nullptr;
@@ -376,15 +379,14 @@ int32_t towards_impl(s4p_normals_ctx* h, float* normals, const float* viewpoint,
   if (!normals) return fail(h, S4P_NORMALS_ERR_BAD_ARG, "orient_towards: null normals");
   NRM_HIP(hipSetDevice(h->device));
   const uint64_t un = uint64_t(h->n);
-  Arena ar;
-  if (int32_t rc = arena_reserve(h, device ? 0 : arena_round(3 * un * sizeof(float)) + (flipped ? arena_round(un) : 0), &ar)) return rc;
   float* dn = normals;
   uint8_t* dfl = flipped;
-  if (!device) {
-    dn = ar.take<float>(3 * un);
-    if (flipped) dfl = ar.take<uint8_t>(un);
-    NRM_HIP(hipMemcpyAsync(dn, normals, 3 * un * sizeof(float), hipMemcpyHostToDevice, h->st));
-  }
+  if (int32_t rc = arena_layout(h, "orient_towards", [&](Arena& ar) {
+        if (device) return;
+        dn = ar.take<float>(3 * un);
+        if (flipped) dfl = ar.take<uint8_t>(un);
+      })) return rc;
+  if (!device) NRM_HIP(hipMemcpyAsync(dn, normals, 3 * un * sizeof(float), hipMemcpyHostToDevice, h->st));
   hipLaunchKernelGGL(k_orient_towards, dim3(blocks_for(h->n)), dim3(kBlock), 0, h->st, un, (const float4*)h->pos, viewpoint[0], viewpoint[1],
                      viewpoint[2], dn, dfl);
   NRM_HIP(hipGetLastError());

@@ -29,32 +29,6 @@ struct VoxGrid {
 
 __host__ __device__ inline double voxel_coord(float x, double v) { return floor(double(x) / v); }
 
-// per-block float minima and maxima (rows of 6) over the points whose three coordinates are finite; a block that saw
-// none leaves +inf / -inf
-__global__ __launch_bounds__(kBlock) void k_voxel_bounds(const float4* p, uint64_t n, float* rows) {
-  float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
-    const float4 q = p[i];
-    if (!(isfinite(q.x) && isfinite(q.y) && isfinite(q.z))) continue;
-    v[0] = fminf(v[0], q.x); v[1] = fminf(v[1], q.y); v[2] = fminf(v[2], q.z);
-    v[3] = fmaxf(v[3], q.x); v[4] = fmaxf(v[4], q.y); v[5] = fmaxf(v[5], q.z);
-  }
-  __shared__ float sh[kBlock];
-  for (int k = 0; k < 6; ++k) {
-    sh[threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = kBlock / 2; w > 0; w >>= 1) {
-      if (threadIdx.x < unsigned(w)) {
-        const float a = sh[threadIdx.x], b = sh[threadIdx.x + w];
-        sh[threadIdx.x] = k < 3 ? fminf(a, b) : fmaxf(a, b);
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) rows[blockIdx.x * 6 + k] = sh[0];
-    __syncthreads();
-  }
-}
-
 // packed voxel key of every point (offsets from the smallest index, 21 bits per axis); a dropped point gets all ones
 __global__ __launch_bounds__(kBlock) void k_voxel_keys(const float4* p, uint64_t n, VoxGrid g, uint64_t* keys, uint32_t* vals) {
   for (uint64_t i = blockIdx.x * (uint64_t)kBlock + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kBlock) {
@@ -252,60 +226,55 @@ int32_t voxel_impl(s4p_normals_ctx* h, const float* x, const float* y, const flo
   NRM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan2_bytes, (const uint32_t*)noval, noval, int(un + 1), h->st));
   const size_t tmp_bytes = std::max(sort_bytes, std::max(scan_bytes, scan2_bytes));
 
-  size_t need = arena_round(un * sizeof(float4)) + arena_round(size_t(nb) * 6 * sizeof(float)) + 2 * arena_round(un * 8) +
-                4 * arena_round(un * 4) + 3 * arena_round((un + 1) * 4) + arena_round(max_seg * C * sizeof(double)) + arena_round(max_seg * 4) +
-                arena_round(tmp_bytes);
-  if (!device)
-    need += 3 * arena_round(un * 4) + arena_round(un * na * 4) + arena_round(3 * un * 4) + arena_round(un * na * 4) + 2 * arena_round(un * 4);
-  Arena ar;
-  if (int32_t rc = arena_reserve(h, need, &ar)) return rc;
-
+  float *stage[3] = {nullptr, nullptr, nullptr}, *stage_attr = nullptr;      // host form: device copies of the caller's arrays
+  float *d_xyz = out_xyz, *d_attr = out_attr, *rows = nullptr;
+  int32_t *d_count = out_count, *d_vof = voxel_of;
+  float4* pos = nullptr;
+  uint64_t *keys = nullptr, *keys2 = nullptr;
+  uint32_t *vals = nullptr, *order = nullptr, *flags = nullptr, *rows1 = nullptr, *begin = nullptr, *nseg = nullptr, *segoff = nullptr, *segrow = nullptr;
+  double* partial = nullptr;
+  void* tmp = nullptr;
+  if (int32_t rc = arena_layout(h, "voxel_downsample", [&](Arena& ar) {
+        if (!device) {
+          for (int a = 0; a < 3; ++a) stage[a] = ar.take<float>(un);
+          if (nattr > 0) stage_attr = ar.take<float>(un * na);
+          d_xyz = ar.take<float>(3 * un);
+          if (nattr > 0) d_attr = ar.take<float>(un * na);
+          if (out_count) d_count = ar.take<int32_t>(un);
+          if (voxel_of) d_vof = ar.take<int32_t>(un);
+        }
+        pos = ar.take<float4>(un);
+        rows = ar.take<float>(size_t(nb) * 6);
+        keys = ar.take<uint64_t>(un);
+        keys2 = ar.take<uint64_t>(un);
+        vals = ar.take<uint32_t>(un);
+        order = ar.take<uint32_t>(un);
+        flags = ar.take<uint32_t>(un);
+        rows1 = ar.take<uint32_t>(un);
+        begin = ar.take<uint32_t>(un + 1);
+        nseg = ar.take<uint32_t>(un + 1);
+        segoff = ar.take<uint32_t>(un + 1);
+        partial = ar.take<double>(max_seg * C);
+        segrow = ar.take<uint32_t>(max_seg);
+        tmp = ar.take<char>(tmp_bytes);
+      })) return rc;
   const float* in[3] = {x, y, z};
   const float* dattr = attr;
   if (!device) {
     for (int a = 0; a < 3; ++a) {
-      float* p = ar.take<float>(un);
-      NRM_HIP(hipMemcpyAsync(p, in[a], un * sizeof(float), hipMemcpyHostToDevice, h->st));
-      in[a] = p;
+      NRM_HIP(hipMemcpyAsync(stage[a], in[a], un * sizeof(float), hipMemcpyHostToDevice, h->st));
+      in[a] = stage[a];
     }
     if (nattr > 0) {
-      float* p = ar.take<float>(un * na);
-      NRM_HIP(hipMemcpyAsync(p, attr, un * na * sizeof(float), hipMemcpyHostToDevice, h->st));
-      dattr = p;
+      NRM_HIP(hipMemcpyAsync(stage_attr, attr, un * na * sizeof(float), hipMemcpyHostToDevice, h->st));
+      dattr = stage_attr;
     }
   }
-  float* d_xyz = device ? out_xyz : ar.take<float>(3 * un);
-  float* d_attr = nattr == 0 ? nullptr : (device ? out_attr : ar.take<float>(un * na));
-  int32_t* d_count = out_count ? (device ? out_count : ar.take<int32_t>(un)) : nullptr;
-  int32_t* d_vof = voxel_of ? (device ? voxel_of : ar.take<int32_t>(un)) : nullptr;
-  float4* pos = ar.take<float4>(un);
-  float* rows = ar.take<float>(size_t(nb) * 6);
-  uint64_t* keys = ar.take<uint64_t>(un);
-  uint64_t* keys2 = ar.take<uint64_t>(un);
-  uint32_t* vals = ar.take<uint32_t>(un);
-  uint32_t* order = ar.take<uint32_t>(un);
-  uint32_t* flags = ar.take<uint32_t>(un);
-  uint32_t* rows1 = ar.take<uint32_t>(un);
-  uint32_t* begin = ar.take<uint32_t>(un + 1);
-  uint32_t* nseg = ar.take<uint32_t>(un + 1);
-  uint32_t* segoff = ar.take<uint32_t>(un + 1);
-  double* partial = ar.take<double>(max_seg * C);
-  uint32_t* segrow = ar.take<uint32_t>(max_seg);
-  void* tmp = ar.take<char>(tmp_bytes);
 
   hipLaunchKernelGGL(k_pack, dim3(nb), dim3(kBlock), 0, h->st, in[0], in[1], in[2], un, pos);
   NRM_HIP(hipGetLastError());
-  hipLaunchKernelGGL(k_voxel_bounds, dim3(nb), dim3(kBlock), 0, h->st, (const float4*)pos, un, rows);
-  NRM_HIP(hipGetLastError());
-  std::vector<float> hr(size_t(nb) * 6);
-  NRM_HIP(hipMemcpyAsync(hr.data(), rows, hr.size() * sizeof(float), hipMemcpyDeviceToHost, h->st));
-  NRM_HIP(hipStreamSynchronize(h->st));
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int b = 0; b < nb; ++b)
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = std::min(lo[a], hr[size_t(b) * 6 + a]);
-      hi[a] = std::max(hi[a], hr[size_t(b) * 6 + 3 + a]);
-    }
+  float lo[3], hi[3];
+  if (int32_t rc = cloud_bounds(h, true, pos, un, rows, lo, hi)) return rc;
   *m_out = 0;
   if (!(lo[0] <= hi[0])) {                                    // no finite point: nothing is kept
     if (voxel_of) {

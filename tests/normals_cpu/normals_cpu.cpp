@@ -133,4 +133,19 @@ void normals_cpu_normals(const float* px, const float* py, const float* pz, int6
   }
 }
 
+// out[3 m]: the normal of every query from the lists it is given (idx[m * k], -1 padded), taken in list order: what the
+// contract makes of exactly those neighbours, whoever found them
+void normals_cpu_normals_of_lists(const float* px, const float* py, const float* pz, const float* qx, const float* qy, const float* qz,
+                                  int64_t m, int32_t k, const int32_t* idx, float* out) {
+  const float* p[3] = {px, py, pz};
+  std::vector<Hit> nb;
+  for (int64_t i = 0; i < m; ++i) {
+    const float q[3] = {qx[i], qy[i], qz[i]};
+    nb.clear();
+    for (int t = 0; t < k; ++t)
+      if (idx[i * k + t] >= 0) nb.push_back(Hit(0.f, idx[i * k + t]));
+    normal_of(p, q, nb, out + 3 * i);
+  }
+}
+
 }  // extern "C"

@@ -19,6 +19,8 @@ def build_cpu(outdir):
     L.normals_cpu_knn.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp, vp, C.c_int32]
     L.normals_cpu_normals.restype = None
     L.normals_cpu_normals.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp, C.c_int32]
+    L.normals_cpu_normals_of_lists.restype = None
+    L.normals_cpu_normals_of_lists.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp]
     return CPU(L)
 
 
@@ -56,6 +58,18 @@ class CPU:
         out = np.empty((m, 3), np.float32)
         self.L.normals_cpu_normals(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, p[0].shape[0], q[0].ctypes.data,
                                    q[1].ctypes.data, q[2].ctypes.data, m, int(k), _r(radius), out.ctypes.data, int(threads))
+        return out
+
+    def normals_of_lists(self, X, idx, queries=None):
+        """float32 (m, 3): the contract's normal of every query from the neighbour lists idx (m, k), -1 padded, in list order."""
+        p = _cols(X)
+        q = p if queries is None else _cols(queries)
+        idx = np.ascontiguousarray(idx, np.int32)
+        m, k = idx.shape
+        assert q[0].shape[0] == m
+        out = np.empty((m, 3), np.float32)
+        self.L.normals_cpu_normals_of_lists(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, q[0].ctypes.data, q[1].ctypes.data,
+                                            q[2].ctypes.data, m, k, idx.ctypes.data, out.ctypes.data)
         return out
 
 
