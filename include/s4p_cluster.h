@@ -23,10 +23,12 @@
  *  - Host forms read and write host memory, _device forms memory of the context's device.  Two calls give the same bits;
  *    host and device forms give the same bits.  A call leaves the context's cloud and grid as they were.
  *
- * Refused with S4P_NORMALS_ERR_BAD_ARG: eps or radius that is not finite, is <= 0 or whose float square is not finite;
- * min_points < 1; a null label or count.  With S4P_NORMALS_ERR_STATE: a call before set_cloud.  S4P_CLUSTER_ERR_INTERNAL: a
- * bounded loop of the device path ran out, which the bound's derivation excludes; the call returns instead of spinning.
- * s4p_normals_last_error has the message.
+ * Limits.  Refused with S4P_NORMALS_ERR_BAD_ARG: eps or radius that is not finite, is <= 0 or whose float square is not
+ * finite and normal (fl(eps*eps) >= FLT_MIN = 2^-126, so eps above about 1.1e-19: a subnormal or zero square cannot bound
+ * float distances); min_points < 1; a null label or count.  The cloud's scale is limited by set_cloud (s4p_normals.h).
+ * With S4P_NORMALS_ERR_STATE: a call before set_cloud.  S4P_CLUSTER_ERR_INTERNAL: a bounded loop of the device path ran
+ * out, which the bound's derivation excludes; the call returns instead of spinning.  s4p_normals_last_error has the
+ * message.
  */
 #ifndef S4P_CLUSTER_H_
 #define S4P_CLUSTER_H_

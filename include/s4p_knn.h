@@ -28,7 +28,8 @@
  * Limits (S4P_NORMALS_ERR_BAD_ARG outside them; S4P_NORMALS_ERR_STATE before set_cloud): 1 <= k <= 32; radius finite (<= 0:
  * unbounded) for the lists; 0 <= m <= 2^31 - 2; std_ratio finite and >= 0; for radius removal radius finite and > 0 and
  * 1 <= min_neighbours <= 32; non-null idx, d2 and keep (and queries when m > 0).  Error codes and s4p_normals_last_error
- * as in s4p_normals.h.
+ * as in s4p_normals.h.  The lists are exactly the k smallest (d2, index) for every cloud that set_cloud accepts: it refuses
+ * a cloud whose planned cell edge is below 2^-43, where neighbours' d2 becomes subnormal (s4p_normals.h, Limits).
  */
 #ifndef S4P_KNN_H_
 #define S4P_KNN_H_

@@ -15,7 +15,12 @@
  *    give the same bits; host and device forms give the same bits.  A non-finite query gets (0, 0, 0).
  *
  * Limits (S4P_NORMALS_ERR_BAD_ARG outside them): 1 <= n <= 2^31 - 2 finite points; 3 <= k <= 32; radius finite
- * (<= 0: unbounded); 0 <= m <= 2^31 - 2; non-null pointers (queries and out may be null when m == 0).
+ * (<= 0: unbounded); 0 <= m <= 2^31 - 2; non-null pointers (queries and out may be null when m == 0).  The cloud's scale:
+ * set_cloud refuses a cloud whose planned cell edge (about the distance to the 16th neighbour, at least 2^-20 of the
+ * largest extent; s4p_normals_grid reports it) is below 2^-43, about 1.1e-13.  Under it squared distances between
+ * neighbours fall into float's subnormal range, where the contract's float d2 cannot order them: rescale such a cloud.  A
+ * cloud of identical points (extent 0) is accepted.  Large scales have no limit: where d2 overflows, the lists hold the
+ * +inf the float expression gives, ordered by index.
  */
 #ifndef S4P_NORMALS_H_
 #define S4P_NORMALS_H_

@@ -218,8 +218,9 @@ constexpr double kClusterEdgeMargin = 1.0 + 0x1p-16;
 int32_t cluster_check(s4p_normals_ctx* h, const char* what, const char* name, float eps) {
   if (!h->has_cloud) return fail(h, S4P_NORMALS_ERR_STATE, std::string(what) + ": set_cloud first");
   const float r2 = eps * eps;
-  if (!std::isfinite(eps) || !(eps > 0.f) || !std::isfinite(r2))
-    return fail(h, S4P_NORMALS_ERR_BAD_ARG, std::string(what) + ": " + name + " must be finite and > 0, with a finite square in float");
+  // a subnormal or zero r2 has no relative precision left: the cell margin of the grid no longer covers d2 <= r2
+  if (!std::isfinite(eps) || !(eps > 0.f) || !std::isfinite(r2) || !(r2 >= FLT_MIN))
+    return fail(h, S4P_NORMALS_ERR_BAD_ARG, std::string(what) + ": " + name + " must be finite and > 0, with a finite and normal square in float (>= 2^-126)");
   return S4P_NORMALS_OK;
 }
 

@@ -24,6 +24,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -43,6 +44,11 @@ constexpr int kSamples = 64;                // seeded sample points of the spaci
 constexpr int kBinLo = 252;                 // spacing histogram: 4 bins per octave of d2 / L^2 in [2^-64, 2^-10)
 constexpr int kBins = 216;                  //   (bin = (float bits >> 21) - kBinLo; below 2^-64, 0 included, -> bin 0)
 constexpr int kJacobiSweeps = 64;
+// The smallest cell edge set_cloud accepts.  The walk's (1 - 1e-5) comparison presumes a relative error of a float d2; in
+// the subnormal range the error is absolute, up to 1.5 * 2^-149, and the comparison still holds for a skipped point whose
+// true d2 exceeds 2^-131.8.  A skipped point lies farther from the query than 1e-6 h less the rounding of its cell
+// location, at least 5e-7 h, so h >= 2^-44.9 suffices: 2^-43 leaves a factor of 4 in h (DESIGN.md section "Grid regimes").
+constexpr double kMinCellEdge = 0x1p-43;
 
 struct GridDev {
   double ox, oy, oz, h, inv_h;
@@ -219,8 +225,9 @@ __device__ inline float key_d2(uint64_t key) { return key == ~0ull ? INFINITY : 
 // Rings of cells around the query's (clamped) cell are visited in order R = 0, 1, ...; before ring R the search stops
 // when every cell outside the (2R - 1)^3 block already visited is farther than the bound, and inside a ring a cell is
 // skipped when its box is.  Box distances are in double, widened by 1e-6 h for the rounding of the cell location and
-// compared with a (1 - 1e-5) factor that exceeds the rounding of any float d2 (as the ICP library's nearest()): a skipped
-// point can neither enter the list nor tie with its last entry.
+// compared with a (1 - 1e-5) factor that exceeds the rounding of any normal float d2 (as the ICP library's nearest()): a
+// skipped point can neither enter the list nor tie with its last entry.  A skipped point is farther than 1e-6 h from the
+// query, and set_cloud's kMinCellEdge keeps the d2 of such a point a normal float.
 // The walk is one text, S4P_KNN_WALK, expanded twice.  In k_knn_normals it stands in the kernel, because a walk that the
 // kernel calls is compiled on its own first, with the list in memory behind a reference, and the kernel then carries the
 // list twice (156 / 252 VGPRs against 131 / 193, estimate at k = 16 one percent slower).  knn_walk<K>
@@ -608,6 +615,9 @@ int32_t set_cloud_impl(s4p_normals_ctx* h, const float* x, const float* y, const
   for (int a = 0; a < 3; ++a) ext = std::max(ext, double(hi[a]) - double(lo[a]));
   double hh = ext > 0.0 ? std::max(spacing, ext * 0x1p-20) : 1.0;
   if (int32_t rc = fit_grid(h, "set_cloud", lo, hi, hh, un, &h->g, &h->ncell)) return rc;
+  if (h->g.h < kMinCellEdge)
+    return fail(h, S4P_NORMALS_ERR_BAD_ARG, "set_cloud: the cloud's spacing is too small for float distances (the planned cell edge is below "
+                                            "2^-43, where squared distances become subnormal): rescale the cloud");
   h->spacing = spacing;
   for (int a = 0; a < 3; ++a) { h->lo[a] = lo[a]; h->hi[a] = hi[a]; }
   uint32_t *keys, *vals, *keys2, *vals2;

@@ -160,5 +160,19 @@ def two_clusters(n_each=150, seed=4):
     return (np.concatenate(out)[perm].astype(np.float32), np.concatenate(nrm)[perm].astype(np.float32), np.concatenate(ctr)[perm])
 
 
+def same(ctx, X, N, idx, k, radius, viewpoint, what):
+    """One orient call equals the restatement: mask, components, counts, and the output's bits.  Returns the info."""
+    out, info = ctx.orient(N, k, radius, viewpoint, return_info=True)
+    flip, comp, ncomp = reference(X, N, idx, viewpoint)
+    assert out.dtype == np.float32 and info["flipped"].dtype == bool and info["component"].dtype == np.int32
+    bad = np.flatnonzero(info["flipped"] != flip)
+    assert len(bad) == 0, (what, len(bad), bad[:8])
+    assert np.array_equal(info["component"], comp), (what, np.flatnonzero(info["component"] != comp)[:8])
+    assert np.array_equal(bits(out), bits(apply(N, flip))), what
+    assert (info["vertices"], info["components"], info["flipped_count"]) == (int(usable(N).sum()), ncomp, int(flip.sum())), (what, info)
+    assert 0 <= info["rounds"] <= 32 and 0 <= info["max_jumps"] <= 32 and (info["rounds"] == 0) == (info["max_jumps"] == 0)
+    return info
+
+
 numpy_lists = KH.numpy_lists
 cpu_lists = KH.cpu_lists

@@ -33,20 +33,6 @@ def cpu(tmp_path_factory):
     return NH.build_cpu(tmp_path_factory.mktemp("orient_cpu"))
 
 
-def _same(ctx, X, N, idx, k, radius, viewpoint, what):
-    """One orient call equals the restatement: mask, components, counts, and the output's bits.  Returns the info."""
-    out, info = ctx.orient(N, k, radius, viewpoint, return_info=True)
-    flip, comp, ncomp = OH.reference(X, N, idx, viewpoint)
-    assert out.dtype == np.float32 and info["flipped"].dtype == bool and info["component"].dtype == np.int32
-    bad = np.flatnonzero(info["flipped"] != flip)
-    assert len(bad) == 0, (what, len(bad), bad[:8])
-    assert np.array_equal(info["component"], comp), (what, np.flatnonzero(info["component"] != comp)[:8])
-    assert np.array_equal(OH.bits(out), OH.bits(OH.apply(N, flip))), what
-    assert (info["vertices"], info["components"], info["flipped_count"]) == (int(OH.usable(N).sum()), ncomp, int(flip.sum())), (what, info)
-    assert 0 <= info["rounds"] <= 32 and 0 <= info["max_jumps"] <= 32 and (info["rounds"] == 0) == (info["max_jumps"] == 0)
-    return info
-
-
 @pytest.mark.parametrize("n", [1, 2, 3, 64, 65, 257])
 @pytest.mark.parametrize("dup", [False, True])
 def test_tiny_clouds_equal_the_restatement(nrm, n, dup):
@@ -60,7 +46,7 @@ def test_tiny_clouds_equal_the_restatement(nrm, n, dup):
         for r in (None, KH.tiny_radius(n)):
             idx, _, cnt = OH.numpy_lists(X, k, r, exclude_self=True)
             for vp in (None, VIEW):
-                info = _same(ctx, X, N, idx, k, r, vp, (n, dup, k, r, vp))
+                info = OH.same(ctx, X, N, idx, k, r, vp, (n, dup, k, r, vp))
                 many += int(k == 1 and info["components"] > 4)
                 alone += int(r is not None and (cnt == 0).any())
     assert n < 64 or (many >= 2 and alone >= 2)
@@ -73,7 +59,7 @@ def test_lattice_of_ties_equals_the_restatement_with_one_sign(nrm, cpu, m):
     ctx = nrm.Normals(0)
     ctx.set_cloud(X)
     idx = OH.cpu_lists(cpu, X, 8, exclude_self=True)[0]
-    info = _same(ctx, X, N, idx, 8, None, None, ("lattice", m))
+    info = OH.same(ctx, X, N, idx, 8, None, None, ("lattice", m))
     out = ctx.orient(N, 8)
     assert info["components"] == 1 and len(np.unique(out[:, 2])) == 1 and 0.3 < info["flipped_count"] / len(X) < 0.7
     print("lattice %d: rounds %d, max jumps %d" % (m, info["rounds"], info["max_jumps"]))
@@ -87,7 +73,7 @@ def test_two_clusters_are_anchored_separately(nrm):
     idx = OH.numpy_lists(X, 8, exclude_self=True)[0]
     radial = X.astype(np.float64) - Cn
     for vp in (None, (0.0, 0.0, 0.0)):
-        info = _same(ctx, X, N, idx, 8, None, vp, ("clusters", vp))
+        info = OH.same(ctx, X, N, idx, 8, None, vp, ("clusters", vp))
         assert info["components"] == 2
         out = ctx.orient(N, 8, viewpoint=vp).astype(np.float64)
         assert ((out * radial).sum(1) > 0).all()                 # a viewpoint between them makes both face it: both outward
@@ -111,7 +97,7 @@ def test_real_clouds_equal_the_restatement_bit_for_bit(nrm, cpu, name):
     N = ctx.estimate(16)
     idx16 = OH.cpu_lists(cpu, X, 16, exclude_self=True)[0]
     for k, vp in ((8, None), (16, None), (8, VIEW)):
-        info = _same(ctx, X, N, np.ascontiguousarray(idx16[:, :k]), k, None, vp, (name, k, vp))
+        info = OH.same(ctx, X, N, np.ascontiguousarray(idx16[:, :k]), k, None, vp, (name, k, vp))
         print("%s k %d: vertices %d components %d flipped %d rounds %d max jumps %d"
               % (name, k, info["vertices"], info["components"], info["flipped_count"], info["rounds"], info["max_jumps"]))
         assert info["rounds"] >= 2
@@ -200,7 +186,7 @@ def test_non_finite_normals_count_as_zero_normals(nrm):
     ctx.set_cloud(X)
     for k in (2, 8):
         idx = OH.numpy_lists(X, k, exclude_self=True)[0]
-        info = _same(ctx, X, N, idx, k, None, None, ("nonfinite", k))
+        info = OH.same(ctx, X, N, idx, k, None, None, ("nonfinite", k))
         assert (info["component"][[5, 40, 41, 200]] == -1).all() and not info["flipped"][[5, 40, 41, 200]].any()
         zi = ctx.orient(Z, k, return_info=True)[1]
         assert np.array_equal(zi["flipped"], info["flipped"]) and np.array_equal(zi["component"], info["component"])

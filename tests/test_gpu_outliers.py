@@ -13,7 +13,6 @@ from tests import normals_helpers as NH
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-EPS = KH.EPS
 
 
 @pytest.fixture(scope="module")
@@ -62,39 +61,6 @@ def _reference_m(X, idx33, k):
     return KH.mean_dist(d2, cnt)
 
 
-def _check_against_reference(n, k, ratio, md, stats, keep, m_ref, what):
-    """The bounds, with eps = 2^-52 (twice the unit roundoff, so every "one rounding" below is covered with room):
-    - m_j: k sqrt roundings, k - 1 additions and one division of non-negative terms: relative (k + 2) eps.
-    - mu, t: any summation order of n non-negative terms is within relative (n - 1) eps / 2 of the exact sum; with the
-      division, relative n eps.  t = mu + ratio sigma inherits it (sigma's bound below is no larger for n >= 8).
-    - sigma: S = sum (m_j - mu')^2 with the device's mu' = mu (1 + theta), |theta| <= n eps.  Since sum (m_j - mu) = 0,
-      sum (m_j - mu')^2 = S + n (mu - mu')^2: the error of mu enters at second order, n (n eps mu)^2.  Each term carries
-      the rounding of the difference (twice, squared) and of the square, 3 eps / 2, and the sum of n non-negative terms
-      (n - 1) eps / 2; the division by n - 1 and the square root add 3 eps / 2 and the root halves what came before.  In
-      all |sigma' - sigma| / sigma <= (n / 4 + 4) eps + n (n eps mu)^2 / (2 S), and the same 4 eps again for the
-      reference's own (m - mu)^2 terms: (n / 4 + 8) eps + (n eps mu / sigma)^2 / 2 is asserted."""
-    mu, sigma, t = KH.sor_reference(m_ref, ratio)
-    rel_m = np.max(np.abs(md - m_ref) / np.where(m_ref > 0, m_ref, 1.0))
-    gap = np.min(np.abs(m_ref - t)) / t if t > 0 else np.inf
-    keep_ref = m_ref <= t
-    print("%s: n %d k %d ratio %g: mu %.17g (ref %.17g) sigma %.17g (ref %.17g) t %.17g (ref %.17g) max rel m %.3g "
-          "(equal %s) gap %.3g kept %d (ref %d)" % (what, n, k, ratio, stats["mean"], mu, stats["stddev"], sigma, stats["threshold"], t,
-                                                     rel_m, np.array_equal(md, m_ref), gap, stats["kept"], keep_ref.sum()))
-    assert stats["n"] == n
-    assert rel_m <= (k + 2) * EPS
-    assert abs(stats["mean"] - mu) <= n * EPS * mu
-    assert abs(stats["threshold"] - t) <= n * EPS * t
-    if sigma > 0:
-        assert abs(stats["stddev"] - sigma) <= ((n / 4 + 8) * EPS + 0.5 * (n * EPS * mu / sigma) ** 2) * sigma
-    else:
-        assert stats["stddev"] == 0.0
-    # the mask is the device's own comparison, exactly, and the reference's
-    assert np.array_equal(keep, md <= stats["threshold"]) and stats["kept"] == int(keep.sum())
-    assert gap > 1e-9                                    # no reference m_j so near the reference t that rounding could flip it
-    assert np.array_equal(keep, keep_ref)
-    return keep_ref
-
-
 @pytest.mark.parametrize("name,k,ratio", [("bumpy", 1, 2.0), ("bumpy", 8, 2.0), ("bumpy", 16, 2.0), ("bumpy", 32, 2.0),
                                           ("lidar", 16, 2.0), ("lidar", 8, 1.0)])
 def test_statistical_removal_equals_the_reference(knn, planted, contexts, reference_lists, name, k, ratio):
@@ -102,7 +68,7 @@ def test_statistical_removal_equals_the_reference(knn, planted, contexts, refere
     keep, stats, md = contexts[name].statistical_outliers(k, ratio)
     assert keep.dtype == bool and md.dtype == np.float64 and keep.shape == (len(X),) and md.shape == (len(X),)
     m_ref = _reference_m(X, reference_lists[name], k)
-    _check_against_reference(len(X), k, ratio, md, stats, keep, m_ref, name)
+    KH.check_sor(len(X), k, ratio, md, stats, keep, m_ref, name)
     if name == "bumpy":                                  # the filter does its job: the surface stays, the strays go
         assert keep[~is_planted].all() and (~keep[is_planted]).sum() >= 51, (~keep[is_planted]).sum()
 
@@ -131,7 +97,7 @@ def test_statistical_removal_edge_cases(knn, cpu):
         keep, st, md = ctx.statistical_outliers(32, ratio)
         _, d2, cnt = KH.numpy_lists(X, 32, exclude_self=True)
         assert (cnt == 19).all()
-        _check_against_reference(20, 32, ratio, md, st, keep, KH.mean_dist(d2, cnt), "20 points")
+        KH.check_sor(20, 32, ratio, md, st, keep, KH.mean_dist(d2, cnt), "20 points")
     ctx.close()
 
 

@@ -61,7 +61,8 @@ def test_the_normals_header_and_its_symbol_list_are_unchanged(knn):
     from super4pcs_amd import normals
     assert _declared("s4p_normals.h", "s4p_normals_") == sorted(normals.SYMBOLS) and len(normals.SYMBOLS) == 10
     digest = hashlib.sha256(open(os.path.join(ROOT, "include", "s4p_normals.h"), "rb").read()).hexdigest()
-    assert digest == "ff4eeb9270a3f6594d76ff288f31e3d50a918d6288bf758862f4e1ccbb75db80", digest
+    # the header as of the scale limit in its Limits paragraph: a comment grew, no declaration changed
+    assert digest == "f5f72bed94da6af3e2c3cfa3c129249e091cc62eff74a555a0d401bb0a9d2f22", digest
     assert not [s for s in knn.SYMBOLS if s.startswith("s4p_normals_")]
 
 
