@@ -11,6 +11,7 @@
 //             [--remove-outliers k] [--remove-outliers-std ratio]
 //             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K] [--icp-information file]
 //             [--cluster-eps e] [--cluster-min-points m] [--cluster-keep K]
+//             [--remove-plane d] [--remove-plane-trials T] [--remove-plane-count K]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -40,6 +41,10 @@
 // easiest to choose, and before --estimate-normals, the matcher and ICP: a dense fragment away from the surface goes, which
 // --remove-outliers keeps; -r then writes the filtered, registered second input.  An input with faces, or one left with no
 // cluster, is refused (exit status 254).
+// --remove-plane d removes the --remove-plane-count K (default 1) dominant planes of both inputs (algorithms/plane.h: RANSAC with
+// --remove-plane-trials T candidates, default 1024, inliers within d, one least-squares refit) after --voxel-size and before
+// --cluster-eps, which would otherwise join a scanned scene through its ground; -r then writes the filtered, registered
+// second input.  An input with faces, or one left with fewer than 3 points, is refused (exit status 254).
 // --icp-scales v1,v2,... (needs --icp) refines coarse to fine (algorithms/icp_multiscale.h): one level per voxel size, both
 // inputs downsampled at it (the second in its own frame; 0, allowed last, takes them as they are), the level's distance
 // max(--icp-dist, 3 v) and --icp iterations per level; every --icp-metric and --icp-loss applies to every level.
@@ -66,6 +71,7 @@
 #include "super4pcs/algorithms/icp_multiscale.h"
 #include "super4pcs/algorithms/normals.h"
 #include "super4pcs/algorithms/outliers.h"
+#include "super4pcs/algorithms/plane.h"
 #include "super4pcs/algorithms/super4pcs.h"
 #include "super4pcs/algorithms/voxelgrid.h"
 #include "super4pcs/io/io.h"
@@ -89,11 +95,12 @@ struct Mesh {                                    // everything IOManager returns
     if (faces.empty()) Utils::CleanInvalidNormals(points, normals);   // point sets only: faces index the vertex list
     return true;
   }
-  // statistical outlier removal of the points; per-vertex normal and texture lists follow the vertices
-  size_t remove_outliers(const OutlierRemovalOptions& oopt) {
+  // a filter that erases points in place and reports which it kept: per-vertex normal and texture lists follow the vertices
+  template <class Erase>
+  size_t filtered(Erase erase) {
     const size_t before = points.size();
     std::vector<uint8_t> kept;
-    const size_t removed = RemoveOutliers(points, oopt, &kept);
+    const size_t removed = erase(points, &kept);
     compact(normals, kept, before);
     compact(tex, kept, before);
     return removed;
@@ -107,14 +114,17 @@ struct Mesh {                                    // everything IOManager returns
       if (kept[i]) list[w++] = list[i];
     list.resize(w);
   }
-  // the largest density clusters of the points; per-vertex normal and texture lists follow the vertices
+  // statistical outlier removal of the points
+  size_t remove_outliers(const OutlierRemovalOptions& oopt) {
+    return filtered([&](std::vector<Point3D>& pts, std::vector<uint8_t>* kept) { return RemoveOutliers(pts, oopt, kept); });
+  }
+  // the largest density clusters of the points
   size_t keep_clusters(const ClusterOptions& copt) {
-    const size_t before = points.size();
-    std::vector<uint8_t> kept;
-    const size_t removed = KeepLargestClusters(points, copt, &kept);
-    compact(normals, kept, before);
-    compact(tex, kept, before);
-    return removed;
+    return filtered([&](std::vector<Point3D>& pts, std::vector<uint8_t>* kept) { return KeepLargestClusters(pts, copt, kept); });
+  }
+  // the points without their dominant planes
+  size_t remove_planes(const PlaneOptions& popt) {
+    return filtered([&](std::vector<Point3D>& pts, std::vector<uint8_t>* kept) { return RemovePlanes(pts, popt, kept); });
   }
   // voxel-grid downsampling of the points; the per-vertex normal list is rebuilt from the averaged normals when they were
   // carried (every point had one), the texture list does not survive
@@ -184,6 +194,10 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
     log.Log<Utils::ErrorReport>("--voxel-size: an input has faces; faces index the vertex list, so only point sets can be downsampled");
     return -2;
   }
+  if (opt.remove_plane >= 0 && (!P.faces.empty() || !Q.faces.empty())) {
+    log.Log<Utils::ErrorReport>("--remove-plane: an input has faces; faces index the vertex list, so only point sets can be filtered");
+    return -2;
+  }
   if (opt.cluster_eps > 0 && (!P.faces.empty() || !Q.faces.empty())) {
     log.Log<Utils::ErrorReport>("--cluster-eps: an input has faces; faces index the vertex list, so only point sets can be filtered");
     return -2;
@@ -202,6 +216,18 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       const size_t np = P.points.size(), nq = Q.points.size();
       const size_t mp = P.voxel_downsample(vopt), mq = Q.voxel_downsample(vopt);
       log.Log<Utils::Verbose>("Voxel grid: edge ", opt.voxel_size, ": ", mp, " of ", np, " points of input1, ", mq, " of ", nq, " of input2");
+    }
+    if (opt.remove_plane >= 0) {
+      PlaneOptions popt;
+      popt.distance = opt.remove_plane;
+      popt.trials = opt.remove_plane_trials;
+      popt.count = opt.remove_plane_count;
+      const size_t rp = P.remove_planes(popt), rq = Q.remove_planes(popt);
+      log.Log<Utils::Verbose>("Removed planes: distance ", opt.remove_plane, ", trials ", opt.remove_plane_trials, ", count ", opt.remove_plane_count,
+                              ": removed ", rp, " of input1, ", rq, " of input2");
+      if (P.points.size() < 3 || Q.points.size() < 3)
+        throw std::runtime_error(std::string("--remove-plane: fewer than 3 points are left of ") + (P.points.size() < 3 ? "input1" : "input2") +
+                                 " at this distance; nothing is left to register");
     }
     if (opt.cluster_eps > 0) {
       ClusterOptions copt;

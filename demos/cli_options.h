@@ -60,6 +60,10 @@ struct Options {
   int cluster_min_points = 10;                               // --cluster-min-points m  (needs eps)
   int cluster_keep = 1;                                      // --cluster-keep K  (needs eps)
   bool cluster_min_points_set = false, cluster_keep_set = false;
+  double remove_plane = -1;                                  // --remove-plane distance  remove the dominant planes of both inputs (off)
+  int remove_plane_trials = 1024;                            // --remove-plane-trials T  (needs distance; 1 .. 2^20)
+  int remove_plane_count = 1;                                // --remove-plane-count K  (needs distance)
+  bool remove_plane_trials_set = false, remove_plane_count_set = false;
   bool bad_value = false;                                   // a flag's value does not parse
 };
 
@@ -238,6 +242,24 @@ inline const Flag* flag_table(size_t* n) {
          o.cluster_keep_set = true;
          if (end == v[0] || *end != '\0' || k < 1 || k > 2147483647L) o.bad_value = true; else o.cluster_keep = int(k);
        }},
+      {"--remove-plane", 1, [](Options& o, char** v) {
+         // finite, >= 0, and a finite float
+         char* end = nullptr;
+         const double d = std::strtod(v[0], &end);
+         if (end == v[0] || *end != '\0' || !(d >= 0) || !(d < 3.0e38)) o.bad_value = true; else o.remove_plane = d;
+       }},
+      {"--remove-plane-trials", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long t = std::strtol(v[0], &end, 10);
+         o.remove_plane_trials_set = true;
+         if (end == v[0] || *end != '\0' || t < 1 || t > 1048576L) o.bad_value = true; else o.remove_plane_trials = int(t);
+       }},
+      {"--remove-plane-count", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long k = std::strtol(v[0], &end, 10);
+         o.remove_plane_count_set = true;
+         if (end == v[0] || *end != '\0' || k < 1 || k > 2147483647L) o.bad_value = true; else o.remove_plane_count = int(k);
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -265,6 +287,7 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.orient_k > 0 && o.normals_k == 0) return Parse::Bad;           // --orient-normals needs --estimate-normals
   if (o.orient_viewpoint_set && o.orient_k == 0) return Parse::Bad;    // --orient-viewpoint needs --orient-normals
   if ((o.cluster_min_points_set || o.cluster_keep_set) && !(o.cluster_eps > 0)) return Parse::Bad;    // both need --cluster-eps
+  if ((o.remove_plane_trials_set || o.remove_plane_count_set) && !(o.remove_plane >= 0)) return Parse::Bad;    // both need --remove-plane
   if (o.icp_trim_set && o.icp_loss != 1) return Parse::Bad;            // --icp-trim needs --icp-loss trimmed
   if (o.icp_loss_scale_set && o.icp_loss < 2) return Parse::Bad;       // --icp-loss-scale needs huber or tukey
   if (o.icp_gicp && o.icp_loss != 0) return Parse::Bad;                // the generalized metric takes no loss
@@ -333,6 +356,11 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t     at least m points within e, itself included, is a core point, core points within e of each other share a\n");
   std::fprintf(stderr, "\t     cluster, and the K largest clusters stay: a dense fragment away from the surface goes, which\n");
   std::fprintf(stderr, "\t     --remove-outliers keeps; point sets only, -r writes the filtered input2)\n");
+  std::fprintf(stderr, "\t[ --remove-plane d (>= 0; off) ] [ --remove-plane-trials T (needs d; 1024, 1..1048576) ] [ --remove-plane-count K (needs d; 1, >= 1) ]\n");
+  std::fprintf(stderr, "\t    (RANSAC plane removal of both inputs on the device, after --voxel-size and before --cluster-eps: of T sampled\n");
+  std::fprintf(stderr, "\t     planes the one with the most points within d wins, is refitted once to them by least squares and goes with\n");
+  std::fprintf(stderr, "\t     them, K times: the ground of a scan, through which --cluster-eps would join the scene; point sets only, -r\n");
+  std::fprintf(stderr, "\t     writes the filtered input2)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

@@ -10,6 +10,7 @@
 //   voxel-grid downsampling (include/s4p_voxel.h): s4p_voxel.inc, of a cloud passed per call, on the context's stream.
 //   normal orientation (include/s4p_normals_orient.h): s4p_orient.inc, a minimum spanning forest over the lists' graph.
 //   density clustering (include/s4p_cluster.h): s4p_cluster.inc, a fixed-radius walk on a grid of edge eps and a union-find.
+//   plane segmentation (include/s4p_plane.h): s4p_plane.inc, RANSAC as a dense candidates x points count, no grid.
 //   estimate    queries in cell order (the cloud itself, or QueryStage: k_cell_keys + sort + k_gather of the caller's
 //               queries) -> k_knn_normals<K>: one lane per query, knn_walk (ring search with conservative box pruning, the
 //               k best (d2, index) sorted in registers), covariance in double, 3x3 Jacobi, the normal scattered to the
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void k_knn_normals(KnnArgs A) {
   }
 }
 
-uint64_t splitmix64(uint64_t& s) {
+__host__ __device__ inline uint64_t splitmix64(uint64_t& s) {
   uint64_t z = (s += 0x9E3779B97F4A7C15ull);
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -740,6 +741,7 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
 #include "s4p_voxel.inc"                 // include/s4p_voxel.h: voxel-grid downsampling on the context's stream and arena
 #include "s4p_orient.inc"                // include/s4p_normals_orient.h: consistent normal orientation on the lists of s4p_knn.inc
 #include "s4p_cluster.inc"               // include/s4p_cluster.h: density clustering on a grid of its own, on the same stream and arena
+#include "s4p_plane.inc"                 // include/s4p_plane.h: RANSAC plane segmentation on the cloud in the caller's order, same stream and arena
 
 extern "C" {
 
