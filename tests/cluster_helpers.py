@@ -3,16 +3,13 @@
 contract's order, the border rule by lexsort on (d2 bits, index), labels ranked by the smallest core index), and the clouds
 the host and the GPU tests share.  Only numpy is used: no scipy, no sklearn."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cluster_cpu", "cluster_cpu.cpp")
 NOISE, BORDER, CORE = 0, 1, 2
 STAT_KEYS = ("core", "border", "noise", "clusters")
 
@@ -20,9 +17,7 @@ bits = NH.bits
 
 
 def build_cpu(outdir):
-    so = os.path.join(str(outdir), "libcluster_cpu.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("cluster_cpu/cluster_cpu.cpp", outdir, "libcluster_cpu")
     vp = C.c_void_p
     L.cluster_cpu_dbscan.restype = None
     L.cluster_cpu_dbscan.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_int32, vp, vp, vp, C.c_int32]
@@ -37,18 +32,16 @@ class CPU:
 
     def dbscan(self, X, eps, min_points, threads=16):
         """(label int32[n], kind uint8[n], stats dict) of the contract."""
-        p = NH._cols(X)
+        p = S.cols(X)
         n = p[0].shape[0]
         label = np.empty(n, np.int32); kind = np.empty(n, np.uint8); st = np.zeros(4, np.int64)
-        self.L.cluster_cpu_dbscan(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, n, float(eps), int(min_points), label.ctypes.data,
-                                  kind.ctypes.data, st.ctypes.data, int(threads))
+        self.L.cluster_cpu_dbscan(*S.xyzn(p), float(eps), int(min_points), label.ctypes.data, kind.ctypes.data, st.ctypes.data, int(threads))
         return label, kind, dict(zip(STAT_KEYS, (int(v) for v in st)))
 
     def density(self, X, radius, threads=16):
-        p = NH._cols(X)
-        n = p[0].shape[0]
-        count = np.empty(n, np.int32)
-        self.L.cluster_cpu_density(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, n, float(radius), count.ctypes.data, int(threads))
+        p = S.cols(X)
+        count = np.empty(p[0].shape[0], np.int32)
+        self.L.cluster_cpu_density(*S.xyzn(p), float(radius), count.ctypes.data, int(threads))
         return count
 
 

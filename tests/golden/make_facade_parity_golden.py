@@ -32,8 +32,7 @@ F = np.float32
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "facade_parity.json")
 NORMALS_LIBS = ("super4pcs_normals",)
 PROGRAMS = {"icp_facade_app": apps.ICP_FACADE_LIBS, "multiway_app": apps.ICP_FACADE_LIBS,
-            "icp_multiscale_app": ("super4pcs_icp", "super4pcs_normals", "dl"), "normals_app": NORMALS_LIBS,
-            "orient_app": NORMALS_LIBS, "knn_app": NORMALS_LIBS, "voxel_app": NORMALS_LIBS}
+            "icp_multiscale_app": ("super4pcs_icp", "super4pcs_normals", "dl"), "normals_facade_app": NORMALS_LIBS}
 COS1, SIN1 = 0.9998476951563913, 0.01745240643728351          # of one degree
 
 
@@ -57,10 +56,10 @@ CASES += [_icp("icp/trimmed", "P.xyz", "Q.xyz", "--identity", "--loss", "trimmed
           ("multiway/plane", "multiway_app", ("poses.txt", "0.04", "0.3", "scan0.xyz", "scan1.xyz", "scan2.xyz")),
           ("multiway/gicp", "multiway_app", ("poses.txt", "0.04", "0.3", "scan0.xyz", "scan1.xyz", "scan2.xyz", "--metric", "gicp")),
           ("multiscale/point", "icp_multiscale_app", ("P.xyz", "Q_own_frame.xyz", "T0.txt", "point", "0.02:0.06:20", "0:0.04:20")),
-          ("normals", "normals_app", ("P.xyz", "16")),
-          ("orient", "orient_app", ("P_n_mixed.txt", "8", "-1")),
-          ("outliers", "knn_app", ("P.xyz", "stat", "16", "2.0")),
-          ("voxel", "voxel_app", ("P_n_rgb.txt", "0.02", "attrs"))]
+          ("normals", "normals_facade_app", ("normals", "P.xyz", "16")),
+          ("orient", "normals_facade_app", ("orient", "P_n_mixed.txt", "8", "-1")),
+          ("outliers", "normals_facade_app", ("outliers", "P.xyz", "stat", "16", "2.0")),
+          ("voxel", "normals_facade_app", ("voxel", "P_n_rgb.txt", "0.02", "attrs"))]
 
 
 def _radial(X):
@@ -107,7 +106,7 @@ def write_inputs(d):
 
 
 def build(outdir, include=None):
-    """The seven programs against the facade headers under `include` (default: this tree's): program -> path."""
+    """The programs against the facade headers under `include` (default: this tree's): program -> path."""
     return {name: apps.build_app(outdir, name, libs, ("-Werror",), include=include) for name, libs in PROGRAMS.items()}
 
 

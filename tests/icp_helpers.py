@@ -1,19 +1,14 @@
 """Test-side restatement of the ICP contract (include/s4p_icp.h): tests/icp_cpu/icp_cpu.cpp through ctypes, and the
 refine loop on top of it with the library's host solve (s4p_icp_solve)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "icp_cpu", "icp_cpu.cpp")
+from tests import normals_suite as S
 
 
 def build_cpu(outdir):
-    so = os.path.join(str(outdir), "libicp_cpu.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("icp_cpu/icp_cpu.cpp", outdir, "libicp_cpu")
     fp, vp = C.POINTER(C.c_float), C.c_void_p
     L.icp_cpu_pass.restype = C.c_int64
     L.icp_cpu_pass.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, vp, C.c_float, vp, vp, vp, C.c_int32]

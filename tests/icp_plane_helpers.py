@@ -2,21 +2,15 @@
 tests/icp_plane_cpu/icp_plane_cpu.cpp, the normals and the 31 plane sums in numpy, and the refine loop on top of them with
 the library's host solve (s4p_icp_solve_plane)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from tests import icp_helpers as H
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "icp_plane_cpu", "icp_plane_cpu.cpp")
+from tests import normals_suite as S
 
 
 def build_plane_cpu(outdir):
-    so = os.path.join(str(outdir), "libicp_plane_cpu.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("icp_plane_cpu/icp_plane_cpu.cpp", outdir, "libicp_plane_cpu")
     vp = C.c_void_p
     L.icp_plane_cpu_cov.restype = None
     L.icp_plane_cpu_cov.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, vp, C.c_int32]
@@ -37,14 +31,9 @@ class PlaneCPU:
         return k, c6
 
 
-LITERAL_SRC = os.path.join(ROOT, "tests", "icp_plane_cpu", "icp_normals_literal.cpp")
-
-
 def build_normals_literal(outdir):
     """tests/icp_plane_cpu/icp_normals_literal.cpp: k_normals restated term by term, for bit-for-bit comparison."""
-    so = os.path.join(str(outdir), "libicp_normals_literal.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", LITERAL_SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("icp_plane_cpu/icp_normals_literal.cpp", outdir, "libicp_normals_literal")
     vp = C.c_void_p
     L.icp_normals_literal.restype = C.c_int32
     L.icp_normals_literal.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_float, C.c_int32, vp, C.c_int64, vp, vp, vp, C.c_int32]

@@ -3,14 +3,12 @@ restatement (tests/normals_helpers.py): lists from the numpy lexsort brute force
 numpy float32 in the contract's order, lists without self as the first k of (the k + 1 list minus the own index), the mean
 neighbour distances in double in ascending order, and the clouds the tests share."""
 import math
-import os
 
 import numpy as np
 
 from tests import apps
 from tests import normals_helpers as NH
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = 2.0 ** -52
 
 
@@ -157,8 +155,3 @@ def tiny_radius(n):
 
 
 write_obj = apps.write_obj
-
-
-def build_app(outdir, extra=()):
-    """tests/knn_app/main.cpp against the facade header and libsuper4pcs_normals.so."""
-    return apps.build_app(outdir, "knn_app", ("super4pcs_normals",), ("-Werror",) + tuple(extra))

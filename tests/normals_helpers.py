@@ -1,19 +1,14 @@
 """Test-side restatement of the normal-estimation contract (include/s4p_normals.h): tests/normals_cpu/normals_cpu.cpp through
 ctypes (brute-force neighbour sets and normals), and a numpy brute force of the neighbour sets."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "normals_cpu", "normals_cpu.cpp")
+from tests import normals_suite as S
 
 
 def build_cpu(outdir):
-    so = os.path.join(str(outdir), "libnormals_cpu.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("normals_cpu/normals_cpu.cpp", outdir, "libnormals_cpu")
     vp = C.c_void_p
     L.normals_cpu_knn.restype = None
     L.normals_cpu_knn.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp, vp, C.c_int32]
@@ -28,8 +23,7 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def _cols(X):
-    return [np.ascontiguousarray(np.asarray(X)[:, a], np.float32) for a in range(3)]
+_cols = S.cols
 
 
 def _r(radius):
@@ -46,8 +40,7 @@ class CPU:
         q = p if queries is None else _cols(queries)
         m = q[0].shape[0]
         idx = np.empty((m, k), np.int32); cnt = np.empty(m, np.int32)
-        self.L.normals_cpu_knn(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, p[0].shape[0], q[0].ctypes.data, q[1].ctypes.data,
-                               q[2].ctypes.data, m, int(k), _r(radius), idx.ctypes.data, cnt.ctypes.data, int(threads))
+        self.L.normals_cpu_knn(*S.xyzn(p), *S.xyzn(q), int(k), _r(radius), idx.ctypes.data, cnt.ctypes.data, int(threads))
         return idx, cnt
 
     def normals(self, X, k, radius=None, queries=None, threads=0):
@@ -56,8 +49,7 @@ class CPU:
         q = p if queries is None else _cols(queries)
         m = q[0].shape[0]
         out = np.empty((m, 3), np.float32)
-        self.L.normals_cpu_normals(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, p[0].shape[0], q[0].ctypes.data,
-                                   q[1].ctypes.data, q[2].ctypes.data, m, int(k), _r(radius), out.ctypes.data, int(threads))
+        self.L.normals_cpu_normals(*S.xyzn(p), *S.xyzn(q), int(k), _r(radius), out.ctypes.data, int(threads))
         return out
 
     def normals_of_lists(self, X, idx, queries=None):
@@ -68,8 +60,7 @@ class CPU:
         m, k = idx.shape
         assert q[0].shape[0] == m
         out = np.empty((m, 3), np.float32)
-        self.L.normals_cpu_normals_of_lists(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, q[0].ctypes.data, q[1].ctypes.data,
-                                            q[2].ctypes.data, m, k, idx.ctypes.data, out.ctypes.data)
+        self.L.normals_cpu_normals_of_lists(*S.xyzn(p)[:3], *S.xyzn(q), k, idx.ctypes.data, out.ctypes.data)
         return out
 
 

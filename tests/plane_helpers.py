@@ -5,16 +5,13 @@ two-level order, a Jacobi of its own in Python floats), the distance of every re
 the host and the GPU tests share.  Only numpy is used."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 from tests import cluster_helpers as CH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "plane_cpu", "plane_cpu.cpp")
 SUM_BLOCK = 128
 GOLDEN, MASK64 = 0x9E3779B97F4A7C15, (1 << 64) - 1
 
@@ -22,9 +19,7 @@ bits = NH.bits
 
 
 def build_cpu(outdir):
-    so = os.path.join(str(outdir), "libplane_cpu.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("plane_cpu/plane_cpu.cpp", outdir, "libplane_cpu")
     vp = C.c_void_p
     L.plane_cpu_segment.restype = None
     L.plane_cpu_segment.argtypes = [vp, vp, vp, C.c_int64, C.c_float, C.c_int32, C.c_uint64, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32]
@@ -38,14 +33,13 @@ class CPU:
     def segment(self, X, distance, trials=1024, seed=0, refine=1, exclude=None, threads=16, all_counts=False):
         """(plane (4,) float32, mask (n,) uint8, info) as super4pcs_amd.plane.Plane.segment returns them; with all_counts the
         info also holds "counts" (int32 per candidate, 0 for an invalid one) and "valid" (uint8 per candidate)."""
-        p = NH._cols(X)
+        p = S.cols(X)
         n = p[0].shape[0]
         ex = None if exclude is None else np.ascontiguousarray(np.asarray(exclude) != 0, dtype=np.uint8)
         pl = np.zeros(8, np.float32); ints = np.zeros(4, np.int64); mask = np.zeros(n, np.uint8)
         counts = np.zeros(trials, np.int32); valid = np.zeros(trials, np.uint8)
-        self.L.plane_cpu_segment(p[0].ctypes.data, p[1].ctypes.data, p[2].ctypes.data, n, float(distance), int(trials), int(seed) & MASK64, int(refine),
-                                 None if ex is None else ex.ctypes.data, pl.ctypes.data, ints.ctypes.data, mask.ctypes.data, counts.ctypes.data,
-                                 valid.ctypes.data, int(threads))
+        self.L.plane_cpu_segment(*S.xyzn(p), float(distance), int(trials), int(seed) & MASK64, int(refine), S.ptr(ex), pl.ctypes.data,
+                                 ints.ctypes.data, mask.ctypes.data, counts.ctypes.data, valid.ctypes.data, int(threads))
         info = {"centre": pl[4:7].copy(), "d_centred": pl[7], "inliers": int(ints[0]), "alive": int(ints[1]), "trial": int(ints[2]),
                 "valid_trials": int(ints[3])}
         if all_counts:
@@ -57,8 +51,7 @@ def same(a, b):
     """Bit equality of two (plane, mask, info) triples: the plane, d_centred, the centre, trial, valid_trials, inliers, alive
     and the mask."""
     (pa, ma, ia), (pb, mb, ib) = a, b
-    ma = ma.cpu().numpy() if hasattr(ma, "cpu") else np.asarray(ma)
-    mb = mb.cpu().numpy() if hasattr(mb, "cpu") else np.asarray(mb)
+    ma, mb = S.to_host(ma), S.to_host(mb)
     return (np.array_equal(bits(pa), bits(pb)) and np.array_equal(ma, mb) and
             np.array_equal(bits(np.float32(ia["d_centred"])), bits(np.float32(ib["d_centred"]))) and
             np.array_equal(bits(ia["centre"]), bits(ib["centre"])) and

@@ -4,26 +4,18 @@ binding and the exports, the new kernels in the library's namespace, the loud fa
 sklearn.cluster.DBSCAN on the real clouds, the reference figures of the planted and the lidar clouds, the border rule's two
 outcomes, the command line's new flags and the facade header with and without Eigen."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import apps
 from tests import cluster_helpers as CH
 from tests import knn_helpers as KH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import normals_suite as S
 
 
 @pytest.fixture(scope="module")
 def clu():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import cluster
-    return cluster
+    return S.normals_module("cluster")
 
 
 @pytest.fixture(scope="module")
@@ -31,42 +23,24 @@ def cpu(tmp_path_factory):
     return CH.build_cpu(tmp_path_factory.mktemp("cluster_cpu"))
 
 
-def _gpu_visible():
-    from tests.conftest import _gpu_visible as g
-    return g()
-
-
 def test_header_declarations_equal_the_binding_and_the_exports(clu):
     from super4pcs_amd import normals
-    txt = open(os.path.join(ROOT, "include", "s4p_cluster.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    decl = sorted(set(re.findall(r"\b(s4p_cluster_\w+)\s*\(", txt)))
-    assert len(decl) == 4 and decl == sorted(clu.SYMBOLS), decl
-    assert not re.findall(r"\b(s4p_(?:normals|knn|outliers|voxel|orient)_\w+)\s*\(", txt)      # the older prefixes stay closed sets
-    L = clu.load_library()
-    for s in decl:
-        assert getattr(L, s).argtypes is not None and getattr(L, s).restype is ctypes.c_int32, s
-    exported = subprocess.run(["nm", "-D", "--defined-only", normals.LIB_PATH], capture_output=True, text=True).stdout
-    assert sorted(set(re.findall(r"\b(s4p_cluster_\w+)", exported))) == decl
+    txt, decl, _ = S.check_header("s4p_cluster.h", "s4p_cluster_", clu.SYMBOLS, clu.load_library(),
+                                  closed_prefixes="s4p_(?:normals|knn|outliers|voxel|orient)_")
+    assert len(decl) == 4
     assert ctypes.sizeof(clu.ClusterStats) == 32
     assert (clu.NOISE, clu.BORDER, clu.CORE) == (0, 1, 2) and "S4P_CLUSTER_ERR_INTERNAL (-8)" in txt and normals.ERR_NAMES[-8] == "INTERNAL"
 
 
 def test_new_kernels_live_in_the_library_namespace(clu):
-    from super4pcs_amd import normals
-    out = subprocess.run(["nm", "-C", normals.LIB_PATH], capture_output=True, text=True).stdout
-    for name in ("k_cluster_walk<0>", "k_cluster_walk<1>", "k_cluster_link", "k_cluster_flatten", "k_cluster_label"):
-        assert "s4p_nrm::" + name in out, name
-    assert not re.search(r"(?<!s4p_nrm::)(?<!__device_stub__)\bk_cluster_\w+", out)
+    S.check_kernels_in_namespace(("k_cluster_walk<0>", "k_cluster_walk<1>", "k_cluster_link", "k_cluster_flatten", "k_cluster_label"),
+                                 stray=r"(?<!s4p_nrm::)(?<!__device_stub__)\bk_cluster_\w+")
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_calls_fail_loudly_without_a_device(clu):
     X = np.zeros((10, 3), np.float32)
-    for call in (lambda: clu.cluster_dbscan(X, 0.1), lambda: clu.keep_clusters(X, 0.1), lambda: clu.Cluster(0)):
-        with pytest.raises(clu.NormalsError) as e:
-            call()
-        assert e.value.code == -2 and "no HIP device" in str(e.value)
+    S.check_no_device(clu.NormalsError, (lambda: clu.cluster_dbscan(X, 0.1), lambda: clu.keep_clusters(X, 0.1), lambda: clu.Cluster(0)))
 
 
 def test_largest_labels_break_size_ties_by_the_smaller_label(clu):
@@ -171,69 +145,36 @@ def test_restatement_equals_sklearn_where_no_pair_lies_at_the_boundary(cpu, name
 
 
 def test_cli_cluster_flags(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--cluster-min-points", "4"], ["--cluster-keep", "2"],                                  # both need --cluster-eps
-                ["--cluster-eps", "0"], ["--cluster-eps", "-0.1"], ["--cluster-eps", "nan"], ["--cluster-eps", "inf"],
-                ["--cluster-eps", "1e20"], ["--cluster-eps", "1e-50"], ["--cluster-eps", "0.1x"], ["--cluster-eps", ""], ["--cluster-eps"],
-                ["--cluster-eps", "0.1", "--cluster-min-points", "0"], ["--cluster-eps", "0.1", "--cluster-min-points", "-3"],
-                ["--cluster-eps", "0.1", "--cluster-min-points", "4.5"], ["--cluster-eps", "0.1", "--cluster-min-points", "x"],
-                ["--cluster-eps", "0.1", "--cluster-min-points", ""], ["--cluster-eps", "0.1", "--cluster-min-points"],
-                ["--cluster-eps", "0.1", "--cluster-min-points", "3000000000"],
-                ["--cluster-eps", "0.1", "--cluster-keep", "0"], ["--cluster-eps", "0.1", "--cluster-keep", "1.5"],
-                ["--cluster-eps", "0.1", "--cluster-keep", ""], ["--cluster-eps", "0.1", "--cluster-keep"]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--cluster-eps e" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--cluster-eps", "0.03"], ["--cluster-min-points", "4", "--cluster-eps", "3e-2"],
-                 ["--cluster-eps", "0.5", "--cluster-min-points", "1", "--cluster-keep", "3"],
-                 ["--remove-outliers", "16", "--voxel-size", "0.01", "--cluster-eps", "0.03", "--estimate-normals", "16", "--icp", "10"]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
-    r = subprocess.run(base + ["-h"], capture_output=True, text=True)
-    assert r.stderr.index("--orient-normals k") < r.stderr.index("--cluster-eps e")       # the older usage lines come first
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--cluster-min-points", "4"], ["--cluster-keep", "2"],                                  # both need --cluster-eps
+             ["--cluster-eps", "0"], ["--cluster-eps", "-0.1"], ["--cluster-eps", "nan"], ["--cluster-eps", "inf"],
+             ["--cluster-eps", "1e20"], ["--cluster-eps", "1e-50"], ["--cluster-eps", "0.1x"], ["--cluster-eps", ""], ["--cluster-eps"],
+             ["--cluster-eps", "0.1", "--cluster-min-points", "0"], ["--cluster-eps", "0.1", "--cluster-min-points", "-3"],
+             ["--cluster-eps", "0.1", "--cluster-min-points", "4.5"], ["--cluster-eps", "0.1", "--cluster-min-points", "x"],
+             ["--cluster-eps", "0.1", "--cluster-min-points", ""], ["--cluster-eps", "0.1", "--cluster-min-points"],
+             ["--cluster-eps", "0.1", "--cluster-min-points", "3000000000"],
+             ["--cluster-eps", "0.1", "--cluster-keep", "0"], ["--cluster-eps", "0.1", "--cluster-keep", "1.5"],
+             ["--cluster-eps", "0.1", "--cluster-keep", ""], ["--cluster-eps", "0.1", "--cluster-keep"]),
+        good=(["--cluster-eps", "0.03"], ["--cluster-min-points", "4", "--cluster-eps", "3e-2"],
+              ["--cluster-eps", "0.5", "--cluster-min-points", "1", "--cluster-keep", "3"],
+              ["--remove-outliers", "16", "--voxel-size", "0.01", "--cluster-eps", "0.03", "--estimate-normals", "16", "--icp", "10"]),
+        usage_word="--cluster-eps e", usage_order=("--orient-normals k", "--cluster-eps e"))
 
 
 def test_cli_refuses_an_input_with_faces(tmp_path):
-    """Faces index the vertex list: refused before any device work, with exit status -2 and the flag's name."""
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts)
-    KH.write_obj(tmp_path / "Q.obj", pts, faces=[(1, 2, 3), (2, 3, 4)])
-    for first, second in (("P.obj", "Q.obj"), ("Q.obj", "P.obj")):
-        r = subprocess.run([cli, "-i", str(tmp_path / first), str(tmp_path / second), "--cluster-eps", "0.1", "-m", str(tmp_path / "m.txt")],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 254 and "--cluster-eps" in r.stdout + r.stderr and "faces" in r.stdout + r.stderr, (r.returncode, r.stdout, r.stderr)
-        assert not (tmp_path / "m.txt").exists()
+    S.check_cli_refuses_faces(tmp_path, ["--cluster-eps", "0.1"])
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_cli_valid_command_fails_with_the_device_error_without_a_gpu(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts); KH.write_obj(tmp_path / "Q.obj", pts)
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "--cluster-eps", "0.2", "--cluster-min-points", "4", "-m",
-                        str(tmp_path / "m.txt")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 254, (r.returncode, r.stdout, r.stderr)
-    assert "Unknown flag" not in r.stderr and "ClusterDBSCAN (MI355X)" in r.stdout + r.stderr and "no HIP device" in r.stdout + r.stderr
+    S.check_cli_no_device(tmp_path, ["--cluster-eps", "0.2", "--cluster-min-points", "4"], "ClusterDBSCAN (MI355X)")
 
 
 @pytest.mark.parametrize("eigen", [False, True])
 def test_facade_header_compiles_with_and_without_eigen(clu, tmp_path, eigen):
-    extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text('#include "super4pcs/algorithms/cluster.h"\n#ifdef S4P_HAVE_EIGEN\n#error have\n#else\n#error none\n#endif\n')
-    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include")] + extra + [str(probe)],
-                       capture_output=True, text=True)
-    assert re.search(r"#error (have|none)", r.stderr).group(1) == ("have" if eigen else "none"), r.stderr
-    exe = apps.build_app(tmp_path, "cluster_app", ("super4pcs_normals",), ["-Werror"] + extra)
-    np.savetxt(tmp_path / "P.xyz", np.random.default_rng(2).uniform(size=(20, 3)), fmt="%.6f")
-    if not _gpu_visible():
-        r = subprocess.run([exe, str(tmp_path / "P.xyz"), "0.2", "4", "1", "1"], capture_output=True, text=True)
-        assert r.returncode == 1 and "ClusterDBSCAN (MI355X)" in r.stderr and "no HIP device" in r.stderr
-    for bad in (["0", "4", "1", "1"], ["-1", "4", "1", "1"], ["nan", "4", "1", "1"], ["inf", "4", "1", "1"], ["1e20", "4", "1", "1"],
-                ["0.2", "0", "1", "1"], ["0.2", "4", "0", "1"], ["0.2", "4", "1", "0"]):
-        r = subprocess.run([exe, str(tmp_path / "P.xyz")] + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "ClusterDBSCAN:" in r.stderr, (bad, r.stderr)
+    S.check_facade_header(tmp_path, "cluster.h", eigen, "cluster", np.random.default_rng(2).uniform(size=(20, 3)),
+                          no_device_args=["0.2", "4", "1", "1"], no_device_text=("ClusterDBSCAN (MI355X)", "no HIP device"),
+                          bad_args=(["0", "4", "1", "1"], ["-1", "4", "1", "1"], ["nan", "4", "1", "1"], ["inf", "4", "1", "1"], ["1e20", "4", "1", "1"],
+                                    ["0.2", "0", "1", "1"], ["0.2", "4", "0", "1"], ["0.2", "4", "1", "0"]),
+                          bad_text="ClusterDBSCAN:")

@@ -14,16 +14,14 @@ from tests import apps
 from tests import cluster_helpers as CH
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def clu():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import cluster
-    return cluster
+    return S.normals_module("cluster")
 
 
 @pytest.fixture(scope="module")
@@ -102,7 +100,6 @@ def test_fragment_goes_through_python_the_facade_and_the_command_line(clu, cpu, 
     """The cloud the statistical filter cannot clean: the surface, a dense blob away from it and 60 planted points.  At
     (0.03, 4) there are two clusters; keeping the largest removes the blob and the planted points, 209 in all, through
     keep_clusters, KeepLargestClusters (normals and colours move with their points) and --cluster-eps."""
-    from super4pcs_amd import build as B
     X, planted = CH.fragment_cloud()
     F = CH.FRAGMENT
     ctx = clu.Cluster(0)
@@ -116,20 +113,16 @@ def test_fragment_goes_through_python_the_facade_and_the_command_line(clu, cpu, 
     assert np.array_equal(both, label >= 0)
     assert np.array_equal(clu.keep_clusters(X, F["eps"], F["min_points"], keep=2, min_size=150)[1], mask)
     # the facade
-    exe = apps.build_app(tmp_path, "cluster_app", ("super4pcs_normals",), ("-Werror",))
-    apps.write_xyz(tmp_path / "X.xyz", X)
-    r = subprocess.run([exe, str(tmp_path / "X.xyz"), str(F["eps"]), str(F["min_points"]), "1", "1"], capture_output=True, text=True, timeout=apps.TIMEOUT)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.splitlines()
+    heads, (got_label, got_mask), rest = S.run_points_app(S.build_facade_app(tmp_path), ["cluster", F["eps"], F["min_points"], "1", "1"], X)
     n = len(X)
-    assert lines[0] == "clusters 2" and np.array_equal(np.array(lines[1:1 + n], np.int32), label)
-    assert lines[1 + n] == "removed %d" % F["removed"] and np.array_equal(np.array(lines[2 + n:2 + 2 * n], np.int32) != 0, mask)
-    rest = np.array([[float(v) for v in ln.split()] for ln in lines[2 + 2 * n:]], np.float32)
+    assert heads[0] == "clusters 2" and np.array_equal(got_label, label)
+    assert heads[1:] == ["removed %d" % F["removed"]] and len(got_mask) == n and np.array_equal(got_mask != 0, mask)
+    rest = rest.astype(np.float32)
     assert np.array_equal(NH.bits(rest[:, :3]), NH.bits(X[mask])) and (rest[:, 3] == 1).all()
     assert np.array_equal(rest[:, 4].astype(np.int64), np.flatnonzero(mask))
     # the command line: both inputs filtered, -r holds the kept points of the second
     apps.write_obj(tmp_path / "P.obj", X); apps.write_obj(tmp_path / "Q.obj", X)
-    cli = B.build_cli()
+    cli = S.cli()
     M, out = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", 0.01, 0.6, 200,
                           ["--cluster-eps", F["eps"], "--cluster-min-points", F["min_points"], "-r", tmp_path / "R.obj"])
     assert "removed %d of input1, %d of input2" % (F["removed"], F["removed"]) in out, out
@@ -167,27 +160,26 @@ def test_one_multi_trip_size_at_the_float_boundary(clu, cpu):
     assert np.array_equal(label, l2) and np.array_equal(kind, k2) and s2 == stats
     ctx.close()
     t = clu.Cluster(0)
-    t.set_cloud(torch.from_numpy(X).cuda())
+    t.set_cloud(S.to_device(X))
     lt, kt, st = t.dbscan(G["eps"], G["min_points"])
     ct = t.density(G["eps"])
     assert lt.is_cuda and kt.is_cuda and ct.is_cuda and lt.dtype == torch.int32 and kt.dtype == torch.uint8 and ct.dtype == torch.int32
-    assert np.array_equal(lt.cpu().numpy(), label) and np.array_equal(kt.cpu().numpy(), kind) and st == stats
-    assert np.array_equal(ct.cpu().numpy() >= G["min_points"], kind == CH.CORE)
+    assert np.array_equal(S.to_host(lt), label) and np.array_equal(S.to_host(kt), kind) and st == stats
+    assert np.array_equal(S.to_host(ct) >= G["min_points"], kind == CH.CORE)
     t.close()
 
 
 def test_numpy_and_torch_give_the_same_bits_and_two_calls_too(clu):
-    import torch
     X = KH.tiny_cloud(257, True)
     eps = CH.tiny_eps(257)
     a = clu.cluster_dbscan(X, eps, 2)
     b = clu.cluster_dbscan(X, eps, 2)
-    t = clu.cluster_dbscan(torch.from_numpy(X).cuda(), eps, 2)
+    t = clu.cluster_dbscan(S.to_device(X), eps, 2)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[2] == b[2]
-    assert t[0].is_cuda and np.array_equal(t[0].cpu().numpy(), a[0]) and np.array_equal(t[1].cpu().numpy(), a[1]) and t[2] == a[2]
-    kept, mask, lab = clu.keep_clusters(torch.from_numpy(X).cuda(), eps, 2, keep=3)
+    assert t[0].is_cuda and np.array_equal(S.to_host(t[0]), a[0]) and np.array_equal(S.to_host(t[1]), a[1]) and t[2] == a[2]
+    kept, mask, lab = clu.keep_clusters(S.to_device(X), eps, 2, keep=3)
     kn, mn, ln = clu.keep_clusters(X, eps, 2, keep=3)
-    assert kept.is_cuda and mask.is_cuda and np.array_equal(kept.cpu().numpy(), kn) and np.array_equal(mask.cpu().numpy(), mn)
+    assert kept.is_cuda and mask.is_cuda and np.array_equal(S.to_host(kept), kn) and np.array_equal(S.to_host(mask), mn)
     assert 0 < mn.sum() < len(X) and np.array_equal(np.isin(ln, clu.largest_labels(ln, 3)), mn)
 
 

@@ -1,6 +1,6 @@
 """The facade headers against tests/golden/facade_parity.json: what tests/icp_facade_app (RefineICP with every metric, own and
-estimated normals, losses, rejection; RefineICPBatch), multiway_app (RegisterMultiway, ICPInformation), icp_multiscale_app,
-normals_app, orient_app, knn_app and voxel_app print on the hippo fixture.  The file was recorded on the MI355X by
+estimated normals, losses, rejection; RefineICPBatch), multiway_app (RegisterMultiway, ICPInformation), icp_multiscale_app and
+normals_facade_app (normals, orient, outliers, voxel) print on the hippo fixture.  The file was recorded on the MI355X by
 tests/golden/make_facade_parity_golden.py with the headers as they stood before the session steps were stated once
 (DESIGN.md section "Facade: layout"); this test builds the programs from this tree and runs the recorder's own list.  The
 headers' host arithmetic has a fixed order and the libraries sum in a fixed order, so the bar is equal strings, line by

@@ -16,6 +16,7 @@ from tests import cluster_helpers as CH
 from tests import grid_regime_cases as G
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 from tests import orient_helpers as OH
 
 pytestmark = pytest.mark.gpu
@@ -23,10 +24,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def clu():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import cluster
-    return cluster
+    return S.normals_module("cluster")
 
 
 @pytest.fixture(scope="module")
@@ -239,7 +237,7 @@ def test_a_cloud_below_the_scale_limit_is_refused_and_the_context_stays_usable(c
     ctx.set_cloud(line)
     if kind == "torch":
         import torch
-        X = torch.from_numpy(np.array(X)).cuda()
+        X = S.to_device(np.array(X))
     with pytest.raises(clu.NormalsError) as e:
         ctx.set_cloud(X)
     assert e.value.code == -1 and "too small for float distances" in str(e.value) and "rescale the cloud" in str(e.value)

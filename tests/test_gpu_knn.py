@@ -7,16 +7,14 @@ import pytest
 
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def knn():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import knn
-    return knn
+    return S.normals_module("knn")
 
 
 @pytest.fixture(scope="module")
@@ -147,17 +145,17 @@ def test_two_calls_and_numpy_torch_agree(knn, real):
     b = ctx.search(16, None, exclude_self=True)
     for u, v in zip(a, b):
         assert np.array_equal(u.view(np.uint32) if u.dtype == np.float32 else u, v.view(np.uint32) if v.dtype == np.float32 else v)
-    Xt = torch.from_numpy(X).cuda()
+    Xt = S.to_device(X)
     t = knn.knn(Xt, 16, exclude_self=True)
     assert all(v.is_cuda for v in t) and t[0].dtype == torch.int32 and t[1].dtype == torch.float32 and t[2].dtype == torch.int32
     assert tuple(t[0].shape) == (len(X), 16)
-    _same(tuple(v.cpu().numpy() for v in t), a, what="torch self")
+    _same(tuple(S.to_host(v) for v in t), a, what="torch self")
     _same(knn.knn(X, 16, exclude_self=True), a, what="one-shot")
     Q = X[:777] + np.float32(0.01)
     qn = knn.knn(X, 8, radius=0.5, queries=Q)
-    qt = knn.knn(Xt, 8, radius=0.5, queries=torch.from_numpy(Q).cuda())
+    qt = knn.knn(Xt, 8, radius=0.5, queries=S.to_device(Q))
     assert all(v.is_cuda for v in qt)
-    _same(tuple(v.cpu().numpy() for v in qt), qn, what="torch queries")
+    _same(tuple(S.to_host(v) for v in qt), qn, what="torch queries")
 
 
 def test_bad_arguments(knn):

@@ -12,6 +12,7 @@ import pytest
 from tests import apps
 from tests import helpers as H
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -20,10 +21,7 @@ KS = (3, 8, 16, 32)
 
 @pytest.fixture(scope="module")
 def nrm():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import normals
-    return normals
+    return S.normals_module("normals")
 
 
 @pytest.fixture(scope="module")
@@ -130,15 +128,15 @@ def test_two_calls_and_numpy_torch_agree(nrm, clouds, contexts):
     ctx = contexts["lidar"]
     a = ctx.estimate(16)
     assert np.array_equal(NH.bits(a), NH.bits(ctx.estimate(16)))
-    Xt = torch.from_numpy(X).cuda()
+    Xt = S.to_device(X)
     t = nrm.estimate_normals(Xt, k=16)
     assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (len(X), 3)
-    assert np.array_equal(NH.bits(t.cpu().numpy()), NH.bits(a))
+    assert np.array_equal(NH.bits(S.to_host(t)), NH.bits(a))
     assert np.array_equal(NH.bits(nrm.estimate_normals(X, k=16)), NH.bits(a))
     Q = X[:777] + np.float32(0.01)
     qn = nrm.estimate_normals(X, k=8, radius=0.5, queries=Q)
-    qt = nrm.estimate_normals(Xt, k=8, radius=0.5, queries=torch.from_numpy(Q).cuda())
-    assert np.array_equal(NH.bits(qt.cpu().numpy()), NH.bits(qn))
+    qt = nrm.estimate_normals(Xt, k=8, radius=0.5, queries=S.to_device(Q))
+    assert np.array_equal(NH.bits(S.to_host(qt)), NH.bits(qn))
 
 
 def test_plane_sphere_and_zero_normals(nrm):

@@ -14,6 +14,7 @@ from tests import apps
 from tests import helpers as H
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 from tests import orient_helpers as OH
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,7 @@ VIEW = (0.3, -0.2, 2.0)
 
 @pytest.fixture(scope="module")
 def nrm():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import normals
-    return normals
+    return S.normals_module("normals")
 
 
 @pytest.fixture(scope="module")
@@ -117,11 +115,11 @@ def test_one_multi_trip_size_is_deterministic_and_outward(nrm):
     N = ctx.estimate(16)
     a, info = ctx.orient(N, 8, return_info=True)
     b = ctx.orient(N, 8)
-    t = ctx.orient(torch.from_numpy(N).cuda(), 8)
-    assert t.is_cuda and np.array_equal(OH.bits(a), OH.bits(b)) and np.array_equal(OH.bits(a), OH.bits(t.cpu().numpy()))
-    Xt = torch.from_numpy(X).cuda()
+    t = ctx.orient(S.to_device(N), 8)
+    assert t.is_cuda and np.array_equal(OH.bits(a), OH.bits(b)) and np.array_equal(OH.bits(a), OH.bits(S.to_host(t)))
+    Xt = S.to_device(X)
     u = nrm.estimate_normals(Xt, k=16, orient="outward")
-    assert u.is_cuda and np.array_equal(OH.bits(a), OH.bits(u.cpu().numpy()))
+    assert u.is_cuda and np.array_equal(OH.bits(a), OH.bits(S.to_host(u)))
     assert info["vertices"] == n and info["components"] == 1 and info["rounds"] >= 2
     assert ((a.astype(np.float64) * X).sum(1) > 0).all()
     assert np.array_equal(np.abs(a), np.abs(N)) and np.array_equal(info["flipped"], (a != N).any(1))
@@ -149,7 +147,6 @@ def test_sphere_and_bumpy_cloud_come_out_outward(nrm):
 
 
 def test_orient_towards_equals_the_numpy_expression(nrm):
-    import torch
     rng = np.random.default_rng(6)
     X = np.concatenate([np.array([[1, 0, 0], [1, 0, 0], [1, 0, 0], [0, 2, 0], [0, 2, 0], [0, 0, 1]], np.float32),
                         rng.uniform(-1, 1, size=(3000, 3)).astype(np.float32)])
@@ -162,8 +159,8 @@ def test_orient_towards_equals_the_numpy_expression(nrm):
         got = ctx.orient_towards(N, vp)
         assert np.array_equal(OH.bits(got), OH.bits(want)), vp
         assert 0.2 < flip.mean() < 0.8
-        t = ctx.orient_towards(torch.from_numpy(N).cuda(), vp)
-        assert t.is_cuda and np.array_equal(OH.bits(t.cpu().numpy()), OH.bits(want))
+        t = ctx.orient_towards(S.to_device(N), vp)
+        assert t.is_cuda and np.array_equal(OH.bits(S.to_host(t)), OH.bits(want))
     want, flip = OH.towards(X, N, (0, 0, 0))
     assert flip[:6].tolist() == [False, True, False, False, False, False]      # n . g = 0, no normal, non-finite: untouched
     fl = np.full(len(X), 7, np.uint8)
@@ -260,29 +257,25 @@ def test_refusals(nrm):
 
 
 def test_facade_and_command_line(nrm, s4p_lib_built, tmp_path):
-    """orient_app: OrientNormals on points whose normals went through Point3D::set_normal equals the Python result on the
-    same normals (a flipped point is renormalised once more, the others are untouched).  The command line with
+    """The facade program's orient: OrientNormals on points whose normals went through Point3D::set_normal equals the Python
+    result on the same normals (a flipped point is renormalised once more, the others are untouched).  The command line with
     --estimate-normals 16 --orient-normals 8 --icp 10 --icp-normal-angle 60 registers; the two `needs` rules are usage errors."""
-    from super4pcs_amd import build as B
     X = KH.tiny_cloud(257, True)
     N0 = OH.random_normals(257, 13)
     Nin = NH.point3d_normalise(N0)                                # what the app's points hold: set_normal renormalises
-    exe = apps.build_app(tmp_path, "orient_app", ("super4pcs_normals",), ("-Werror",))
-    apps.write_xyz(tmp_path / "PN.txt", np.concatenate([X, N0], 1))
-    for extra, vp in (([], None), ([str(v) for v in VIEW], VIEW)):
-        r = subprocess.run([exe, str(tmp_path / "PN.txt"), "8", "-1"] + extra, capture_output=True, text=True, timeout=apps.TIMEOUT)
-        assert r.returncode == 0, r.stderr
-        lines = r.stdout.splitlines()
-        got = np.array([[float(v) for v in ln.split()] for ln in lines[1:]], np.float32)
+    exe = S.build_facade_app(tmp_path)
+    for extra, vp in (([], None), (list(VIEW), VIEW)):
+        heads, _, got = S.run_points_app(exe, ["orient", "8", "-1"] + extra, np.concatenate([X, N0], 1))
+        got = got.astype(np.float32)
         O = nrm.orient_normals(X, Nin, k=8, viewpoint=vp)
         flip = (OH.bits(O) != OH.bits(Nin)).any(1)
         want = Nin.copy()
         want[flip] = NH.point3d_normalise(O)[flip]
-        assert int(lines[0].split()[1]) == int(flip.sum()) > 20 and np.array_equal(OH.bits(got), OH.bits(want)), vp
+        assert heads == ["flipped %d" % flip.sum()] and flip.sum() > 20 and np.array_equal(OH.bits(got), OH.bits(want)), vp
     delta, overlap, n_s = 0.01, 0.6, 200
     P, Q, _ = H.small_pair(8000, delta=delta, seed=33)
     apps.write_obj(tmp_path / "P.obj", P); apps.write_obj(tmp_path / "Q.obj", Q)
-    cli = B.build_cli()
+    cli = S.cli()
     M, out = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", delta, overlap, n_s,
                           ["--estimate-normals", "16", "--orient-normals", "8", "--icp", "10", "--icp-normal-angle", "60"])
     assert "Oriented normals: k 8, outward" in out and "ICP:" in out and np.isfinite(M).all() and abs(np.linalg.det(M[:3, :3]) - 1) < 1e-3

@@ -9,6 +9,7 @@ import pytest
 from tests import cluster_helpers as CH
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 from tests import orient_helpers as OH
 
 pytestmark = pytest.mark.gpu
@@ -18,11 +19,8 @@ VIEW = (0.3, -0.2, 2.0)
 
 @pytest.fixture(scope="module")
 def clu():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import cluster, voxel
-    voxel.load_library()
-    return cluster
+    S.normals_module("voxel").load_library()
+    return S.normals_module("cluster")
 
 
 @pytest.fixture(scope="module")
@@ -83,7 +81,7 @@ def _flat(out):
     if isinstance(out, dict):
         return {key: _flat(v) for key, v in sorted(out.items())}
     if type(out).__module__.startswith("torch"):
-        out = out.cpu().numpy()
+        out = S.to_host(out)
     if isinstance(out, np.ndarray):
         return (out.dtype.str, out.shape, np.ascontiguousarray(out).tobytes())
     return out
@@ -120,7 +118,7 @@ def _sequence(wrap, tensors):
 def test_one_context_through_growing_and_shrinking_needs_equals_fresh_contexts(clu, form):
     if form == "torch":
         import torch
-        X, calls = _sequence(lambda a: torch.from_numpy(a).cuda(), True)
+        X, calls = _sequence(S.to_device, True)
     else:
         X, calls = _sequence(np.asarray, False)
     ctx = clu.Cluster(0)
@@ -171,7 +169,7 @@ def test_calls_without_their_optional_outputs_equal_the_full_calls(clu, form):
     from super4pcs_amd import knn, normals, voxel
     if form == "torch":
         import torch
-        wrap, dev = (lambda a: torch.from_numpy(a).cuda()), True
+        wrap, dev = S.to_device, True
     else:
         wrap, dev = np.asarray, False
     rng = np.random.default_rng(7)

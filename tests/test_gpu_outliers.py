@@ -1,7 +1,6 @@
 """Outlier removal on the MI355X (include/s4p_knn.h): the statistical filter's mean distances, mu, sigma, t and mask against
 the CPU restatement with correctly rounded sums, its edge cases, the radius filter's mask against numpy, determinism,
 numpy against torch, the facade application and the command line's --remove-outliers."""
-import os
 import subprocess
 
 import numpy as np
@@ -10,17 +9,14 @@ import pytest
 from tests import helpers as H
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def knn():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import knn
-    return knn
+    return S.normals_module("knn")
 
 
 @pytest.fixture(scope="module")
@@ -145,70 +141,47 @@ def test_two_calls_and_numpy_torch_agree(knn, planted, contexts):
     # the one-shot functions, numpy and torch
     kept, mask, stats = knn.remove_statistical_outliers(X, k=16, std_ratio=2.0)
     assert isinstance(kept, np.ndarray) and np.array_equal(mask, k1) and stats == s1 and np.array_equal(kept, X[k1])
-    Xt = torch.from_numpy(X).cuda()
+    Xt = S.to_device(X)
     kept_t, mask_t, stats_t = knn.remove_statistical_outliers(Xt, k=16, std_ratio=2.0)
     assert kept_t.is_cuda and mask_t.is_cuda and mask_t.dtype == torch.bool and stats_t == s1
-    assert np.array_equal(mask_t.cpu().numpy(), k1) and np.array_equal(kept_t.cpu().numpy(), X[k1])
+    assert np.array_equal(S.to_host(mask_t), k1) and np.array_equal(S.to_host(kept_t), X[k1])
     tctx = knn.Knn(0)
     tctx.set_cloud(Xt)
     _, _, md_t = tctx.statistical_outliers(16, 2.0)
-    assert md_t.is_cuda and md_t.dtype == torch.float64 and np.array_equal(md_t.cpu().numpy().view(np.uint64), m1.view(np.uint64))
+    assert md_t.is_cuda and md_t.dtype == torch.float64 and np.array_equal(S.to_host(md_t).view(np.uint64), m1.view(np.uint64))
     tctx.close()
     kept, mask = knn.remove_radius_outliers(X, 0.05, 8)
     kept_t, mask_t = knn.remove_radius_outliers(Xt, 0.05, 8)
-    assert np.array_equal(mask, r1) and np.array_equal(mask_t.cpu().numpy(), r1) and np.array_equal(kept_t.cpu().numpy(), kept)
+    assert np.array_equal(mask, r1) and np.array_equal(S.to_host(mask_t), r1) and np.array_equal(S.to_host(kept_t), kept)
     assert np.array_equal(kept, X[r1])
 
 
 def test_facade_application_gives_the_same_mask(knn, planted, contexts, tmp_path):
     X, _ = planted["bumpy"]
-    exe = KH.build_app(tmp_path)
+    exe = S.build_facade_app(tmp_path)
     np.savetxt(tmp_path / "P.xyz", X, fmt="%.9g")
     Xr = np.loadtxt(tmp_path / "P.xyz", dtype=np.float32)
     assert np.array_equal(Xr, X)
     for args, want in ((["stat", "16", "2.0"], contexts["bumpy"].statistical_outliers(16, 2.0)[0]),
                        (["radius", "0.02", "8"], contexts["bumpy"].radius_outliers(0.02, 8))):
-        r = subprocess.run([exe, str(tmp_path / "P.xyz")] + args, capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0, r.stderr
-        lines = r.stdout.splitlines()
-        n = len(X)
-        assert lines[0] == "removed %d" % (~want).sum()
-        mask = np.array([int(v) for v in lines[1:1 + n]], bool)
-        assert np.array_equal(mask, want)
-        rest = np.array([[float(v) for v in ln.split()] for ln in lines[1 + n:]])
+        heads, (mask,), rest = S.run_points_app(exe, ["outliers"] + args, X)
+        assert heads == ["removed %d" % (~want).sum()]
+        assert len(mask) == len(X) and np.array_equal(mask.astype(bool), want)
         # erased in place, order kept, normals and colours moved with their points
         assert np.array_equal(rest[:, :3].astype(np.float32), X[want]) and (rest[:, 3] == 1.0).all()
         assert np.array_equal(rest[:, 4].astype(np.int64), np.flatnonzero(want))
 
 
 def test_cli_remove_outliers_matches_the_python_path(knn, s4p_lib_built, tmp_path):
-    from super4pcs_amd import build as B, capi
-    delta, overlap, n_s = 0.01, 0.6, 200
-    P, Q, _ = H.small_pair(8000, delta=delta, seed=33)
+    P, Q, _ = H.small_pair(8000, delta=0.01, seed=33)
     P, _ = KH.plant(P, 40)
     Q, _ = KH.plant(Q, 40)
-    KH.write_obj(tmp_path / "P.obj", P); KH.write_obj(tmp_path / "Q.obj", Q)
-    cli = B.build_cli()
-    common = [cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-n", str(n_s), "-t", "1000"]
-    r = subprocess.run(common + ["--remove-outliers", "16", "-m", str(tmp_path / "mat.txt"), "-r", str(tmp_path / "reg.obj")],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    got = np.array([[float(v) for v in ln.split()] for ln in (tmp_path / "mat.txt").read_text().splitlines()[2:6]])
-    # the Python path: filter both clouds, then register with the same options
-    Pk, pm, _ = knn.remove_statistical_outliers(P, k=16, std_ratio=2.0)
-    Qk, qm, _ = knn.remove_statistical_outliers(Q, k=16, std_ratio=2.0)
-    assert 0 < (~pm).sum() < 400 and 0 < (~qm).sum() < 400
-    gm = capi.Matcher(capi.make_options(delta, overlap, n_s))
-    _, M, gQ = gm.compute_transformation(Pk, Qk)
-    print("removed %d / %d\ncli:\n%s\npython:\n%s" % ((~pm).sum(), (~qm).sum(), got, M))
-    assert np.max(np.abs(got - np.asarray(M, np.float64))) <= 1e-5
-    assert "Removed outliers: k 16" in r.stdout + r.stderr
-    # -r: the filtered Q, registered
-    head, body = (tmp_path / "reg.ply").read_bytes().split(b"end_header\n", 1)
-    assert b"element vertex %d\n" % len(Qk) in head
-    assert np.array_equal(np.frombuffer(body, "<f4").reshape(-1, 3), gQ)
+    # the Python path: filter both clouds, then register with the same options; -r: the filtered Q, registered
+    Pk, Qk = S.cli_filter_equals_python(tmp_path, P, Q, ["--remove-outliers", "16"],
+                                        lambda Z: knn.remove_statistical_outliers(Z, k=16, std_ratio=2.0)[0], "Removed outliers: k 16")
+    assert 0 < len(P) - len(Pk) < 400 and 0 < len(Q) - len(Qk) < 400
     # an input with faces is refused
     KH.write_obj(tmp_path / "F.obj", Q[:100], faces=[(1, 2, 3)])
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "F.obj"), "--remove-outliers", "16"], capture_output=True,
+    r = subprocess.run([S.cli(), "-i", str(tmp_path / "P.obj"), str(tmp_path / "F.obj"), "--remove-outliers", "16"], capture_output=True,
                        text=True, timeout=120)
     assert r.returncode == 254 and "faces" in r.stdout + r.stderr

@@ -6,13 +6,13 @@ lidar cloud at the origin and at 1e4, and on 524 289 points where a lane takes f
 lidar pair through Python, the facade and the command line; determinism, numpy against torch, every refusal, and the
 context's other calls after a plane call."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import apps
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 from tests import plane_helpers as PH
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +20,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def pln():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import plane
-    return plane
+    return S.normals_module("plane")
 
 
 @pytest.fixture(scope="module")
@@ -147,10 +144,10 @@ def test_one_multi_trip_size_numpy_and_torch(pln, cpu):
     assert PH.same(ctx.segment(0.01, 1024, 0, 1), (pl, mask, info))
     ctx.close()
     t = pln.Plane(0)
-    t.set_cloud(torch.from_numpy(X).cuda())
+    t.set_cloud(S.to_device(X))
     pt, mt, it = t.segment(0.01, 1024, 0, 1)
     assert mt.is_cuda and mt.dtype == torch.uint8 and PH.same((pt, mt, it), (pl, mask, info))
-    ex = torch.from_numpy(mask).cuda()
+    ex = S.to_device(mask)
     p2, m2, i2 = t.segment(0.01, 256, 1, 1, exclude=ex)
     assert PH.same((p2, m2, i2), cpu.segment(X, 0.01, 256, 1, 1, mask)) and i2["alive"] == len(X) - info["inliers"]
     t.close()
@@ -170,7 +167,6 @@ def test_segment_planes_on_a_box_corner(pln, cpu):
 
 
 def test_lidar_pair_through_python_the_facade_and_the_command_line(pln, cpu, s4p_lib_built, tmp_path):
-    from super4pcs_amd import build as B
     from super4pcs_amd import datasets as D
     P, Q, _ = D.lidar_pair(20000)
     want = [cpu.segment(Z, 0.15, 1024, 0, 1) for Z in (P, Q)]
@@ -180,22 +176,16 @@ def test_lidar_pair_through_python_the_facade_and_the_command_line(pln, cpu, s4p
         kept, keep, planes = pln.remove_planes(Z, 0.15)
         assert np.array_equal(keep, w[1] == 0) and np.array_equal(kept, Z[keep]) and np.array_equal(NH.bits(planes[0]), NH.bits(w[0]))
     # the facade
-    exe = apps.build_app(tmp_path, "plane_app", ("super4pcs_normals",), ("-Werror",))
-    apps.write_xyz(tmp_path / "P.xyz", P)
-    r = subprocess.run([exe, str(tmp_path / "P.xyz"), "0.15", "1024", "1", "1"], capture_output=True, text=True, timeout=apps.TIMEOUT)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.splitlines()
-    n = len(P)
-    assert np.array_equal(NH.bits(np.array(lines[0].split()[1:], np.float32)), NH.bits(want[0][0]))
-    assert lines[1] == "inliers %d" % removed[0] and np.array_equal(np.array(lines[2:2 + n], np.uint8), want[0][1])
-    assert lines[2 + n] == "removed %d planes 1" % removed[0]
-    rest = np.array([[float(v) for v in ln.split()] for ln in lines[3 + n:]], np.float32)
+    heads, (_, got_mask, _), rest = S.run_points_app(S.build_facade_app(tmp_path), ["plane", "0.15", "1024", "1", "1"], P)
+    assert np.array_equal(NH.bits(np.array(heads[0].split()[1:], np.float32)), NH.bits(want[0][0]))
+    assert heads[1] == "inliers %d" % removed[0] and np.array_equal(got_mask, want[0][1])
+    assert heads[2:] == ["removed %d planes 1" % removed[0]]
+    rest = rest.astype(np.float32)
     assert np.array_equal(NH.bits(rest[:, :3]), NH.bits(P[want[0][1] == 0])) and (rest[:, 3] == 1).all()
     assert np.array_equal(rest[:, 4].astype(np.int64), np.flatnonzero(want[0][1] == 0))
     # the command line: both inputs filtered, -r holds the kept points of the second
     apps.write_obj(tmp_path / "P.obj", P); apps.write_obj(tmp_path / "Q.obj", Q)
-    cli = B.build_cli()
-    M, out = apps.run_cli(cli, tmp_path / "P.obj", tmp_path / "Q.obj", 0.05, 0.6, 200, ["--remove-plane", "0.15", "-r", tmp_path / "R.obj"])
+    M, out = apps.run_cli(S.cli(), tmp_path / "P.obj", tmp_path / "Q.obj", 0.05, 0.6, 200, ["--remove-plane", "0.15", "-r", tmp_path / "R.obj"])
     assert "removed %d of input1, %d of input2" % (removed[0], removed[1]) in out, out
     head, body = (tmp_path / "R.ply").read_bytes().split(b"end_header\n", 1)
     assert b"element vertex %d\n" % (len(Q) - removed[1]) in head and len(body) == 12 * (len(Q) - removed[1]) and np.isfinite(M).all()
@@ -206,12 +196,12 @@ def test_two_calls_and_both_forms_give_the_same_bits(pln):
     X = PH.tiny_cloud(2049, seed=4)
     a = pln.segment_plane(X, PH.TINY_DISTANCE, 200, 7, 2)
     b = pln.segment_plane(X, PH.TINY_DISTANCE, 200, 7, 2)
-    t = pln.segment_plane(torch.from_numpy(X).cuda(), PH.TINY_DISTANCE, 200, 7, 2)
+    t = pln.segment_plane(S.to_device(X), PH.TINY_DISTANCE, 200, 7, 2)
     assert PH.same(a, b) and t[1].is_cuda and PH.same(a, t) and a[2]["trial"] >= 0
     assert not PH.same(a, pln.segment_plane(X, PH.TINY_DISTANCE, 200, 8, 0))           # another seed and no refit: another plane
-    pt, lt = pln.segment_planes(torch.from_numpy(X).cuda(), PH.TINY_DISTANCE, 2, 100, 200, 7)
+    pt, lt = pln.segment_planes(S.to_device(X), PH.TINY_DISTANCE, 2, 100, 200, 7)
     pn, ln = pln.segment_planes(X, PH.TINY_DISTANCE, 2, 100, 200, 7)
-    assert lt.is_cuda and lt.dtype == torch.int32 and np.array_equal(lt.cpu().numpy(), ln) and np.array_equal(NH.bits(pt), NH.bits(pn))
+    assert lt.is_cuda and lt.dtype == torch.int32 and np.array_equal(S.to_host(lt), ln) and np.array_equal(NH.bits(pt), NH.bits(pn))
 
 
 def test_other_calls_on_the_context_are_unchanged_after_a_plane_call(pln):

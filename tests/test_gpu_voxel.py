@@ -4,6 +4,7 @@ host entry point (numpy) and the device one (torch), at the block edges of the t
 import numpy as np
 import pytest
 
+from tests import normals_suite as S
 from tests import voxel_helpers as VH
 
 pytestmark = pytest.mark.gpu
@@ -11,10 +12,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(scope="module")
 def vox():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import voxel
-    return voxel
+    return S.normals_module("voxel")
 
 
 @pytest.fixture(scope="module")
@@ -30,8 +28,7 @@ def ctx(vox):
 
 
 def _torch_args(X, A):
-    import torch
-    return torch.from_numpy(X).cuda(), None if A is None else torch.from_numpy(A).cuda()
+    return S.to_device(X), None if A is None else S.to_device(A)
 
 
 @pytest.mark.parametrize("name", list(VH.CASES))
@@ -67,9 +64,8 @@ def test_extent_of_2_to_21_is_accepted_and_one_more_refused(vox, ctx, cpu):
         with pytest.raises(vox.NormalsError) as e:
             ctx.downsample(X, 1.0)
         assert e.value.code == -1 and "%s axis" % "xyz"[axis] in str(e.value) and str(VH.MAX_EXTENT + 1) in str(e.value), str(e.value)
-        import torch
         with pytest.raises(vox.NormalsError) as e:
-            ctx.downsample(torch.from_numpy(X).cuda(), 1.0)
+            ctx.downsample(S.to_device(X), 1.0)
         assert e.value.code == -1
     # a non-finite point does not count towards the extent
     X = np.array([[0, 0, 0], [np.inf, 0, 0], [1e30, np.nan, 0]], np.float32)
@@ -130,7 +126,7 @@ def test_lidar_scene_at_a_multi_trip_size_equals_the_restatement_on_all_rows(vox
         want = cpu.downsample(X, v, A)
         print("lidar %d at %g: m %d, largest voxel %d" % (n, v, len(want[0]), want[2].max()))
         VH.assert_same(ctx.downsample(X, v, A), want, "lidar numpy %g" % v)
-        VH.assert_same(ctx.downsample(torch.from_numpy(X).cuda(), v, torch.from_numpy(A).cuda()), want, "lidar torch %g" % v)
+        VH.assert_same(ctx.downsample(S.to_device(X), v, S.to_device(A)), want, "lidar torch %g" % v)
     assert want[2].max() > 64 * 64
 
 
@@ -170,10 +166,10 @@ def test_one_shot_call_carries_attributes_and_renormalised_normals(vox, cpu):
     VH.assert_same((xyz, a, cnt, vof), (wx, wa[:, :3], wc, wv), "one-shot numpy")
     assert np.array_equal(VH.bits(nrm), VH.bits(wn))
     assert np.allclose(np.linalg.norm(nrm[nrm.any(1)], axis=1), 1, atol=1e-6)
-    t = vox.voxel_downsample(torch.from_numpy(X).cuda(), v, attrs=torch.from_numpy(rgb).cuda(), normals=torch.from_numpy(N).cuda())
+    t = vox.voxel_downsample(S.to_device(X), v, attrs=S.to_device(rgb), normals=S.to_device(N))
     assert all(q.is_cuda for q in t)
     VH.assert_same((t[0], t[1], t[3], t[4]), (wx, wa[:, :3], wc, wv), "one-shot torch")
-    assert np.array_equal(VH.bits(t[2].cpu().numpy()), VH.bits(wn))
+    assert np.array_equal(VH.bits(S.to_host(t[2])), VH.bits(wn))
     # one (n,) channel comes back as (m,); nothing asked for, nothing returned
     one = vox.voxel_downsample(X, v, attrs=rgb[:, 0])
     assert one[1].shape == (len(wx),) and one[2] is None and np.array_equal(VH.bits(one[1]), VH.bits(wa[:, 0]))
@@ -182,26 +178,20 @@ def test_one_shot_call_carries_attributes_and_renormalised_normals(vox, cpu):
 
 
 def test_facade_application_gives_the_python_rows_and_carries_normals_and_colours(vox, tmp_path):
-    import subprocess
     from tests import normals_helpers as NH
     X, v, _ = VH.CASES["duplicates"]()
     rng = np.random.default_rng(21)
     raw = rng.normal(size=(len(X), 3)).astype(np.float32)
     N = NH.point3d_normalise(raw)                         # what Point3D::set_normal stores of the file's values
     rgb = rng.integers(0, 256, size=(len(X), 3)).astype(np.float32)
-    exe = VH.build_app(tmp_path)
-    VH.write_table(tmp_path / "P.txt", X)
-    VH.write_table(tmp_path / "PA.txt", np.concatenate([X, raw, rgb], axis=1))
-    for mode, attrs in (("plain", None), ("attrs", np.concatenate([N, rgb], axis=1))):
+    exe = S.build_facade_app(tmp_path)
+    for mode, attrs, table in (("plain", None, X), ("attrs", np.concatenate([N, rgb], axis=1), np.concatenate([X, raw, rgb], axis=1))):
         xyz, a, _, _, vof = vox.voxel_downsample(X, v, attrs=attrs)
-        r = subprocess.run([exe, str(tmp_path / ("P.txt" if attrs is None else "PA.txt")), "%.9g" % v, mode], capture_output=True, text=True,
-                           timeout=120)
-        assert r.returncode == 0, r.stderr
-        lines = r.stdout.splitlines()
+        heads, (got_vof,), rows = S.run_points_app(exe, ["voxel", "%.9g" % v, mode], table)
         m = len(xyz)
-        assert lines[0] == "m %d" % m and 1 < m < len(X)
-        assert np.array_equal(np.array([int(t) for t in lines[1:1 + len(X)]]), vof)
-        rows = np.array([[float(t) for t in ln.split()] for ln in lines[1 + len(X):]], np.float64).astype(np.float32)
+        assert heads == ["m %d" % m] and 1 < m < len(X)
+        assert np.array_equal(got_vof, vof)
+        rows = rows.astype(np.float32)
         assert rows.shape == (m, 9) and np.array_equal(VH.bits(rows[:, :3]), VH.bits(xyz))
         if attrs is None:
             assert not rows[:, 3:6].any() and (rows[:, 6:] == -1).all()                  # no normal, no colour
@@ -211,31 +201,8 @@ def test_facade_application_gives_the_python_rows_and_carries_normals_and_colour
 
 
 def test_cli_voxel_size_matches_the_python_path(vox, s4p_lib_built, tmp_path):
-    import subprocess
-    from super4pcs_amd import build as B, capi
     from tests import helpers as H
-    delta, overlap, n_s = 0.01, 0.6, 200
-    P, Q, _ = H.small_pair(8000, delta=delta, seed=33)
-    VH.write_obj(tmp_path / "P.obj", P); VH.write_obj(tmp_path / "Q.obj", Q)
-    cli = B.build_cli()
-    v = 0.03
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "-o", str(overlap), "-d", str(delta), "-n", str(n_s),
-                        "-t", "1000", "--voxel-size", str(v), "-m", str(tmp_path / "mat.txt"), "-r", str(tmp_path / "reg.obj")],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    got = np.array([[float(t) for t in ln.split()] for ln in (tmp_path / "mat.txt").read_text().splitlines()[2:6]])
-    # the Python path: downsample both clouds, then register with the same options
-    Pv = vox.voxel_downsample(P, v)[0]
-    Qv = vox.voxel_downsample(Q, v)[0]
+    P, Q, _ = H.small_pair(8000, delta=0.01, seed=33)
+    # the Python path: downsample both clouds, then register with the same options; -r: the downsampled Q, registered: m rows
+    Pv, Qv = S.cli_filter_equals_python(tmp_path, P, Q, ["--voxel-size", "0.03"], lambda Z: vox.voxel_downsample(Z, 0.03)[0], "Voxel grid: edge")
     assert 200 < len(Pv) < len(P) and 200 < len(Qv) < len(Q)
-    gm = capi.Matcher(capi.make_options(delta, overlap, n_s))
-    _, M, gQ = gm.compute_transformation(Pv, Qv)
-    print("kept %d of %d, %d of %d\ncli:\n%s\npython:\n%s" % (len(Pv), len(P), len(Qv), len(Q), got, M))
-    # the matrix file is text of limited precision: the bound tests/test_gpu_outliers.py uses for the same file; the -r file
-    # below holds binary floats and is compared bit for bit
-    assert np.max(np.abs(got - np.asarray(M, np.float64))) <= 1e-5
-    assert "Voxel grid: edge" in r.stdout + r.stderr
-    # -r: the downsampled Q, registered: m rows
-    head, body = (tmp_path / "reg.ply").read_bytes().split(b"end_header\n", 1)
-    assert b"element vertex %d\n" % len(Qv) in head
-    assert np.array_equal(np.frombuffer(body, "<f4").reshape(-1, 3), gQ)

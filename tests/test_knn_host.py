@@ -5,24 +5,18 @@ the GPU tests, the reference statistics, the command line's new flags and the fa
 import ctypes
 import hashlib
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import knn_helpers as KH
 from tests import normals_helpers as NH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import normals_suite as S
 
 
 @pytest.fixture(scope="module")
 def knn():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import knn
-    return knn
+    return S.normals_module("knn")
 
 
 @pytest.fixture(scope="module")
@@ -30,63 +24,32 @@ def cpu(tmp_path_factory):
     return NH.build_cpu(tmp_path_factory.mktemp("knn_cpu"))
 
 
-def _gpu_visible():
-    from tests.conftest import _gpu_visible as g
-    return g()
-
-
-def _declared(header, prefix):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(%s\w+)\s*\(" % prefix, txt)))
-
-
 def test_header_declarations_equal_the_binding_and_the_exports(knn):
-    decl = _declared("s4p_knn.h", "s4p_(?:knn|outliers)_")
-    assert len(decl) == 8 and decl == sorted(knn.SYMBOLS), decl
-    assert not _declared("s4p_knn.h", "s4p_normals_")                       # the new functions carry their own prefixes
-    from super4pcs_amd import normals
-    L = ctypes.CDLL(normals.LIB_PATH)
-    assert not [s for s in decl if not hasattr(L, s)]
-    Lb = knn.load_library()
-    for s in decl:
-        assert getattr(Lb, s).argtypes is not None and getattr(Lb, s).restype is ctypes.c_int32, s
-    exported = subprocess.run(["nm", "-D", "--defined-only", normals.LIB_PATH], capture_output=True, text=True).stdout
-    got = sorted(set(re.findall(r"\b(s4p_(?:knn|outliers)_\w+)", exported)))
-    assert got == decl, got
+    # the new functions carry their own prefixes
+    _, decl, _ = S.check_header("s4p_knn.h", "s4p_(?:knn|outliers)_", knn.SYMBOLS, knn.load_library(), closed_prefixes="s4p_normals_")
+    assert len(decl) == 8
     assert ctypes.sizeof(knn.OutlierStats) == 40
 
 
 def test_the_normals_header_and_its_symbol_list_are_unchanged(knn):
     from super4pcs_amd import normals
-    assert _declared("s4p_normals.h", "s4p_normals_") == sorted(normals.SYMBOLS) and len(normals.SYMBOLS) == 10
-    digest = hashlib.sha256(open(os.path.join(ROOT, "include", "s4p_normals.h"), "rb").read()).hexdigest()
+    assert S.declared("s4p_normals.h", "s4p_normals_") == sorted(normals.SYMBOLS) and len(normals.SYMBOLS) == 10
+    digest = hashlib.sha256(open(os.path.join(S.INCLUDE, "s4p_normals.h"), "rb").read()).hexdigest()
     # the header as of the scale limit in its Limits paragraph: a comment grew, no declaration changed
     assert digest == "f5f72bed94da6af3e2c3cfa3c129249e091cc62eff74a555a0d401bb0a9d2f22", digest
     assert not [s for s in knn.SYMBOLS if s.startswith("s4p_normals_")]
 
 
 def test_new_kernels_live_in_the_library_namespace(knn):
-    from super4pcs_amd import normals
-    out = subprocess.run(["nm", "-C", normals.LIB_PATH], capture_output=True, text=True).stdout
-    for k in (8, 16, 32):
-        for mode in (0, 1, 2):
-            assert re.search(r"s4p_nrm::k_knn_search<%d, %d>" % (k, mode), out), (k, mode)
-        assert re.search(r"s4p_nrm::k_knn_normals<%d>" % k, out), k
-    for name in ("k_sor_rows<0>", "k_sor_rows<1>", "k_sor_reduce", "k_sor_mask"):
-        assert "s4p_nrm::" + name in out, name
+    S.check_kernels_in_namespace(["k_knn_search<%d, %d>" % (k, mode) for k in (8, 16, 32) for mode in (0, 1, 2)] +
+                                 ["k_knn_normals<%d>" % k for k in (8, 16, 32)] + ["k_sor_rows<0>", "k_sor_rows<1>", "k_sor_reduce", "k_sor_mask"])
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_create_fails_loudly_without_a_device(knn):
-    with pytest.raises(knn.NormalsError) as e:
-        knn.Knn(0)
-    assert e.value.code == -2 and "no HIP device" in str(e.value)
     X = np.zeros((10, 3), np.float32)
-    for call in (lambda: knn.knn(X, 4), lambda: knn.remove_statistical_outliers(X), lambda: knn.remove_radius_outliers(X, 0.1, 2)):
-        with pytest.raises(knn.NormalsError) as e:
-            call()
-        assert e.value.code == -2
+    S.check_no_device(knn.NormalsError, (lambda: knn.Knn(0), lambda: knn.knn(X, 4), lambda: knn.remove_statistical_outliers(X),
+                                         lambda: knn.remove_radius_outliers(X, 0.1, 2)))
 
 
 @pytest.mark.parametrize("n", KH.TINY_N)
@@ -134,62 +97,29 @@ def test_planted_points_are_outliers_of_the_reference(cpu):
 
 
 def test_cli_remove_outliers_flags(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--remove-outliers", "0"], ["--remove-outliers", "33"], ["--remove-outliers", "1.5"], ["--remove-outliers", "x"],
-                ["--remove-outliers", ""], ["--remove-outliers-std", "2.0"], ["--remove-outliers", "16", "--remove-outliers-std", "-1"],
-                ["--remove-outliers", "16", "--remove-outliers-std", "nan"], ["--remove-outliers", "16", "--remove-outliers-std", "2x"]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--remove-outliers" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--remove-outliers", "1"], ["--remove-outliers", "32", "--remove-outliers-std", "0"],
-                 ["--remove-outliers-std", "1.5", "--remove-outliers", "16"],
-                 ["--remove-outliers", "16", "--estimate-normals", "16", "--icp", "5", "--icp-metric", "gicp"]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--remove-outliers", "0"], ["--remove-outliers", "33"], ["--remove-outliers", "1.5"], ["--remove-outliers", "x"],
+             ["--remove-outliers", ""], ["--remove-outliers-std", "2.0"], ["--remove-outliers", "16", "--remove-outliers-std", "-1"],
+             ["--remove-outliers", "16", "--remove-outliers-std", "nan"], ["--remove-outliers", "16", "--remove-outliers-std", "2x"]),
+        good=(["--remove-outliers", "1"], ["--remove-outliers", "32", "--remove-outliers-std", "0"],
+              ["--remove-outliers-std", "1.5", "--remove-outliers", "16"],
+              ["--remove-outliers", "16", "--estimate-normals", "16", "--icp", "5", "--icp-metric", "gicp"]),
+        usage_word="--remove-outliers")
 
 
 def test_cli_refuses_an_input_with_faces(tmp_path):
-    """Faces index the vertex list: refused before any device work, with exit status -2."""
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts)
-    KH.write_obj(tmp_path / "Q.obj", pts, faces=[(1, 2, 3), (2, 3, 4)])
-    for first, second in (("P.obj", "Q.obj"), ("Q.obj", "P.obj")):
-        r = subprocess.run([cli, "-i", str(tmp_path / first), str(tmp_path / second), "--remove-outliers", "16", "-m", str(tmp_path / "m.txt")],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 254 and "faces" in r.stdout + r.stderr, (r.returncode, r.stdout, r.stderr)
-        assert not (tmp_path / "m.txt").exists()
+    S.check_cli_refuses_faces(tmp_path, ["--remove-outliers", "16"])
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_cli_valid_command_fails_with_the_device_error_without_a_gpu(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts); KH.write_obj(tmp_path / "Q.obj", pts)
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "--remove-outliers", "16", "-m", str(tmp_path / "m.txt")],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 254, (r.returncode, r.stdout, r.stderr)
-    assert "Unknown flag" not in r.stderr and "RemoveOutliers (MI355X)" in r.stdout + r.stderr and "no HIP device" in r.stdout + r.stderr
+    S.check_cli_no_device(tmp_path, ["--remove-outliers", "16"], "RemoveOutliers (MI355X)")
 
 
 @pytest.mark.parametrize("eigen", [False, True])
 def test_facade_header_compiles_with_and_without_eigen(knn, tmp_path, eigen):
-    extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text('#include "super4pcs/algorithms/outliers.h"\n#ifdef S4P_HAVE_EIGEN\n#error have\n#else\n#error none\n#endif\n')
-    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include")] + extra + [str(probe)],
-                       capture_output=True, text=True)
-    assert re.search(r"#error (have|none)", r.stderr).group(1) == ("have" if eigen else "none"), r.stderr
-    exe = KH.build_app(tmp_path, extra)
-    assert os.path.exists(exe)
-    if not _gpu_visible():
-        np.savetxt(tmp_path / "P.xyz", np.random.default_rng(2).uniform(size=(20, 3)), fmt="%.6f")
-        r = subprocess.run([exe, str(tmp_path / "P.xyz"), "stat", "8", "2.0"], capture_output=True, text=True)
-        assert r.returncode == 1 and "no HIP device" in r.stderr
-    for bad in (["stat", "0", "2.0"], ["stat", "33", "2.0"], ["stat", "8", "-1"], ["radius", "-1", "4"], ["radius", "0.1", "33"]):
-        np.savetxt(tmp_path / "P.xyz", np.random.default_rng(2).uniform(size=(20, 3)), fmt="%.6f")
-        r = subprocess.run([exe, str(tmp_path / "P.xyz")] + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "RemoveOutliers:" in r.stderr, (bad, r.stderr)
+    S.check_facade_header(tmp_path, "outliers.h", eigen, "outliers", np.random.default_rng(2).uniform(size=(20, 3)),
+                          no_device_args=["stat", "8", "2.0"], no_device_text=("no HIP device",),
+                          bad_args=(["stat", "0", "2.0"], ["stat", "33", "2.0"], ["stat", "8", "-1"], ["radius", "-1", "4"], ["radius", "0.1", "33"]),
+                          bad_text="RemoveOutliers:")

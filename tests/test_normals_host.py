@@ -1,7 +1,6 @@
 """Normal estimation (include/s4p_normals.h, libsuper4pcs_normals.so) on the host: exports and binding, the library's
 namespace, the loud failure without a device, the CPU restatement's neighbour sets against a numpy lexsort brute force and
 its normals against numpy eigh, the command line's new flags and the facade header."""
-import ctypes
 import os
 import re
 import subprocess
@@ -9,18 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import apps
 from tests import normals_helpers as NH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import normals_suite as S
 
 
 @pytest.fixture(scope="module")
 def nrm():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import normals
-    return normals
+    return S.normals_module("normals")
 
 
 @pytest.fixture(scope="module")
@@ -28,43 +22,25 @@ def cpu(tmp_path_factory):
     return NH.build_cpu(tmp_path_factory.mktemp("normals_cpu"))
 
 
-def _gpu_visible():
-    from tests.conftest import _gpu_visible as g
-    return g()
-
-
 def test_header_declarations_equal_the_binding_and_the_exports(nrm):
-    txt = open(os.path.join(ROOT, "include", "s4p_normals.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    decl = sorted(set(re.findall(r"\b(s4p_normals_\w+)\s*\(", txt)))
-    assert decl == sorted(nrm.SYMBOLS), decl
-    L = ctypes.CDLL(nrm.LIB_PATH)
-    assert not [s for s in decl if not hasattr(L, s)]
-    Lb = nrm.load_library()
-    for s in decl:
-        assert getattr(Lb, s).argtypes is not None, s
+    S.check_header("s4p_normals.h", "s4p_normals_", nrm.SYMBOLS, nrm.load_library(), restype=None)   # create returns the handle, last_error a string
 
 
 def test_kernels_live_in_their_own_namespace(nrm):
     dyn = subprocess.run(["nm", "-D", "--defined-only", nrm.LIB_PATH], capture_output=True, text=True).stdout
     assert "_ZN3s4p" not in dyn
-    out = subprocess.run(["nm", "-C", nrm.LIB_PATH], capture_output=True, text=True).stdout
+    out = S.check_kernels_in_namespace(("k_knn_normals<8>", "k_knn_normals<32>"))
     assert "s4p_icp::" not in out
     for k in ("k_normals", "k_match", "k_final", "k_match_plane", "k_final_plane", "k_stats"):
         assert not re.search(r"\b%s\b" % k, out), k
-    assert re.search(r"s4p_nrm::k_knn_normals<8>", out) and re.search(r"s4p_nrm::k_knn_normals<32>", out)
     # only the HIP runtime (and the C / C++ runtimes) are linked
     needed = subprocess.run(["readelf", "-d", nrm.LIB_PATH], capture_output=True, text=True).stdout
     assert "super4pcs" not in needed
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_create_fails_loudly_without_a_device(nrm):
-    with pytest.raises(nrm.NormalsError) as e:
-        nrm.Normals(0)
-    assert e.value.code == -2 and "no HIP device" in str(e.value)
-    with pytest.raises(nrm.NormalsError):
-        nrm.estimate_normals(np.zeros((10, 3), np.float32))
+    S.check_no_device(nrm.NormalsError, (lambda: nrm.Normals(0), lambda: nrm.estimate_normals(np.zeros((10, 3), np.float32))))
 
 
 def _cloud_with_ties(rng, n):
@@ -129,36 +105,22 @@ def test_restatement_zero_normals(cpu):
 
 
 def test_cli_estimate_normals_flags(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--estimate-normals", "2"], ["--estimate-normals", "33"], ["--estimate-normals", "16.5"], ["--estimate-normals", "x"],
-                ["--estimate-normals", ""], ["--estimate-normals", "16", "--estimate-normals-radius", "0"],
-                ["--estimate-normals", "16", "--estimate-normals-radius", "-1"],
-                ["--estimate-normals", "16", "--estimate-normals-radius", "nan"],
-                ["--estimate-normals", "16", "--estimate-normals-radius", "0.1x"], ["--estimate-normals-radius", "0.1"]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--estimate-normals" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--estimate-normals", "3"], ["--estimate-normals", "32", "--estimate-normals-radius", "0.05"],
-                 ["--estimate-normals-radius", "0.05", "--estimate-normals", "16"]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--estimate-normals", "2"], ["--estimate-normals", "33"], ["--estimate-normals", "16.5"], ["--estimate-normals", "x"],
+             ["--estimate-normals", ""], ["--estimate-normals", "16", "--estimate-normals-radius", "0"],
+             ["--estimate-normals", "16", "--estimate-normals-radius", "-1"],
+             ["--estimate-normals", "16", "--estimate-normals-radius", "nan"],
+             ["--estimate-normals", "16", "--estimate-normals-radius", "0.1x"], ["--estimate-normals-radius", "0.1"]),
+        good=(["--estimate-normals", "3"], ["--estimate-normals", "32", "--estimate-normals-radius", "0.05"],
+              ["--estimate-normals-radius", "0.05", "--estimate-normals", "16"]),
+        usage_word="--estimate-normals")
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_cli_valid_command_fails_with_the_device_error_without_a_gpu(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    for name in ("P.obj", "Q.obj"):
-        with open(tmp_path / name, "w") as f:
-            for p in np.random.default_rng(1).uniform(size=(50, 3)):
-                f.write("v %.6f %.6f %.6f\n" % tuple(p))
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "--estimate-normals", "16", "-a", "20",
-                        "-m", str(tmp_path / "m.txt")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 254, (r.returncode, r.stdout, r.stderr)
-    assert "Unknown flag" not in r.stderr and "EstimateNormals (MI355X)" in r.stdout + r.stderr and "no HIP device" in r.stdout + r.stderr
+    S.check_cli_no_device(tmp_path, ["--estimate-normals", "16", "-a", "20"], "EstimateNormals (MI355X)")
 
 
 def test_facade_header_compiles_in_a_small_app(nrm, tmp_path):
-    exe = apps.build_app(tmp_path, "normals_app", ("super4pcs_normals",), ("-Werror",))
-    assert os.path.exists(exe)
+    assert os.path.exists(S.build_facade_app(tmp_path))

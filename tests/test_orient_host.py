@@ -4,27 +4,18 @@ the binding and the exports, the new kernels in the library's namespace, the lou
 outward) and on two separate clusters, the simple call's expression, the command line's new flags and the facade header with
 and without Eigen."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from tests import apps
-from tests import knn_helpers as KH
 from tests import normals_helpers as NH
+from tests import normals_suite as S
 from tests import orient_helpers as OH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def nrm():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import normals
-    return normals
+    return S.normals_module("normals")
 
 
 @pytest.fixture(scope="module")
@@ -32,41 +23,24 @@ def cpu(tmp_path_factory):
     return NH.build_cpu(tmp_path_factory.mktemp("orient_cpu"))
 
 
-def _gpu_visible():
-    from tests.conftest import _gpu_visible as g
-    return g()
-
-
 def test_header_declarations_equal_the_binding_and_the_exports(nrm):
-    txt = open(os.path.join(ROOT, "include", "s4p_normals_orient.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    decl = sorted(set(re.findall(r"\b(s4p_orient_\w+)\s*\(", txt)))
-    assert len(decl) == 4 and decl == sorted(nrm.ORIENT_SYMBOLS), decl
-    assert not re.findall(r"\b(s4p_(?:normals|knn|outliers|voxel)_\w+)\s*\(", txt)      # the older prefixes stay closed sets
-    L = nrm.load_orient()
-    for s in decl:
-        assert getattr(L, s).argtypes is not None and getattr(L, s).restype is ctypes.c_int32, s
-    exported = subprocess.run(["nm", "-D", "--defined-only", nrm.LIB_PATH], capture_output=True, text=True).stdout
-    assert sorted(set(re.findall(r"\b(s4p_orient_\w+)", exported))) == decl
+    txt, decl, _ = S.check_header("s4p_normals_orient.h", "s4p_orient_", nrm.ORIENT_SYMBOLS, nrm.load_orient(),
+                                  closed_prefixes="s4p_(?:normals|knn|outliers|voxel)_")
+    assert len(decl) == 4
     assert ctypes.sizeof(nrm.OrientStats) == 32
     assert (nrm.ORIENT_OUTWARD, nrm.ORIENT_VIEWPOINT) == (0, 1) and "S4P_ORIENT_ERR_INTERNAL (-8)" in txt and nrm.ERR_NAMES[-8] == "INTERNAL"
 
 
 def test_new_kernels_live_in_the_library_namespace(nrm):
-    out = subprocess.run(["nm", "-C", nrm.LIB_PATH], capture_output=True, text=True).stdout
-    for name in ("k_orient_edges", "k_orient_min<0>", "k_orient_min<1>", "k_orient_hook", "k_orient_jump", "k_orient_anchor",
-                 "k_orient_anchor_flip", "k_orient_apply", "k_orient_towards"):
-        assert "s4p_nrm::" + name in out, name
-    assert not re.search(r"(?<!s4p_nrm::)(?<!__device_stub__)\bk_orient_\w+", out)
+    S.check_kernels_in_namespace(("k_orient_edges", "k_orient_min<0>", "k_orient_min<1>", "k_orient_hook", "k_orient_jump", "k_orient_anchor",
+                                  "k_orient_anchor_flip", "k_orient_apply", "k_orient_towards"),
+                                 stray=r"(?<!s4p_nrm::)(?<!__device_stub__)\bk_orient_\w+")
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_calls_fail_loudly_without_a_device(nrm):
     X = np.zeros((10, 3), np.float32)
-    for call in (lambda: nrm.orient_normals(X, X), lambda: nrm.estimate_normals(X, orient="outward")):
-        with pytest.raises(nrm.NormalsError) as e:
-            call()
-        assert e.value.code == -2 and "no HIP device" in str(e.value)
+    S.check_no_device(nrm.NormalsError, (lambda: nrm.orient_normals(X, X), lambda: nrm.estimate_normals(X, orient="outward")))
     with pytest.raises(ValueError):
         nrm.estimate_normals(X, queries=X, orient="outward")
     with pytest.raises(ValueError):
@@ -141,52 +115,35 @@ def test_towards_is_one_expression():
 
 
 def test_cli_orient_flags(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--orient-normals", "8"],                                                      # needs --estimate-normals
-                ["--estimate-normals", "16", "--orient-viewpoint", "0,0,0"],                    # needs --orient-normals
-                ["--orient-viewpoint", "0,0,0"],
-                ["--estimate-normals", "16", "--orient-normals", "0"], ["--estimate-normals", "16", "--orient-normals", "33"],
-                ["--estimate-normals", "16", "--orient-normals", "8.5"], ["--estimate-normals", "16", "--orient-normals", "x"],
-                ["--estimate-normals", "16", "--orient-normals", ""], ["--estimate-normals", "16", "--orient-normals"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,0"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,0,0,0"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,0,nan"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,inf,0"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0 0 0"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "1e39,0,0"],
-                ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", ""]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--orient-normals k" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--estimate-normals", "16", "--orient-normals", "1"], ["--orient-normals", "32", "--estimate-normals", "3"],
-                 ["--orient-viewpoint", "0,-1.5,2e3", "--orient-normals", "8", "--estimate-normals", "16"],
-                 ["--estimate-normals", "16", "--orient-normals", "8", "--icp", "10", "--icp-normal-angle", "60"]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
-    r = subprocess.run(base + ["-h"], capture_output=True, text=True)
-    assert r.stderr.index("--icp-starts K") < r.stderr.index("--orient-normals k")       # the older usage lines come first
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--orient-normals", "8"],                                                      # needs --estimate-normals
+             ["--estimate-normals", "16", "--orient-viewpoint", "0,0,0"],                    # needs --orient-normals
+             ["--orient-viewpoint", "0,0,0"],
+             ["--estimate-normals", "16", "--orient-normals", "0"], ["--estimate-normals", "16", "--orient-normals", "33"],
+             ["--estimate-normals", "16", "--orient-normals", "8.5"], ["--estimate-normals", "16", "--orient-normals", "x"],
+             ["--estimate-normals", "16", "--orient-normals", ""], ["--estimate-normals", "16", "--orient-normals"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,0"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,0,0,0"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,0,nan"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0,inf,0"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "0 0 0"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", "1e39,0,0"],
+             ["--estimate-normals", "16", "--orient-normals", "8", "--orient-viewpoint", ""]),
+        good=(["--estimate-normals", "16", "--orient-normals", "1"], ["--orient-normals", "32", "--estimate-normals", "3"],
+              ["--orient-viewpoint", "0,-1.5,2e3", "--orient-normals", "8", "--estimate-normals", "16"],
+              ["--estimate-normals", "16", "--orient-normals", "8", "--icp", "10", "--icp-normal-angle", "60"]),
+        usage_word="--orient-normals k", usage_order=("--icp-starts K", "--orient-normals k"))
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_cli_valid_command_fails_with_the_device_error_without_a_gpu(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts); KH.write_obj(tmp_path / "Q.obj", pts)
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "--estimate-normals", "16", "--orient-normals", "8",
-                        "-m", str(tmp_path / "m.txt")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 254 and "Unknown flag" not in r.stderr and "no HIP device" in r.stdout + r.stderr, (r.returncode, r.stdout, r.stderr)
+    S.check_cli_no_device(tmp_path, ["--estimate-normals", "16", "--orient-normals", "8"])
 
 
 @pytest.mark.parametrize("eigen", [False, True])
 def test_facade_header_compiles_with_and_without_eigen(nrm, tmp_path, eigen):
-    extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
-    exe = apps.build_app(tmp_path, "orient_app", ("super4pcs_normals",), ["-Werror"] + extra)
-    apps.write_xyz(tmp_path / "PN.txt", np.random.default_rng(2).uniform(0.1, 1, size=(20, 6)))
-    if not _gpu_visible():
-        r = subprocess.run([exe, str(tmp_path / "PN.txt"), "8", "-1"], capture_output=True, text=True)
-        assert r.returncode == 1 and "OrientNormals (MI355X)" in r.stderr and "no HIP device" in r.stderr
-    for bad in (["0", "-1"], ["33", "-1"], ["8", "nan"], ["8", "-1", "0", "nan", "0"], ["8", "-1", "inf", "0", "0"]):
-        r = subprocess.run([exe, str(tmp_path / "PN.txt")] + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "OrientNormals:" in r.stderr, (bad, r.stderr)
+    S.check_facade_header(tmp_path, "normals.h", eigen, "orient", np.random.default_rng(2).uniform(0.1, 1, size=(20, 6)),
+                          no_device_args=["8", "-1"], no_device_text=("OrientNormals (MI355X)", "no HIP device"),
+                          bad_args=(["0", "-1"], ["33", "-1"], ["8", "nan"], ["8", "-1", "0", "nan", "0"], ["8", "-1", "inf", "0", "0"]),
+                          bad_text="OrientNormals:")

@@ -11,19 +11,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import apps
-from tests import knn_helpers as KH
+from tests import normals_suite as S
 from tests import plane_helpers as PH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def pln():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import plane
-    return plane
+    return S.normals_module("plane")
 
 
 @pytest.fixture(scope="module")
@@ -31,23 +25,11 @@ def cpu(tmp_path_factory):
     return PH.build_cpu(tmp_path_factory.mktemp("plane_cpu"))
 
 
-def _gpu_visible():
-    from tests.conftest import _gpu_visible as g
-    return g()
-
-
 def test_header_declarations_equal_the_binding_and_the_exports(pln):
-    from super4pcs_amd import cluster, knn, normals, voxel
-    txt = open(os.path.join(ROOT, "include", "s4p_plane.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    decl = sorted(set(re.findall(r"\b(s4p_plane_\w+)\s*\(", txt)))
-    assert len(decl) == 2 and decl == sorted(pln.SYMBOLS), decl
-    assert not re.findall(r"\b(s4p_(?:normals|knn|outliers|voxel|orient|cluster)_\w+)\s*\(", txt)      # the older prefixes stay closed sets
-    L = pln.load_library()
-    for s in decl:
-        assert getattr(L, s).argtypes is not None and getattr(L, s).restype is ctypes.c_int32, s
-    exported = subprocess.run(["nm", "-D", "--defined-only", normals.LIB_PATH], capture_output=True, text=True).stdout
-    assert sorted(set(re.findall(r"\b(s4p_plane_\w+)", exported))) == decl
+    from super4pcs_amd import cluster, knn, voxel
+    txt, decl, exported = S.check_header("s4p_plane.h", "s4p_plane_", pln.SYMBOLS, pln.load_library(),
+                                         closed_prefixes="s4p_(?:normals|knn|outliers|voxel|orient|cluster)_")
+    assert len(decl) == 2
     # nothing new under the older prefixes: the exports are the ones their bindings list
     older = set(re.findall(r"\b(s4p_(?:normals|knn|outliers|voxel|cluster)_\w+)", exported))
     known = set(knn.SYMBOLS) | set(voxel.SYMBOLS) | set(cluster.SYMBOLS)
@@ -64,25 +46,20 @@ def test_struct_sizes_are_pinned(pln, tmp_path):
     probe = tmp_path / "sizes.c"
     probe.write_text('#include <stddef.h>\n#include "s4p_plane.h"\n_Static_assert(sizeof(s4p_plane_options) == 24, "options");\n'
                      '_Static_assert(sizeof(s4p_plane_result) == 56, "result");\n_Static_assert(offsetof(s4p_plane_result, trial) == 48, "trial");\n')
-    r = subprocess.run(["gcc", "-std=c11", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(probe)], capture_output=True, text=True)
+    r = subprocess.run(["gcc", "-std=c11", "-fsyntax-only", "-I" + S.INCLUDE, str(probe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
 
 def test_new_kernels_live_in_the_library_namespace(pln):
-    from super4pcs_amd import normals
-    out = subprocess.run(["nm", "-C", normals.LIB_PATH], capture_output=True, text=True).stdout
-    for name in ("k_plane_candidates", "k_plane_count", "k_plane_argmax", "k_plane_mask", "k_plane_moments", "k_plane_refit"):
-        assert "s4p_nrm::" + name in out, name
-    assert not re.search(r"(?<!s4p_nrm::)(?<!__device_stub__)\bk_plane_\w+", out)
+    S.check_kernels_in_namespace(("k_plane_candidates", "k_plane_count", "k_plane_argmax", "k_plane_mask", "k_plane_moments", "k_plane_refit"),
+                                 stray=r"(?<!s4p_nrm::)(?<!__device_stub__)\bk_plane_\w+")
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_calls_fail_loudly_without_a_device(pln):
     X = np.zeros((10, 3), np.float32)
-    for call in (lambda: pln.segment_plane(X, 0.1), lambda: pln.segment_planes(X, 0.1), lambda: pln.remove_planes(X, 0.1), lambda: pln.Plane(0)):
-        with pytest.raises(pln.NormalsError) as e:
-            call()
-        assert e.value.code == -2 and "no HIP device" in str(e.value)
+    S.check_no_device(pln.NormalsError, (lambda: pln.segment_plane(X, 0.1), lambda: pln.segment_planes(X, 0.1), lambda: pln.remove_planes(X, 0.1),
+                                         lambda: pln.Plane(0)))
 
 
 def test_splitmix_statement_equals_the_published_stream():
@@ -176,74 +153,42 @@ def test_peeling_stops_at_the_first_small_plane_and_labels_in_order(pln, cpu):
 
 
 def test_cli_remove_plane_flags(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--remove-plane-trials", "64"], ["--remove-plane-count", "2"],                                  # both need --remove-plane
-                ["--remove-plane", "-0.1"], ["--remove-plane", "nan"], ["--remove-plane", "inf"], ["--remove-plane", "1e39"],
-                ["--remove-plane", "0.1x"], ["--remove-plane", ""], ["--remove-plane"],
-                ["--remove-plane", "0.1", "--remove-plane-trials", "0"], ["--remove-plane", "0.1", "--remove-plane-trials", "-3"],
-                ["--remove-plane", "0.1", "--remove-plane-trials", "4.5"], ["--remove-plane", "0.1", "--remove-plane-trials", "x"],
-                ["--remove-plane", "0.1", "--remove-plane-trials", ""], ["--remove-plane", "0.1", "--remove-plane-trials"],
-                ["--remove-plane", "0.1", "--remove-plane-trials", "1048577"],
-                ["--remove-plane", "0.1", "--remove-plane-count", "0"], ["--remove-plane", "0.1", "--remove-plane-count", "1.5"],
-                ["--remove-plane", "0.1", "--remove-plane-count", ""], ["--remove-plane", "0.1", "--remove-plane-count"],
-                ["--remove-plane", "0.1", "--remove-plane-count", "3000000000"]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--remove-plane d" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--remove-plane", "0.15"], ["--remove-plane-trials", "1048576", "--remove-plane", "1.5e-1"], ["--remove-plane", "0"],
-                 ["--remove-plane", "0.5", "--remove-plane-trials", "1", "--remove-plane-count", "3"],
-                 ["--remove-outliers", "16", "--voxel-size", "0.01", "--remove-plane", "0.15", "--cluster-eps", "0.03", "--estimate-normals", "16"]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
-    r = subprocess.run(base + ["-h"], capture_output=True, text=True)
-    assert r.stderr.index("--cluster-eps e") < r.stderr.index("--remove-plane d")       # the older usage lines come first
-    src = open(os.path.join(ROOT, "demos", "Super4PCS", "super4pcs_cli.cc")).read()
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--remove-plane-trials", "64"], ["--remove-plane-count", "2"],                                  # both need --remove-plane
+             ["--remove-plane", "-0.1"], ["--remove-plane", "nan"], ["--remove-plane", "inf"], ["--remove-plane", "1e39"],
+             ["--remove-plane", "0.1x"], ["--remove-plane", ""], ["--remove-plane"],
+             ["--remove-plane", "0.1", "--remove-plane-trials", "0"], ["--remove-plane", "0.1", "--remove-plane-trials", "-3"],
+             ["--remove-plane", "0.1", "--remove-plane-trials", "4.5"], ["--remove-plane", "0.1", "--remove-plane-trials", "x"],
+             ["--remove-plane", "0.1", "--remove-plane-trials", ""], ["--remove-plane", "0.1", "--remove-plane-trials"],
+             ["--remove-plane", "0.1", "--remove-plane-trials", "1048577"],
+             ["--remove-plane", "0.1", "--remove-plane-count", "0"], ["--remove-plane", "0.1", "--remove-plane-count", "1.5"],
+             ["--remove-plane", "0.1", "--remove-plane-count", ""], ["--remove-plane", "0.1", "--remove-plane-count"],
+             ["--remove-plane", "0.1", "--remove-plane-count", "3000000000"]),
+        good=(["--remove-plane", "0.15"], ["--remove-plane-trials", "1048576", "--remove-plane", "1.5e-1"], ["--remove-plane", "0"],
+              ["--remove-plane", "0.5", "--remove-plane-trials", "1", "--remove-plane-count", "3"],
+              ["--remove-outliers", "16", "--voxel-size", "0.01", "--remove-plane", "0.15", "--cluster-eps", "0.03", "--estimate-normals", "16"]),
+        usage_word="--remove-plane d", usage_order=("--cluster-eps e", "--remove-plane d"))
+    src = open(os.path.join(S.ROOT, "demos", "Super4PCS", "super4pcs_cli.cc")).read()
     assert "[--remove-plane d] [--remove-plane-trials T] [--remove-plane-count K]" in src.split("#include")[0]
 
 
 def test_cli_refuses_an_input_with_faces(tmp_path):
-    """Faces index the vertex list: refused before any device work, with exit status -2 and the flag's name."""
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts)
-    KH.write_obj(tmp_path / "Q.obj", pts, faces=[(1, 2, 3), (2, 3, 4)])
-    for first, second in (("P.obj", "Q.obj"), ("Q.obj", "P.obj")):
-        r = subprocess.run([cli, "-i", str(tmp_path / first), str(tmp_path / second), "--remove-plane", "0.1", "-m", str(tmp_path / "m.txt")],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 254 and "--remove-plane" in r.stdout + r.stderr and "faces" in r.stdout + r.stderr, (r.returncode, r.stdout, r.stderr)
-        assert not (tmp_path / "m.txt").exists()
+    S.check_cli_refuses_faces(tmp_path, ["--remove-plane", "0.1"])
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_cli_valid_command_fails_with_the_device_error_without_a_gpu(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts); KH.write_obj(tmp_path / "Q.obj", pts)
-    r = subprocess.run([cli, "-i", str(tmp_path / "P.obj"), str(tmp_path / "Q.obj"), "--remove-plane", "0.2", "--remove-plane-trials", "64", "-m",
-                        str(tmp_path / "m.txt")], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 254, (r.returncode, r.stdout, r.stderr)
-    assert "Unknown flag" not in r.stderr and "RemovePlanes (MI355X)" in r.stdout + r.stderr and "no HIP device" in r.stdout + r.stderr
+    S.check_cli_no_device(tmp_path, ["--remove-plane", "0.2", "--remove-plane-trials", "64"], "RemovePlanes (MI355X)")
 
 
 @pytest.mark.parametrize("eigen", [False, True])
 def test_facade_header_compiles_with_and_without_eigen(pln, tmp_path, eigen):
-    extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text('#include "super4pcs/algorithms/plane.h"\n#ifdef S4P_HAVE_EIGEN\n#error have\n#else\n#error none\n#endif\n')
-    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include")] + extra + [str(probe)],
-                       capture_output=True, text=True)
-    assert re.search(r"#error (have|none)", r.stderr).group(1) == ("have" if eigen else "none"), r.stderr
-    exe = apps.build_app(tmp_path, "plane_app", ("super4pcs_normals",), ["-Werror"] + extra)
-    np.savetxt(tmp_path / "P.xyz", np.random.default_rng(2).uniform(size=(20, 3)), fmt="%.6f")
-    if not _gpu_visible():
-        r = subprocess.run([exe, str(tmp_path / "P.xyz"), "0.2", "64", "1", "1"], capture_output=True, text=True)
-        assert r.returncode == 1 and "SegmentPlane (MI355X)" in r.stderr and "no HIP device" in r.stderr
-    for bad in (["-1", "64", "1", "1"], ["nan", "64", "1", "1"], ["inf", "64", "1", "1"], ["1e39", "64", "1", "1"], ["0.2", "0", "1", "1"],
-                ["0.2", "1048577", "1", "1"], ["0.2", "64", "-1", "1"], ["0.2", "64", "17", "1"]):
-        r = subprocess.run([exe, str(tmp_path / "P.xyz")] + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "SegmentPlane:" in r.stderr, (bad, r.stderr)
-    r = subprocess.run([exe, str(tmp_path / "P.xyz"), "0.2", "64", "1", "0"], capture_output=True, text=True)
+    exe, path = S.check_facade_header(
+        tmp_path, "plane.h", eigen, "plane", np.random.default_rng(2).uniform(size=(20, 3)),
+        no_device_args=["0.2", "64", "1", "1"], no_device_text=("SegmentPlane (MI355X)", "no HIP device"),
+        bad_args=(["-1", "64", "1", "1"], ["nan", "64", "1", "1"], ["inf", "64", "1", "1"], ["1e39", "64", "1", "1"], ["0.2", "0", "1", "1"],
+                  ["0.2", "1048577", "1", "1"], ["0.2", "64", "-1", "1"], ["0.2", "64", "17", "1"]),
+        bad_text="SegmentPlane:")
+    r = subprocess.run([exe, "plane", path, "0.2", "64", "1", "0"], capture_output=True, text=True)
     assert r.returncode == 1 and "count must be at least 1" in r.stderr

@@ -2,25 +2,19 @@
 the new kernels in the library's namespace, the loud failure without a device, the restatement against a plain Python
 dictionary implementation on the tiny shapes of the GPU tests, a crafted voxel on which the order of the sum shows,
 refine_multiscale's argument checks, the command line's new flag and the facade header with and without Eigen."""
-import ctypes
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
+from tests import normals_suite as S
 from tests import voxel_helpers as VH
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def voxel():
-    from super4pcs_amd import build as B
-    B.build_normals()
-    from super4pcs_amd import voxel
-    return voxel
+    return S.normals_module("voxel")
 
 
 @pytest.fixture(scope="module")
@@ -28,27 +22,13 @@ def cpu(tmp_path_factory):
     return VH.build_cpu(tmp_path_factory.mktemp("voxel_cpu"))
 
 
-def _gpu_visible():
-    from tests.conftest import _gpu_visible as g
-    return g()
-
-
-def _declared(header, prefix):
-    txt = open(os.path.join(ROOT, "include", header)).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(%s\w+)\s*\(" % prefix, txt)))
-
-
 def test_header_declarations_equal_the_binding_and_the_exports(voxel):
-    decl = _declared("s4p_voxel.h", "s4p_voxel_")
-    assert len(decl) == 2 and decl == sorted(voxel.SYMBOLS), decl
-    assert not _declared("s4p_voxel.h", "s4p_(?:normals|knn|outliers)_")
     from super4pcs_amd import knn, normals
     L = voxel.load_library()
+    _, decl, exported = S.check_header("s4p_voxel.h", "s4p_voxel_", voxel.SYMBOLS, L, closed_prefixes="s4p_(?:normals|knn|outliers)_")
+    assert len(decl) == 2
     for s in decl:
-        assert getattr(L, s).argtypes is not None and len(getattr(L, s).argtypes) == 13 and getattr(L, s).restype is ctypes.c_int32, s
-    exported = subprocess.run(["nm", "-D", "--defined-only", normals.LIB_PATH], capture_output=True, text=True).stdout
-    assert sorted(set(re.findall(r"\b(s4p_voxel_\w+)", exported))) == decl
+        assert len(getattr(L, s).argtypes) == 13, s
     # nothing new under the older prefixes
     assert sorted(set(re.findall(r"\b(s4p_normals_\w+)", exported))) == sorted(normals.SYMBOLS)
     assert sorted(set(re.findall(r"\b(s4p_(?:knn|outliers)_\w+)", exported))) == sorted(knn.SYMBOLS)
@@ -56,30 +36,20 @@ def test_header_declarations_equal_the_binding_and_the_exports(voxel):
 
 def test_new_kernels_live_in_the_library_namespace(voxel):
     from super4pcs_amd import normals
-    out = subprocess.run(["nm", "-C", normals.LIB_PATH], capture_output=True, text=True).stdout
-    for name in ("k_voxel_bounds", "k_voxel_keys", "k_voxel_heads", "k_voxel_runs", "k_voxel_segs", "k_voxel_long"):
-        assert "s4p_nrm::" + name in out, name
-    for na in range(9):
-        assert "s4p_nrm::k_voxel_reduce<%d>" % na in out and "s4p_nrm::k_voxel_partials<%d>" % na in out, na
-    assert not re.search(r"(?<!s4p_nrm::)\bk_voxel_\w+", out)
+    S.check_kernels_in_namespace(["k_voxel_bounds", "k_voxel_keys", "k_voxel_heads", "k_voxel_runs", "k_voxel_segs", "k_voxel_long"] +
+                                 ["k_voxel_%s<%d>" % (which, na) for na in range(9) for which in ("reduce", "partials")],
+                                 stray=r"(?<!s4p_nrm::)\bk_voxel_\w+")
     needed = subprocess.run(["readelf", "-d", normals.LIB_PATH], capture_output=True, text=True).stdout
     libs = re.findall(r"NEEDED.*\[(.*?)\]", needed)
     assert any("amdhip64" in l for l in libs) and not [l for l in libs if re.search(r"rocblas|rocsolver|hipblas|torch|rccl", l)], libs
 
 
-@pytest.mark.skipif(_gpu_visible(), reason="checks the failure without a device")
+@pytest.mark.skipif(S.gpu_visible(), reason="checks the failure without a device")
 def test_calls_fail_loudly_without_a_device(voxel):
-    with pytest.raises(voxel.NormalsError) as e:
-        voxel.VoxelGrid(0)
-    assert e.value.code == -2 and "no HIP device" in str(e.value)
-    X = np.zeros((10, 3), np.float32)
-    with pytest.raises(voxel.NormalsError) as e:
-        voxel.voxel_downsample(X, 0.1)
-    assert e.value.code == -2
     from super4pcs_amd import icp, multiscale
-    with pytest.raises((voxel.NormalsError, icp.ICPError)) as e:
-        multiscale.refine_multiscale(X, X, voxel_sizes=(0.1, 0), max_distance=0.1)
-    assert e.value.code == -2
+    X = np.zeros((10, 3), np.float32)
+    S.check_no_device(voxel.NormalsError, (lambda: voxel.VoxelGrid(0), lambda: voxel.voxel_downsample(X, 0.1)))
+    S.check_no_device((voxel.NormalsError, icp.ICPError), (lambda: multiscale.refine_multiscale(X, X, voxel_sizes=(0.1, 0), max_distance=0.1),))
 
 
 @pytest.mark.parametrize("name", VH.TINY)
@@ -160,78 +130,43 @@ def test_refine_multiscale_argument_checks():
 
 
 def test_cli_voxel_size_flag(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--voxel-size", "0"], ["--voxel-size", "-1"], ["--voxel-size", "x"], ["--voxel-size", ""], ["--voxel-size", "1x"],
-                ["--voxel-size", "nan"], ["--voxel-size", "inf"], ["--voxel-size", "1e-60"], ["--voxel-size"]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--voxel-size" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--voxel-size", "0.5"], ["--voxel-size", "1e-3", "--remove-outliers", "16", "--estimate-normals", "16"],
-                 ["--icp", "5", "--voxel-size", "2"]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
-    # the older usage lines are still there, in front of the new one
-    r = subprocess.run(base + ["-h"], capture_output=True, text=True)
-    assert r.stderr.index("--remove-outliers k") < r.stderr.index("--voxel-size v")
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--voxel-size", "0"], ["--voxel-size", "-1"], ["--voxel-size", "x"], ["--voxel-size", ""], ["--voxel-size", "1x"],
+             ["--voxel-size", "nan"], ["--voxel-size", "inf"], ["--voxel-size", "1e-60"], ["--voxel-size"]),
+        good=(["--voxel-size", "0.5"], ["--voxel-size", "1e-3", "--remove-outliers", "16", "--estimate-normals", "16"],
+              ["--icp", "5", "--voxel-size", "2"]),
+        usage_word="--voxel-size", usage_order=("--remove-outliers k", "--voxel-size v"))
 
 
 def test_cli_refuses_an_input_with_faces(tmp_path):
-    from super4pcs_amd import build as B
-    from tests import knn_helpers as KH
-    cli = B.build_cli()
-    pts = np.random.default_rng(1).uniform(size=(50, 3))
-    KH.write_obj(tmp_path / "P.obj", pts)
-    KH.write_obj(tmp_path / "Q.obj", pts, faces=[(1, 2, 3), (2, 3, 4)])
-    for first, second in (("P.obj", "Q.obj"), ("Q.obj", "P.obj")):
-        r = subprocess.run([cli, "-i", str(tmp_path / first), str(tmp_path / second), "--voxel-size", "0.2", "-m", str(tmp_path / "m.txt")],
-                           capture_output=True, text=True, timeout=120)
-        assert r.returncode == 254 and "faces" in r.stdout + r.stderr, (r.returncode, r.stdout, r.stderr)
-        assert not (tmp_path / "m.txt").exists()
+    S.check_cli_refuses_faces(tmp_path, ["--voxel-size", "0.2"])
 
 
 @pytest.mark.parametrize("eigen", [False, True])
 def test_facade_header_compiles_with_and_without_eigen(voxel, tmp_path, eigen):
-    extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text('#include "super4pcs/algorithms/voxelgrid.h"\n#ifdef S4P_HAVE_EIGEN\n#error have\n#else\n#error none\n#endif\n')
-    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include")] + extra + [str(probe)],
-                       capture_output=True, text=True)
-    assert re.search(r"#error (have|none)", r.stderr).group(1) == ("have" if eigen else "none"), r.stderr
-    exe = VH.build_app(tmp_path, extra)
-    assert os.path.exists(exe)
-    VH.write_table(tmp_path / "P.txt", np.random.default_rng(2).uniform(size=(20, 3)))
-    if not _gpu_visible():
-        r = subprocess.run([exe, str(tmp_path / "P.txt"), "0.1", "plain"], capture_output=True, text=True)
-        assert r.returncode == 1 and "no HIP device" in r.stderr
-    for bad in ("0", "-1", "nan", "1e39"):
-        r = subprocess.run([exe, str(tmp_path / "P.txt"), bad, "plain"], capture_output=True, text=True)
-        assert r.returncode == 1 and "VoxelDownsample:" in r.stderr, (bad, r.stderr)
+    S.check_facade_header(tmp_path, "voxelgrid.h", eigen, "voxel", np.random.default_rng(2).uniform(size=(20, 3)),
+                          no_device_args=["0.1", "plain"], no_device_text=("no HIP device",),
+                          bad_args=(["0", "plain"], ["-1", "plain"], ["nan", "plain"], ["1e39", "plain"]), bad_text="VoxelDownsample:")
 
 
 def test_cli_icp_scales_flag(tmp_path):
-    from super4pcs_amd import build as B
-    cli = B.build_cli()
-    base = [cli, "-i", "a.obj", "b.obj"]
-    for bad in (["--icp-scales", "0.1"],                                        # needs --icp
-                ["--icp", "0", "--icp-scales", "0.1"],
-                ["--icp", "5", "--icp-scales", "0,0.1"],                         # only the last entry may be 0
-                ["--icp", "5", "--icp-scales", "0.1,0.2"],                       # increasing
-                ["--icp", "5", "--icp-scales", "x"], ["--icp", "5", "--icp-scales", ""], ["--icp", "5", "--icp-scales", "0.1,"],
-                ["--icp", "5", "--icp-scales", ",0.1"], ["--icp", "5", "--icp-scales", "0.1,,0"], ["--icp", "5", "--icp-scales", "-1"],
-                ["--icp", "5", "--icp-scales", "nan"], ["--icp", "5", "--icp-scales", "inf,1"], ["--icp", "5", "--icp-scales", "0.1x"],
-                ["--icp", "5", "--icp-scales", "0.2 0.1"], ["--icp", "5", "--icp-scales", "1e-60"],
-                ["--icp", "5", "--icp-scales", ",".join(["1"] * 17)], ["--icp", "5", "--icp-scales"]):
-        r = subprocess.run(base + bad, capture_output=True, text=True)
-        assert r.returncode == 1 and "Usage:" in r.stderr and "--icp-scales" in r.stderr, (bad, r.returncode, r.stderr)
-    for good in (["--icp", "5", "--icp-scales", "0.2,0.1,0"], ["--icp-scales", "0.2", "--icp", "5"], ["--icp", "5", "--icp-scales", "0"],
-                 ["--icp", "5", "--icp-scales", "0.1,0.1"], ["--icp", "5", "--icp-scales", "4e-2,1e-2,0", "--icp-dist", "0.008"],
-                 ["--icp", "5", "--icp-scales", "0.2,0", "--icp-metric", "gicp", "--voxel-size", "0.01"],
-                 ["--icp", "5", "--icp-scales", ",".join(["1"] * 16)]):
-        r = subprocess.run([cli, "-i", str(tmp_path / "none1.obj"), str(tmp_path / "none2.obj")] + good, capture_output=True, text=True)
-        assert r.returncode == 255 and "Can't read input set1" in r.stderr, (good, r.stderr)
-    r = subprocess.run(base + ["-h"], capture_output=True, text=True)
-    assert r.stderr.index("--voxel-size v") < r.stderr.index("--icp-scales v1")
+    S.check_cli_flags(
+        tmp_path,
+        bad=(["--icp-scales", "0.1"],                                        # needs --icp
+             ["--icp", "0", "--icp-scales", "0.1"],
+             ["--icp", "5", "--icp-scales", "0,0.1"],                         # only the last entry may be 0
+             ["--icp", "5", "--icp-scales", "0.1,0.2"],                       # increasing
+             ["--icp", "5", "--icp-scales", "x"], ["--icp", "5", "--icp-scales", ""], ["--icp", "5", "--icp-scales", "0.1,"],
+             ["--icp", "5", "--icp-scales", ",0.1"], ["--icp", "5", "--icp-scales", "0.1,,0"], ["--icp", "5", "--icp-scales", "-1"],
+             ["--icp", "5", "--icp-scales", "nan"], ["--icp", "5", "--icp-scales", "inf,1"], ["--icp", "5", "--icp-scales", "0.1x"],
+             ["--icp", "5", "--icp-scales", "0.2 0.1"], ["--icp", "5", "--icp-scales", "1e-60"],
+             ["--icp", "5", "--icp-scales", ",".join(["1"] * 17)], ["--icp", "5", "--icp-scales"]),
+        good=(["--icp", "5", "--icp-scales", "0.2,0.1,0"], ["--icp-scales", "0.2", "--icp", "5"], ["--icp", "5", "--icp-scales", "0"],
+              ["--icp", "5", "--icp-scales", "0.1,0.1"], ["--icp", "5", "--icp-scales", "4e-2,1e-2,0", "--icp-dist", "0.008"],
+              ["--icp", "5", "--icp-scales", "0.2,0", "--icp-metric", "gicp", "--voxel-size", "0.01"],
+              ["--icp", "5", "--icp-scales", ",".join(["1"] * 16)]),
+        usage_word="--icp-scales", usage_order=("--voxel-size v", "--icp-scales v1"))
 
 
 @pytest.mark.parametrize("eigen", [False, True])
@@ -239,19 +174,13 @@ def test_multiscale_facade_header_compiles_with_and_without_eigen(voxel, tmp_pat
     from super4pcs_amd import build as B
     from tests import multiscale_helpers as MH
     B.build_icp()
-    extra = ["-I" + os.path.join(ROOT, "oracle", "eigen_shim")] if eigen else ["-DS4P_NO_EIGEN"]
-    probe = tmp_path / "probe.cpp"
-    probe.write_text('#include "super4pcs/algorithms/icp_multiscale.h"\n#ifdef S4P_HAVE_EIGEN\n#error have\n#else\n#error none\n#endif\n')
-    r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include")] + extra + [str(probe)],
-                       capture_output=True, text=True)
-    assert re.search(r"#error (have|none)", r.stderr).group(1) == ("have" if eigen else "none"), r.stderr
-    exe = MH.build_app(tmp_path, extra)
+    exe = MH.build_app(tmp_path, S.check_header_alone(tmp_path, "icp_multiscale.h", eigen))
     pts = np.random.default_rng(2).uniform(size=(20, 3))
     VH.write_table(tmp_path / "P.xyz", pts); VH.write_table(tmp_path / "Q.xyz", pts); VH.write_table(tmp_path / "T0.txt", np.eye(4))
     args = [exe, str(tmp_path / "P.xyz"), str(tmp_path / "Q.xyz"), str(tmp_path / "T0.txt"), "point"]
     for bad in (["0.1:0.3:5", "0.2:0.6:5"], ["0:0.1:5", "0.1:0.3:5"], ["0.1:0:5"], ["-1:0.3:5"], ["nan:0.3:5"]):
         r = subprocess.run(args + bad, capture_output=True, text=True)
         assert r.returncode == 1 and "RefineICPMultiScale:" in r.stderr, (bad, r.stderr)
-    if not _gpu_visible():
+    if not S.gpu_visible():
         r = subprocess.run(args + ["0.1:0.3:5", "0:0.1:5"], capture_output=True, text=True)
         assert r.returncode == 1 and "no HIP device" in r.stderr

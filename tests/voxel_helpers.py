@@ -4,16 +4,13 @@ same contract for the tiny shapes, and the clouds the host and GPU tests share. 
 path: numpy's pairwise sum has another order."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 
 from tests import apps
+from tests import normals_suite as S
 from tests.normals_helpers import bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "voxel_cpu", "voxel_cpu.cpp")
 MAX_EXTENT = 1 << 21
 BLOCK = 64
 
@@ -28,25 +25,20 @@ class CPU:
 
     def downsample(self, X, voxel, attrs=None):
         """(xyz (m, 3) float32, attrs (m, nattr) float32 or None, counts (m,) int32, voxel_of (n,) int32)."""
-        X = np.asarray(X, np.float32)
-        n = len(X)
-        cols = [np.ascontiguousarray(X[:, a]) for a in range(3)]
+        p = S.cols(X)
+        n = p[0].shape[0]
         A = None if attrs is None else np.ascontiguousarray(np.asarray(attrs, np.float32).reshape(n, -1))
         na = 0 if A is None else A.shape[1]
         xyz = np.empty((n, 3), np.float32); out_a = np.empty((n, max(na, 1)), np.float32)
         cnt = np.empty(n, np.int32); vof = np.empty(n, np.int32)
-        m = self.L.voxel_cpu_downsample(cols[0].ctypes.data, cols[1].ctypes.data, cols[2].ctypes.data, n, float(voxel),
-                                        None if A is None else A.ctypes.data, na, xyz.ctypes.data, out_a.ctypes.data, cnt.ctypes.data,
-                                        vof.ctypes.data)
+        m = self.L.voxel_cpu_downsample(*S.xyzn(p), float(voxel), S.ptr(A), na, xyz.ctypes.data, out_a.ctypes.data, cnt.ctypes.data, vof.ctypes.data)
         if m < 0:
             raise ExtentError("an axis spans more than 2^21 voxels")
         return xyz[:m].copy(), (None if A is None else out_a[:m, :na].copy()), cnt[:m].copy(), vof
 
 
 def build_cpu(outdir):
-    so = os.path.join(str(outdir), "libvoxel_cpu.so")
-    subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17", SRC, "-o", so])
-    L = C.CDLL(so)
+    L = S.build_restatement("voxel_cpu/voxel_cpu.cpp", outdir, "libvoxel_cpu", openmp=False)
     vp = C.c_void_p
     L.voxel_cpu_downsample.restype = C.c_int64
     L.voxel_cpu_downsample.argtypes = [vp, vp, vp, C.c_int64, C.c_float, vp, C.c_int32, vp, vp, vp, vp]
@@ -200,7 +192,7 @@ TINY = [k for k in CASES if k != "one4097"]                 # what the Python di
 
 def assert_same(got, want, what):
     """Bit equality of (xyz, attrs, counts, voxel_of) and of m."""
-    gx, ga, gc, gv = [None if t is None else (t.cpu().numpy() if type(t).__module__.startswith("torch") else np.asarray(t)) for t in got]
+    gx, ga, gc, gv = [None if t is None else S.to_host(t) for t in got]
     wx, wa, wc, wv = want
     assert gx.shape == wx.shape, (what, "m", gx.shape, wx.shape)
     assert np.array_equal(gc, wc), (what, "counts")
@@ -216,12 +208,4 @@ def assert_same(got, want, what):
 write_obj = apps.write_obj
 
 
-def build_app(outdir, extra=()):
-    """tests/voxel_app/main.cpp against the facade header and libsuper4pcs_normals.so."""
-    return apps.build_app(outdir, "voxel_app", ("super4pcs_normals",), ("-Werror",) + tuple(extra))
-
-
-def write_table(path, rows):
-    with open(path, "w") as f:
-        for r in rows:
-            f.write(" ".join("%.9g" % t for t in r) + "\n")
+write_table = apps.write_xyz
