@@ -12,6 +12,7 @@
 //             [--voxel-size v] [--icp-scales v1,v2,...] [--icp-starts K] [--icp-information file]
 //             [--cluster-eps e] [--cluster-min-points m] [--cluster-keep K]
 //             [--remove-plane d] [--remove-plane-trials T] [--remove-plane-count K]
+//             [--estimate-normals-within r] [--estimate-normals-min m]
 // --icp N refines the registration by point-to-point ICP on the full clouds (algorithms/icp.h) before -m / -r are written;
 // with --icp-metric plane it minimises point-to-plane distances (P's normals, or normals estimated within r).
 // With --icp-metric gicp it is generalized ICP (include/s4p_icp_gicp.h, covariance parameter --icp-gicp-epsilon): P's
@@ -45,6 +46,9 @@
 // --remove-plane-trials T candidates, default 1024, inliers within d, one least-squares refit) after --voxel-size and before
 // --cluster-eps, which would otherwise join a scanned scene through its ground; -r then writes the filtered, registered
 // second input.  An input with faces, or one left with fewer than 3 points, is refused (exit status 254).
+// --estimate-normals-within r gives both inputs radius normals (algorithms/shape.h: every point within r is a neighbour, a point
+// with fewer than max(3, --estimate-normals-min m) gets none) at the place and in the stead of --estimate-normals, which takes at
+// most 32 neighbours; the two together are a usage error, and --orient-normals may follow either.
 // --icp-scales v1,v2,... (needs --icp) refines coarse to fine (algorithms/icp_multiscale.h): one level per voxel size, both
 // inputs downsampled at it (the second in its own frame; 0, allowed last, takes them as they are), the level's distance
 // max(--icp-dist, 3 v) and --icp iterations per level; every --icp-metric and --icp-loss applies to every level.
@@ -72,6 +76,7 @@
 #include "super4pcs/algorithms/normals.h"
 #include "super4pcs/algorithms/outliers.h"
 #include "super4pcs/algorithms/plane.h"
+#include "super4pcs/algorithms/shape.h"
 #include "super4pcs/algorithms/super4pcs.h"
 #include "super4pcs/algorithms/voxelgrid.h"
 #include "super4pcs/io/io.h"
@@ -248,6 +253,14 @@ int run(const s4p_cli::Options& opt, const Utils::Logger& log) {
       EstimateNormals(P.points, nopt);
       EstimateNormals(Q.points, nopt);
       log.Log<Utils::Verbose>("Estimated normals: k ", opt.normals_k, ", radius ", opt.normals_radius);
+    }
+    if (opt.normals_within > 0) {
+      RadiusNormalOptions ropt;
+      ropt.radius = opt.normals_within;
+      ropt.min_neighbours = opt.normals_min;
+      const size_t zp = EstimateNormalsRadius(P.points, ropt), zq = EstimateNormalsRadius(Q.points, ropt);
+      log.Log<Utils::Verbose>("Estimated normals within radius ", opt.normals_within, ", min neighbours ", opt.normals_min, ": ", zp,
+                              " points of input1 without a normal, ", zq, " of input2");
     }
     if (opt.orient_k > 0) {
       NormalOrientationOptions oopt;

@@ -64,6 +64,9 @@ struct Options {
   int remove_plane_trials = 1024;                            // --remove-plane-trials T  (needs distance; 1 .. 2^20)
   int remove_plane_count = 1;                                // --remove-plane-count K  (needs distance)
   bool remove_plane_trials_set = false, remove_plane_count_set = false;
+  double normals_within = -1;                                // --estimate-normals-within r  radius normals of both inputs on the device (off)
+  int normals_min = 3;                                       // --estimate-normals-min m  (needs r)
+  bool normals_min_set = false;
   bool bad_value = false;                                   // a flag's value does not parse
 };
 
@@ -260,6 +263,18 @@ inline const Flag* flag_table(size_t* n) {
          o.remove_plane_count_set = true;
          if (end == v[0] || *end != '\0' || k < 1 || k > 2147483647L) o.bad_value = true; else o.remove_plane_count = int(k);
        }},
+      {"--estimate-normals-within", 1, [](Options& o, char** v) {
+         // finite, > 0, and with a square that is a finite float
+         char* end = nullptr;
+         const double r = std::strtod(v[0], &end);
+         if (end == v[0] || *end != '\0' || !(r > 0) || !(r < 1.8e19) || !(float(r) > 0.f)) o.bad_value = true; else o.normals_within = r;
+       }},
+      {"--estimate-normals-min", 1, [](Options& o, char** v) {
+         char* end = nullptr;
+         const long m = std::strtol(v[0], &end, 10);
+         o.normals_min_set = true;
+         if (end == v[0] || *end != '\0' || m < 1 || m > 2147483647L) o.bad_value = true; else o.normals_min = int(m);
+       }},
   };
   *n = sizeof(table) / sizeof(table[0]);
   return table;
@@ -284,7 +299,9 @@ inline Parse parse(Options& o, int argc, char** argv) {
   if (o.bad_value) return Parse::Bad;
   if (o.normals_radius_set && o.normals_k == 0) return Parse::Bad;    // the radius needs --estimate-normals
   if (o.outliers_std_set && o.outliers_k == 0) return Parse::Bad;      // the ratio needs --remove-outliers
-  if (o.orient_k > 0 && o.normals_k == 0) return Parse::Bad;           // --orient-normals needs --estimate-normals
+  if (o.normals_k > 0 && o.normals_within > 0) return Parse::Bad;      // k neighbours or a radius neighbourhood, not both
+  if (o.normals_min_set && !(o.normals_within > 0)) return Parse::Bad; // the minimum needs --estimate-normals-within
+  if (o.orient_k > 0 && o.normals_k == 0 && !(o.normals_within > 0)) return Parse::Bad;    // --orient-normals needs --estimate-normals or -within
   if (o.orient_viewpoint_set && o.orient_k == 0) return Parse::Bad;    // --orient-viewpoint needs --orient-normals
   if ((o.cluster_min_points_set || o.cluster_keep_set) && !(o.cluster_eps > 0)) return Parse::Bad;    // both need --cluster-eps
   if ((o.remove_plane_trials_set || o.remove_plane_count_set) && !(o.remove_plane >= 0)) return Parse::Bad;    // both need --remove-plane
@@ -361,6 +378,10 @@ inline void usage(const Options& o, const char* prog, bool all) {
   std::fprintf(stderr, "\t     planes the one with the most points within d wins, is refitted once to them by least squares and goes with\n");
   std::fprintf(stderr, "\t     them, K times: the ground of a scan, through which --cluster-eps would join the scene; point sets only, -r\n");
   std::fprintf(stderr, "\t     writes the filtered input2)\n");
+  std::fprintf(stderr, "\t[ --estimate-normals-within r (> 0; off) ] [ --estimate-normals-min m (needs r; 3, >= 1) ]\n");
+  std::fprintf(stderr, "\t    (radius normals of both inputs on the device, where --estimate-normals stands and instead of it: every point\n");
+  std::fprintf(stderr, "\t     within r is a neighbour, hundreds on a dense scan where 32 lie inside the noise; a point with fewer than\n");
+  std::fprintf(stderr, "\t     max(3, m) gets no normal; --orient-normals may follow)\n");
 }
 
 // false: the overlap / terminate-threshold pair is inconsistent (Match4PCSOptions::configureOverlap)

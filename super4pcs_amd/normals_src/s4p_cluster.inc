@@ -240,11 +240,12 @@ struct ClusterGrid {
   }
 };
 
-int32_t cluster_grid_plan(s4p_normals_ctx* h, const char* what, float eps, ClusterGrid* G) {
+// rings: how many cells on each side of a point's cell hold its neighbours (s4p_shape.inc asks for 2: half the edge)
+int32_t cluster_grid_plan(s4p_normals_ctx* h, const char* what, float eps, ClusterGrid* G, int rings = 1) {
   const uint64_t un = uint64_t(h->n);
   double ext = 0.0;
   for (int a = 0; a < 3; ++a) ext = std::max(ext, double(h->hi[a]) - double(h->lo[a]));
-  const double hh = std::max(double(eps) * kClusterEdgeMargin, ext * 0x1p-20);
+  const double hh = std::max(double(eps) * kClusterEdgeMargin / rings, ext * 0x1p-20);
   if (int32_t rc = fit_grid(h, what, h->lo, h->hi, hh, un, &G->g, &G->ncell)) return rc;
   if (int32_t rc = sort_pairs_bytes(h, un, G->ncell - 1, &G->sort_bytes)) return rc;
   return S4P_NORMALS_OK;
