@@ -1,5 +1,5 @@
 // What the facade functions on libsuper4pcs_normals.so share (EstimateNormals, OrientNormals, RemoveOutliers,
-// VoxelDownsample, ClusterDBSCAN, SegmentPlane, EstimateNormalsRadius): the context that lives for one call, and a cloud's positions as three columns.  algorithms/icp.h takes
+// VoxelDownsample, ClusterDBSCAN, SegmentPlane, EstimateNormalsRadius, ComputeFPFH, MatchFeatures): the context that lives for one call, and a cloud's positions as three columns.  algorithms/icp.h takes
 // cloud_soa from here too; it never names NormalsHandle, so a program that links -lsuper4pcs_icp alone still links.
 #ifndef S4P_FACADE_NORMALS_HANDLE_H_
 #define S4P_FACADE_NORMALS_HANDLE_H_

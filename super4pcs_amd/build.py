@@ -140,13 +140,13 @@ def build_normals(force=False, verbose=False, extra_flags=()):
     """lib/libsuper4pcs_normals.so: k-nearest-neighbour normal estimation (normals_src/, include/s4p_normals.h) and the
     neighbour lists and outlier removal on the same search (include/s4p_knn.h), voxel-grid downsampling
     (include/s4p_voxel.h), consistent normal orientation (include/s4p_normals_orient.h), density clustering
-    (include/s4p_cluster.h), plane segmentation (include/s4p_plane.h) and radius-neighbourhood normals (include/s4p_shape.h),
-    a library of its own so that the main and the ICP libraries stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off); it needs only the HIP
+    (include/s4p_cluster.h), plane segmentation (include/s4p_plane.h), radius-neighbourhood normals (include/s4p_shape.h) and FPFH descriptors with
+    their matcher (include/s4p_feature.h), a library of its own so that the main and the ICP libraries stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off); it needs only the HIP
     runtime and the hipCUB headers."""
     deps = [os.path.join(NORMALS_SRC, f) for f in os.listdir(NORMALS_SRC)] + [os.path.join(ROOT, "include", h)
                                                                                for h in ("s4p_normals.h", "s4p_knn.h", "s4p_voxel.h",
                                                                                          "s4p_normals_orient.h", "s4p_cluster.h", "s4p_plane.h",
-                                                                                         "s4p_shape.h")]
+                                                                                         "s4p_shape.h", "s4p_feature.h")]
     if not force and not extra_flags and os.path.exists(NORMALS_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(NORMALS_LIB)
                                                                              for d in deps):
         return NORMALS_LIB

@@ -12,6 +12,8 @@
 //   density clustering (include/s4p_cluster.h): s4p_cluster.inc, a fixed-radius walk on a grid of edge eps and a union-find.
 //   plane segmentation (include/s4p_plane.h): s4p_plane.inc, RANSAC as a dense candidates x points count, no grid.
 //   radius normals (include/s4p_shape.h): s4p_shape.inc, a fixed-radius walk on a grid of edge r that sums integer moments.
+//   descriptors (include/s4p_feature.h): s4p_feature.inc, FPFH as two walks of that grid over integer histograms, and a dense
+//               rows x columns matcher over integer distances.
 //   estimate    queries in cell order (the cloud itself, or QueryStage: k_cell_keys + sort + k_gather of the caller's
 //               queries) -> k_knn_normals<K>: one lane per query, knn_walk (ring search with conservative box pruning, the
 //               k best (d2, index) sorted in registers), covariance in double, 3x3 Jacobi, the normal scattered to the
@@ -31,6 +33,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "s4p_knn.h"
@@ -744,6 +747,7 @@ int32_t estimate_at_impl(s4p_normals_ctx* h, const float* qx, const float* qy, c
 #include "s4p_cluster.inc"               // include/s4p_cluster.h: density clustering on a grid of its own, on the same stream and arena
 #include "s4p_plane.inc"                 // include/s4p_plane.h: RANSAC plane segmentation on the cloud in the caller's order, same stream and arena
 #include "s4p_shape.inc"                 // include/s4p_shape.h: radius-neighbourhood normals and eigenvalues on a grid of edge r, same stream and arena
+#include "s4p_feature.inc"               // include/s4p_feature.h: FPFH descriptors on the grid of s4p_shape.inc and the feature-space matcher
 
 extern "C" {
 
