@@ -108,6 +108,9 @@ def build_variant(name, defines):
 ICP_SRC = os.path.join(_HERE, "icp_src")
 ICP_LIB = os.path.join(LIBDIR, "libsuper4pcs_icp.so")
 ICP_SOURCES = ["s4p_icp.hip"]
+ICP_HEADERS = [os.path.join(ROOT, "include", h) for h in (
+    "s4p_icp.h", "s4p_icp_plane.h", "s4p_icp_robust.h", "s4p_icp_gicp.h", "s4p_icp_symm.h", "s4p_icp_color.h", "s4p_icp_reject.h",
+    "s4p_icp_batch.h", "s4p_icp_info.h", "s4p_icp_posegraph.h")]
 
 
 def build_icp(force=False, verbose=False):
@@ -115,9 +118,7 @@ def build_icp(force=False, verbose=False):
     so that the main library's sources and kernels stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off).
     One translation unit: s4p_icp.hip includes s4p_icp_k_common / _k_build / _k_pass.hip.hpp (kernels) and s4p_icp_solve / _ctx / _pass /
     _abi.inc (host), then s4p_icp_k_batch.hip.hpp, s4p_icp_batch.inc and s4p_icp_posegraph.inc (host only); a change to any file under icp_src/ rebuilds."""
-    deps = [os.path.join(ICP_SRC, f) for f in os.listdir(ICP_SRC)] + [os.path.join(ROOT, "include", h)
-                                                                       for h in ("s4p_icp.h", "s4p_icp_plane.h", "s4p_icp_robust.h", "s4p_icp_gicp.h", "s4p_icp_symm.h", "s4p_icp_color.h",
-                                                                                 "s4p_icp_reject.h", "s4p_icp_batch.h", "s4p_icp_info.h", "s4p_icp_posegraph.h")]
+    deps = [os.path.join(ICP_SRC, f) for f in os.listdir(ICP_SRC)] + ICP_HEADERS
     if not force and os.path.exists(ICP_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(ICP_LIB) for d in deps):
         return ICP_LIB
     os.makedirs(LIBDIR, exist_ok=True)
@@ -134,6 +135,8 @@ def build_icp(force=False, verbose=False):
 NORMALS_SRC = os.path.join(_HERE, "normals_src")
 NORMALS_LIB = os.path.join(LIBDIR, "libsuper4pcs_normals.so")
 NORMALS_SOURCES = ["s4p_normals.hip"]
+NORMALS_HEADERS = [os.path.join(ROOT, "include", h) for h in (
+    "s4p_normals.h", "s4p_knn.h", "s4p_voxel.h", "s4p_normals_orient.h", "s4p_cluster.h", "s4p_plane.h", "s4p_shape.h", "s4p_feature.h")]
 
 
 def build_normals(force=False, verbose=False, extra_flags=()):
@@ -143,10 +146,7 @@ def build_normals(force=False, verbose=False, extra_flags=()):
     (include/s4p_cluster.h), plane segmentation (include/s4p_plane.h), radius-neighbourhood normals (include/s4p_shape.h) and FPFH descriptors with
     their matcher (include/s4p_feature.h), a library of its own so that the main and the ICP libraries stay exactly the measured ones.  Same hipcc flags (incl. -ffp-contract=off); it needs only the HIP
     runtime and the hipCUB headers."""
-    deps = [os.path.join(NORMALS_SRC, f) for f in os.listdir(NORMALS_SRC)] + [os.path.join(ROOT, "include", h)
-                                                                               for h in ("s4p_normals.h", "s4p_knn.h", "s4p_voxel.h",
-                                                                                         "s4p_normals_orient.h", "s4p_cluster.h", "s4p_plane.h",
-                                                                                         "s4p_shape.h", "s4p_feature.h")]
+    deps = [os.path.join(NORMALS_SRC, f) for f in os.listdir(NORMALS_SRC)] + NORMALS_HEADERS
     if not force and not extra_flags and os.path.exists(NORMALS_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(NORMALS_LIB)
                                                                              for d in deps):
         return NORMALS_LIB
@@ -171,24 +171,12 @@ def build_cli(force=False):
     build()
     build_icp(force=force)
     build_normals(force=force)
-    deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB, ICP_LIB, NORMALS_LIB,
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "normals.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "normals_handle.h"),
-            os.path.join(ROOT, "include", "s4p_normals_orient.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "outliers.h"),
-            os.path.join(ROOT, "include", "s4p_cluster.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "cluster.h"),
-            os.path.join(ROOT, "include", "s4p_plane.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "plane.h"),
-            os.path.join(ROOT, "include", "s4p_shape.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "shape.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "voxelgrid.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp_multiscale.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp_batch.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "icp_information.h"),
-            os.path.join(ROOT, "include", "super4pcs", "io", "io.h"),
-            os.path.join(ROOT, "include", "super4pcs", "algorithms", "match4pcsBase.h")]
+    # the C headers of the two libraries rebuild those libraries, and through them this program, today as before
+    deps = [CLI_SRC, os.path.join(ROOT, "demos", "cli_options.h"), LIB, ICP_LIB, NORMALS_LIB] + ICP_HEADERS + NORMALS_HEADERS + [
+        os.path.join(ROOT, "include", "super4pcs", *h.split("/")) for h in (
+            "algorithms/icp.h", "algorithms/normals.h", "algorithms/normals_handle.h", "algorithms/outliers.h", "algorithms/cluster.h",
+            "algorithms/plane.h", "algorithms/shape.h", "algorithms/voxelgrid.h", "algorithms/icp_multiscale.h", "algorithms/icp_batch.h",
+            "algorithms/icp_information.h", "io/io.h", "algorithms/match4pcsBase.h")]
     if not force and os.path.exists(CLI) and all(os.path.getmtime(d) <= os.path.getmtime(CLI) for d in deps):
         return CLI
     os.makedirs(BINDIR, exist_ok=True)

@@ -15,13 +15,12 @@ import ctypes as C
 
 import numpy as np
 
+from . import _binding as _B
 from . import knn as _K
-from .knn import _empty
-from .normals import NormalsError, _is_torch
+from ._binding import TWIN
+from .normals import NormalsError, session
 
 NOISE, BORDER, CORE = 0, 1, 2
-
-SYMBOLS = ["s4p_cluster_dbscan", "s4p_cluster_dbscan_device", "s4p_cluster_density", "s4p_cluster_density_device"]
 
 
 class ClusterStats(C.Structure):
@@ -31,65 +30,44 @@ class ClusterStats(C.Structure):
         return {"core": self.core, "border": self.border, "noise": self.noise, "clusters": self.clusters}
 
 
-_DECLARED = False
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_cluster.h
+    "s4p_cluster_dbscan" + TWIN: [_VP, C.c_float, C.c_int32, _VP, _VP, C.POINTER(ClusterStats)],
+    "s4p_cluster_density" + TWIN: [_VP, C.c_float, _VP],
+}
+SYMBOLS = _B.names(SIGNATURES)
 
 
-def load_library():
+def load_library(path=None, *tables):
     """The normals library with the s4p_cluster.h entry points declared; a library without them is an error."""
-    global _DECLARED
-    L = _K.load_library()
-    if _DECLARED:
-        return L
-    vp = C.c_void_p
-    missing = [s for s in SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    for name in ("s4p_cluster_dbscan", "s4p_cluster_dbscan_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_float, C.c_int32, vp, vp, C.POINTER(ClusterStats)]
-    for name in ("s4p_cluster_density", "s4p_cluster_density_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_float, vp]
-    _DECLARED = True
-    return L
+    return _K.load_library(path, SIGNATURES, *tables)
 
 
 class Cluster(_K.Knn):
     """An s4p_normals context (one GPU, one cloud) with the clustering calls; the normals and the neighbour-list methods
     work on it too.  Results follow the cloud's kind: numpy for a numpy cloud, torch tensors on its device for a GPU tensor."""
-
-    def __init__(self, device=0):
-        load_library()
-        super().__init__(device)
+    _load = staticmethod(load_library)
 
     def dbscan(self, eps, min_points=10):
         """(labels (n,) int32, kind (n,) uint8, stats dict): labels number the clusters from 0 in ascending order of their
         smallest core index, -1 is noise; kind is NOISE, BORDER or CORE."""
-        labels, pl = _empty(self._like, (self.n,), np.int32)
-        kind, pk = _empty(self._like, (self.n,), np.uint8)
+        labels, pl = _B.empty(self._like, (self.n,), np.int32)
+        kind, pk = _B.empty(self._like, (self.n,), np.uint8)
         st = ClusterStats()
-        self._sync()
-        fn = self.L.s4p_cluster_dbscan_device if self._like is not None else self.L.s4p_cluster_dbscan
-        self._chk(fn(self.h, float(eps), int(min_points), pl, pk, C.byref(st)))
+        self._call("s4p_cluster_dbscan", self._like, float(eps), int(min_points), pl, pk, C.byref(st))
         return labels, kind, st.as_dict()
 
     def density(self, radius):
         """(n,) int32: the number of points within radius of each point (d2 <= fl(r*r)), the point itself included."""
-        count, pc = _empty(self._like, (self.n,), np.int32)
-        self._sync()
-        fn = self.L.s4p_cluster_density_device if self._like is not None else self.L.s4p_cluster_density
-        self._chk(fn(self.h, float(radius), pc))
+        count, pc = _B.empty(self._like, (self.n,), np.int32)
+        self._call("s4p_cluster_density", self._like, float(radius), pc)
         return count
 
 
 def cluster_dbscan(xyz, eps, min_points=10, device=0):
     """DBSCAN of the cloud: (labels, kind, stats) as Cluster.dbscan returns them."""
-    ctx = Cluster(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Cluster, xyz, device) as ctx:
         return ctx.dbscan(eps, min_points)
-    finally:
-        ctx.close()
 
 
 def largest_labels(labels, keep=1, min_size=1):
@@ -106,11 +84,11 @@ def largest_labels(labels, keep=1, min_size=1):
 def keep_clusters(xyz, eps, min_points=10, keep=1, min_size=1, device=0):
     """The cloud without everything but its `keep` largest clusters of at least min_size points (ties in size go to the
     smaller label).  Returns (kept_xyz, keep_mask, labels); kept_xyz = xyz[keep_mask] keeps the input order."""
-    xyz = xyz if _is_torch(xyz) else np.asarray(xyz)
+    xyz = xyz if _B.is_torch(xyz) else np.asarray(xyz)
     labels, _, _ = cluster_dbscan(xyz, eps, min_points, device)
-    host = labels.cpu().numpy() if _is_torch(labels) else labels
+    host = labels.cpu().numpy() if _B.is_torch(labels) else labels
     mask = np.isin(host, np.asarray(largest_labels(host, keep, min_size), np.int64))
-    if _is_torch(labels):
+    if _B.is_torch(labels):
         import torch
         mask = torch.from_numpy(mask).to(labels.device)
     return xyz[mask], mask, labels

@@ -20,40 +20,30 @@ import ctypes as C
 
 import numpy as np
 
+from . import _binding as _B
 from . import shape as _SH
-from .knn import _empty
-from .normals import NormalsError, _is_torch
+from ._binding import TWIN
+from .normals import NormalsError, session
 
-SYMBOLS = ["s4p_feature_fpfh", "s4p_feature_fpfh_device", "s4p_feature_match", "s4p_feature_match_device"]
 BINS = 33
 MAX_VALUE = 4096
 
-_DECLARED = False
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_feature.h
+    "s4p_feature_fpfh" + TWIN: [_VP, _VP, C.c_float, _VP, _VP],
+    "s4p_feature_match" + TWIN: [_VP, _VP, C.c_int64, _VP, C.c_int64, C.c_int32, _VP, _VP],
+}
+SYMBOLS = _B.names(SIGNATURES)
 
 
-def load_library():
+def load_library(path=None, *tables):
     """The normals library with the s4p_feature.h entry points declared; a library without them is an error."""
-    global _DECLARED
-    L = _SH.load_library()
-    if _DECLARED:
-        return L
-    vp = C.c_void_p
-    missing = [s for s in SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    for name in ("s4p_feature_fpfh", "s4p_feature_fpfh_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, C.c_float, vp, vp]
-    for name in ("s4p_feature_match", "s4p_feature_match_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp]
-    _DECLARED = True
-    return L
+    return _SH.load_library(path, SIGNATURES, *tables)
 
 
 def _table(F):
     """(tensor?, a contiguous (rows, 33) uint16 table, its pointer, rows)."""
-    if _is_torch(F):
+    if _B.is_torch(F):
         import torch
         if not (F.is_cuda and F.dtype == torch.uint16 and F.dim() == 2 and F.shape[1] == BINS):
             raise ValueError("torch descriptors must be a (rows, 33) uint16 tensor on the GPU")
@@ -68,23 +58,15 @@ def _table(F):
 class Features(_SH.Shape):
     """An s4p_normals context (one GPU, one cloud) with the descriptor and the matcher; every method of shape.Shape works on
     it too.  match needs no cloud."""
-
-    def __init__(self, device=0):
-        load_library()
-        super().__init__(device)
+    _load = staticmethod(load_library)
 
     def fpfh(self, normals, radius):
         """(F (n, 33) uint16, count (n,) int32) of the cloud's points from their normals (n, 3), which must be consistently
         oriented (Normals.orient).  The results follow the normals' kind: numpy in, numpy out; a GPU tensor in, tensors out."""
-        dev, nrm, pn = self._normals_copy(normals)
-        like = nrm if dev else None
-        F, pf = _empty(like, (self.n, BINS), np.uint16)
-        count, pc = _empty(like, (self.n,), np.int32)
-        if dev:
-            import torch
-            torch.cuda.synchronize(nrm.device)            # torch's copies and allocations before the library's own stream
-        fn = self.L.s4p_feature_fpfh_device if dev else self.L.s4p_feature_fpfh
-        self._chk(fn(self.h, pn, float(radius), pf, pc))
+        like, nrm, pn = self._normals_copy(normals)
+        F, pf = _B.empty(like, (self.n, BINS), np.uint16)
+        count, pc = _B.empty(like, (self.n,), np.int32)
+        self._call("s4p_feature_fpfh", like, pn, float(radius), pf, pc)
         return F, count
 
     def match(self, fa, fb, mutual=True):
@@ -96,13 +78,9 @@ class Features(_SH.Shape):
         if da != db:
             raise ValueError("both tables are numpy arrays or both are GPU tensors")
         like = fa if da else None
-        idx, pi = _empty(like, (m,), np.int32)
-        dist, pd = _empty(like, (m,), np.int32)
-        if da:
-            import torch
-            torch.cuda.synchronize(fa.device)
-        fn = self.L.s4p_feature_match_device if da else self.L.s4p_feature_match
-        self._chk(fn(self.h, pa, m, pb, n, 1 if mutual else 0, pi, pd))
+        idx, pi = _B.empty(like, (m,), np.int32)
+        dist, pd = _B.empty(like, (m,), np.int32)
+        self._call("s4p_feature_match", like, pa, m, pb, n, 1 if mutual else 0, pi, pd)
         return idx, dist
 
 
@@ -119,26 +97,19 @@ def compute_fpfh(xyz, radius, normals=None, normal_radius=None, orient="outward"
         raise ValueError('orient is None, "outward" or a viewpoint (x, y, z)')
     if normals is not None and normal_radius is not None:
         raise ValueError("normal_radius applies to estimated normals only")
-    ctx = Features(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Features, xyz, device) as ctx:
         if normals is None:
             normals = ctx.estimate(float(normal_radius) if normal_radius is not None else float(radius) / 2)[0]
             if orient is not None:
                 normals = ctx.orient(normals, orient_k, None, None if isinstance(orient, str) else orient)
         return ctx.fpfh(normals, radius)
-    finally:
-        ctx.close()
 
 
 def match_features(fa, fb, mutual=True, device=0):
     """(k, 2) int32 of (row of fa, row of fb), in ascending row of fa: Features.match without the rows that found no partner."""
-    ctx = Features(device)
-    try:
+    with session(Features, None, device) as ctx:
         idx, _ = ctx.match(fa, fb, mutual)
-    finally:
-        ctx.close()
-    if _is_torch(idx):
+    if _B.is_torch(idx):
         import torch
         a = torch.nonzero(idx >= 0).flatten()
         return torch.stack([a.to(torch.int32), idx[a]], 1)

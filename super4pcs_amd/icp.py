@@ -26,6 +26,10 @@ import os
 
 import numpy as np
 
+from . import _binding as _B
+from . import posegraph as _PG          # its table and structures; posegraph states them before it imports this module
+from ._binding import TWIN
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsuper4pcs_icp.so")
 
@@ -51,49 +55,15 @@ LOSSES = {"trimmed": 1, "huber": 2, "tukey": 3}             # S4P_ICP_LOSS_*
 LOSS_C = {"huber": 1.345, "tukey": 4.685}                   # default tuning constants
 ROBUST_NINFO = 8
 
-SYMBOLS = [
-    "s4p_icp_default_params", "s4p_icp_create", "s4p_icp_destroy", "s4p_icp_last_error", "s4p_icp_set_target",
-    "s4p_icp_set_source", "s4p_icp_set_target_device", "s4p_icp_set_source_device", "s4p_icp_frame",
-    "s4p_icp_correspondences", "s4p_icp_sums", "s4p_icp_solve", "s4p_icp_refine", "s4p_icp_apply",
-]
-PLANE_SYMBOLS = [                                          # include/s4p_icp_plane.h
-    "s4p_icp_set_target_normals", "s4p_icp_set_target_normals_device", "s4p_icp_estimate_normals", "s4p_icp_target_normals",
-    "s4p_icp_plane_sums", "s4p_icp_solve_plane", "s4p_icp_refine_plane",
-]
-ROBUST_SYMBOLS = [                                         # include/s4p_icp_robust.h
-    "s4p_icp_robust_defaults", "s4p_icp_robust_sums", "s4p_icp_refine_robust",
-]
-GICP_SYMBOLS = [                                           # include/s4p_icp_gicp.h
-    "s4p_icp_set_source_normals", "s4p_icp_set_source_normals_device", "s4p_icp_source_normals", "s4p_icp_gicp_sums",
-    "s4p_icp_refine_gicp",
-]
-SYMM_SYMBOLS = [                                           # include/s4p_icp_symm.h
-    "s4p_icp_symm_sums", "s4p_icp_solve_symmetric", "s4p_icp_refine_symm",
-]
-COLOR_SYMBOLS = [                                          # include/s4p_icp_color.h
-    "s4p_icp_set_target_intensity", "s4p_icp_set_target_intensity_device", "s4p_icp_set_source_intensity",
-    "s4p_icp_set_source_intensity_device", "s4p_icp_estimate_color_gradients", "s4p_icp_target_color_gradients",
-    "s4p_icp_color_sums", "s4p_icp_refine_color",
-]
-REJECT_SYMBOLS = [                                         # include/s4p_icp_reject.h
-    "s4p_icp_reject_defaults", "s4p_icp_set_rejection", "s4p_icp_rejection", "s4p_icp_rejection_counts",
-]
-BATCH_SYMBOLS = [                                          # include/s4p_icp_batch.h
-    "s4p_icp_sums_batch", "s4p_icp_refine_batch", "s4p_icp_rank_batch",
-]
 BATCH_MAX = 64                                             # S4P_ICP_BATCH_MAX
-INFO_SYMBOLS = [                                           # include/s4p_icp_info.h
-    "s4p_icp_information_sums", "s4p_icp_information_from_sums", "s4p_icp_information",
-]
 INFO_NSUMS = 11                                            # S4P_ICP_INFO_NSUMS
-POSEGRAPH_SYMBOLS = [                                      # include/s4p_icp_posegraph.h (bound in super4pcs_amd.posegraph)
-    "s4p_icp_posegraph_default_params", "s4p_icp_posegraph_cost", "s4p_icp_posegraph_optimize",
-]
 NORMALS_OFF, NORMALS_UNORIENTED, NORMALS_ORIENTED = 0, 1, 2         # S4P_ICP_REJECT_NORMALS_*
 WHY_KEPT, WHY_UNMATCHED, WHY_NORMALS, WHY_RECIPROCITY = 0, 1, 2, 3  # S4P_ICP_WHY_*
 
 
 class ICPError(RuntimeError):
+    REBUILD = "build.build_icp()"
+
     def __init__(self, code, msg):
         super().__init__("s4p_icp error %s (%d): %s" % (ERR_NAMES.get(code, "?"), code, msg))
         self.code = code
@@ -128,113 +98,82 @@ class Result(C.Structure):
                 "fitness": self.fitness, "history_rmse": list(self.history_rmse[:k]), "history_n": list(self.history_n[:k])}
 
 
-_LIB = None
+_VP, _FP, _DP, _IP, _LP = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+_PARAMS, _RESULT = C.POINTER(Params), C.POINTER(Result)
+SIGNATURES = {                                             # include/s4p_icp.h
+    "s4p_icp_default_params": (None, [_PARAMS]),
+    "s4p_icp_create": [C.c_int32, C.POINTER(_VP)],
+    "s4p_icp_destroy": (None, [_VP]),
+    "s4p_icp_last_error": (C.c_char_p, [_VP]),
+    "s4p_icp_set_target" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64, C.c_float],
+    "s4p_icp_set_source" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64],
+    "s4p_icp_frame": [_VP, _FP],
+    "s4p_icp_correspondences": [_VP, _FP, _IP, _FP],
+    "s4p_icp_sums": [_VP, _FP, _DP],
+    "s4p_icp_solve": [_DP, _DP],
+    "s4p_icp_refine": [_VP, _PARAMS, _DP, _RESULT],
+    "s4p_icp_apply": [_VP, _DP, _FP, _FP, _FP, C.c_int64],
+}
+PLANE_SIGNATURES = {                                       # include/s4p_icp_plane.h
+    "s4p_icp_set_target_normals" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64],
+    "s4p_icp_estimate_normals": [_VP, C.c_float, C.c_int32],
+    "s4p_icp_target_normals": [_VP, _FP, _FP, _FP],
+    "s4p_icp_plane_sums": [_VP, _FP, _DP],
+    "s4p_icp_solve_plane": [_DP, _DP],
+    "s4p_icp_refine_plane": [_VP, _PARAMS, _DP, _RESULT],
+}
+ROBUST_SIGNATURES = {                                      # include/s4p_icp_robust.h
+    "s4p_icp_robust_defaults": (None, [C.POINTER(Robust), C.c_int32]),
+    "s4p_icp_robust_sums": [_VP, _FP, C.c_int32, C.POINTER(Robust), _DP, _DP],
+    "s4p_icp_refine_robust": [_VP, _PARAMS, C.c_int32, C.POINTER(Robust), _DP, _RESULT, _DP],
+}
+GICP_SIGNATURES = {                                        # include/s4p_icp_gicp.h
+    "s4p_icp_set_source_normals" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64],
+    "s4p_icp_source_normals": [_VP, _FP, _FP, _FP],
+    "s4p_icp_gicp_sums": [_VP, _FP, C.c_double, _DP],
+    "s4p_icp_refine_gicp": [_VP, _PARAMS, C.c_double, _DP, _RESULT],
+}
+SYMM_SIGNATURES = {                                        # include/s4p_icp_symm.h
+    "s4p_icp_symm_sums": [_VP, _FP, _DP],
+    "s4p_icp_solve_symmetric": [_DP, _DP],
+    "s4p_icp_refine_symm": [_VP, _PARAMS, _DP, _RESULT],
+}
+COLOR_SIGNATURES = {                                       # include/s4p_icp_color.h
+    "s4p_icp_set_target_intensity" + TWIN: [_VP, _VP, C.c_int64],
+    "s4p_icp_set_source_intensity" + TWIN: [_VP, _VP, C.c_int64],
+    "s4p_icp_estimate_color_gradients": [_VP, C.c_float, C.c_int32],
+    "s4p_icp_target_color_gradients": [_VP, _FP, _FP, _FP],
+    "s4p_icp_color_sums": [_VP, _FP, C.c_double, _DP],
+    "s4p_icp_refine_color": [_VP, _PARAMS, C.c_double, _DP, _RESULT],
+}
+REJECT_SIGNATURES = {                                      # include/s4p_icp_reject.h
+    "s4p_icp_reject_defaults": (None, [C.POINTER(Reject)]),
+    "s4p_icp_set_rejection": [_VP, C.POINTER(Reject)],
+    "s4p_icp_rejection": [_VP, _FP, _IP, _FP, _IP],
+    "s4p_icp_rejection_counts": [_VP, _LP],
+}
+BATCH_SIGNATURES = {                                       # include/s4p_icp_batch.h
+    "s4p_icp_sums_batch": [_VP, C.c_int32, C.c_int32, _FP, _DP],
+    "s4p_icp_refine_batch": [_VP, C.POINTER(BatchParams), C.c_int32, _DP, _RESULT, _IP],
+    "s4p_icp_rank_batch": [_RESULT, C.c_int32, _IP],
+}
+INFO_SIGNATURES = {                                        # include/s4p_icp_info.h
+    "s4p_icp_information_sums": [_VP, _FP, _DP],
+    "s4p_icp_information_from_sums": [_DP, _FP, _DP, _LP, _DP],
+    "s4p_icp_information": [_VP, _DP, _DP, _LP, _DP],
+}
+TABLES = (SIGNATURES, PLANE_SIGNATURES, ROBUST_SIGNATURES, GICP_SIGNATURES, SYMM_SIGNATURES, COLOR_SIGNATURES, REJECT_SIGNATURES,
+          BATCH_SIGNATURES, INFO_SIGNATURES, _PG.SIGNATURES)           # the last: include/s4p_icp_posegraph.h
+(SYMBOLS, PLANE_SYMBOLS, ROBUST_SYMBOLS, GICP_SYMBOLS, SYMM_SYMBOLS, COLOR_SYMBOLS, REJECT_SYMBOLS, BATCH_SYMBOLS, INFO_SYMBOLS,
+ POSEGRAPH_SYMBOLS) = (_B.names(t) for t in TABLES)
+
+_LOADED = {}           # library path -> (the library, the tables declared on it): _binding.load
 
 
-def load_library():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    if not os.path.exists(LIB_PATH):
-        raise ICPError(-7, "libsuper4pcs_icp.so not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(LIB_PATH)
-    fp, dp, ip, vp = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
-    L.s4p_icp_default_params.restype = None
-    L.s4p_icp_default_params.argtypes = [C.POINTER(Params)]
-    L.s4p_icp_create.restype = C.c_int32
-    L.s4p_icp_create.argtypes = [C.c_int32, C.POINTER(vp)]
-    L.s4p_icp_destroy.restype = None
-    L.s4p_icp_destroy.argtypes = [vp]
-    L.s4p_icp_last_error.restype = C.c_char_p
-    L.s4p_icp_last_error.argtypes = [vp]
-    for name in ("s4p_icp_set_target", "s4p_icp_set_target_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float]
-    for name in ("s4p_icp_set_source", "s4p_icp_set_source_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
-    L.s4p_icp_frame.restype = C.c_int32
-    L.s4p_icp_frame.argtypes = [vp, fp]
-    L.s4p_icp_correspondences.restype = C.c_int32
-    L.s4p_icp_correspondences.argtypes = [vp, fp, ip, fp]
-    L.s4p_icp_sums.restype = C.c_int32
-    L.s4p_icp_sums.argtypes = [vp, fp, dp]
-    L.s4p_icp_solve.restype = C.c_int32
-    L.s4p_icp_solve.argtypes = [dp, dp]
-    L.s4p_icp_refine.restype = C.c_int32
-    L.s4p_icp_refine.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
-    L.s4p_icp_apply.restype = C.c_int32
-    L.s4p_icp_apply.argtypes = [vp, dp, fp, fp, fp, C.c_int64]
-    for name in ("s4p_icp_set_target_normals", "s4p_icp_set_target_normals_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
-    L.s4p_icp_estimate_normals.restype = C.c_int32
-    L.s4p_icp_estimate_normals.argtypes = [vp, C.c_float, C.c_int32]
-    L.s4p_icp_target_normals.restype = C.c_int32
-    L.s4p_icp_target_normals.argtypes = [vp, fp, fp, fp]
-    L.s4p_icp_plane_sums.restype = C.c_int32
-    L.s4p_icp_plane_sums.argtypes = [vp, fp, dp]
-    L.s4p_icp_solve_plane.restype = C.c_int32
-    L.s4p_icp_solve_plane.argtypes = [dp, dp]
-    L.s4p_icp_refine_plane.restype = C.c_int32
-    L.s4p_icp_refine_plane.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
-    L.s4p_icp_robust_defaults.restype = None
-    L.s4p_icp_robust_defaults.argtypes = [C.POINTER(Robust), C.c_int32]
-    L.s4p_icp_robust_sums.restype = C.c_int32
-    L.s4p_icp_robust_sums.argtypes = [vp, fp, C.c_int32, C.POINTER(Robust), dp, dp]
-    L.s4p_icp_refine_robust.restype = C.c_int32
-    L.s4p_icp_refine_robust.argtypes = [vp, C.POINTER(Params), C.c_int32, C.POINTER(Robust), dp, C.POINTER(Result), dp]
-    for name in ("s4p_icp_set_source_normals", "s4p_icp_set_source_normals_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
-    L.s4p_icp_source_normals.restype = C.c_int32
-    L.s4p_icp_source_normals.argtypes = [vp, fp, fp, fp]
-    L.s4p_icp_gicp_sums.restype = C.c_int32
-    L.s4p_icp_gicp_sums.argtypes = [vp, fp, C.c_double, dp]
-    L.s4p_icp_refine_gicp.restype = C.c_int32
-    L.s4p_icp_refine_gicp.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
-    L.s4p_icp_symm_sums.restype = C.c_int32
-    L.s4p_icp_symm_sums.argtypes = [vp, fp, dp]
-    L.s4p_icp_solve_symmetric.restype = C.c_int32
-    L.s4p_icp_solve_symmetric.argtypes = [dp, dp]
-    L.s4p_icp_refine_symm.restype = C.c_int32
-    L.s4p_icp_refine_symm.argtypes = [vp, C.POINTER(Params), dp, C.POINTER(Result)]
-    for name in ("s4p_icp_set_target_intensity", "s4p_icp_set_target_intensity_device", "s4p_icp_set_source_intensity",
-                 "s4p_icp_set_source_intensity_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, C.c_int64]
-    L.s4p_icp_estimate_color_gradients.restype = C.c_int32
-    L.s4p_icp_estimate_color_gradients.argtypes = [vp, C.c_float, C.c_int32]
-    L.s4p_icp_target_color_gradients.restype = C.c_int32
-    L.s4p_icp_target_color_gradients.argtypes = [vp, fp, fp, fp]
-    L.s4p_icp_color_sums.restype = C.c_int32
-    L.s4p_icp_color_sums.argtypes = [vp, fp, C.c_double, dp]
-    L.s4p_icp_refine_color.restype = C.c_int32
-    L.s4p_icp_refine_color.argtypes = [vp, C.POINTER(Params), C.c_double, dp, C.POINTER(Result)]
-    L.s4p_icp_reject_defaults.restype = None
-    L.s4p_icp_reject_defaults.argtypes = [C.POINTER(Reject)]
-    L.s4p_icp_set_rejection.restype = C.c_int32
-    L.s4p_icp_set_rejection.argtypes = [vp, C.POINTER(Reject)]
-    L.s4p_icp_rejection.restype = C.c_int32
-    L.s4p_icp_rejection.argtypes = [vp, fp, ip, fp, ip]
-    L.s4p_icp_rejection_counts.restype = C.c_int32
-    L.s4p_icp_rejection_counts.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.s4p_icp_sums_batch.restype = C.c_int32
-    L.s4p_icp_sums_batch.argtypes = [vp, C.c_int32, C.c_int32, fp, dp]
-    L.s4p_icp_refine_batch.restype = C.c_int32
-    L.s4p_icp_refine_batch.argtypes = [vp, C.POINTER(BatchParams), C.c_int32, dp, C.POINTER(Result), ip]
-    L.s4p_icp_rank_batch.restype = C.c_int32
-    L.s4p_icp_rank_batch.argtypes = [C.POINTER(Result), C.c_int32, ip]
-    L.s4p_icp_information_sums.restype = C.c_int32
-    L.s4p_icp_information_sums.argtypes = [vp, fp, dp]
-    L.s4p_icp_information_from_sums.restype = C.c_int32
-    L.s4p_icp_information_from_sums.argtypes = [dp, fp, dp, C.POINTER(C.c_int64), dp]
-    L.s4p_icp_information.restype = C.c_int32
-    L.s4p_icp_information.argtypes = [vp, dp, dp, C.POINTER(C.c_int64), dp]
-    from super4pcs_amd import posegraph
-    posegraph.bind(L)
-    _LIB = L
-    return L
+def load_library(path=None):
+    """The library at path (default LIB_PATH), opened once per process, with every table declared; a library without one of
+    their functions is an error."""
+    return _B.load(_LOADED, path or LIB_PATH, TABLES, ICPError, "libsuper4pcs_icp.so")
 
 
 def _dp(a):
@@ -330,10 +269,6 @@ def compose(A, B):
     return out
 
 
-def _is_torch(t):
-    return type(t).__module__.startswith("torch")
-
-
 def _batch_metric(metric):
     if metric not in METRICS:
         raise ValueError("a batch refines metric \"point\" or \"plane\" (robust losses, \"gicp\", \"symmetric\" and \"color\" have no batch form)")
@@ -375,7 +310,7 @@ def _check_metric(metric, loss):
 def rgb_to_intensity(rgb):
     """float32 (n,): ((double r + double g) + double b) / 765 of an (n, 3) rgb array in 0..255 (numpy, or a torch tensor,
     which stays on its device) -- the formula of the facade (include/super4pcs/algorithms/icp.h)."""
-    if _is_torch(rgb):
+    if _B.is_torch(rgb):
         import torch
         if rgb.dim() != 2 or rgb.shape[1] != 3:
             raise ValueError("rgb is (N, 3)")
@@ -389,9 +324,9 @@ def rgb_to_intensity(rgb):
 
 def _as_intensity(v):
     """One float per point: an (n, 3) input is rgb and goes through rgb_to_intensity, an (n,) or (n, 1) one is taken as it is."""
-    if not _is_torch(v):
+    if not _B.is_torch(v):
         v = np.asarray(v)
-    nd = v.dim() if _is_torch(v) else v.ndim
+    nd = v.dim() if _B.is_torch(v) else v.ndim
     if nd == 2 and v.shape[1] == 3:
         return rgb_to_intensity(v)
     if nd == 2 and v.shape[1] == 1:
@@ -404,8 +339,9 @@ def _as_intensity(v):
 class ICP:
     """One s4p_icp context (one GPU)."""
 
-    def __init__(self, device=0):
-        self.L = load_library()
+    def __init__(self, device=0, lib=None):
+        """lib: the path of another copy or build of the library, bound next to the package's (None)."""
+        self.L = load_library(lib)
         self.device = device
         h = C.c_void_p()
         rc = self.L.s4p_icp_create(device, C.byref(h))
@@ -430,32 +366,18 @@ class ICP:
         if rc != 0:
             raise ICPError(rc, self.L.s4p_icp_last_error(self.h).decode())
 
-    def _cols(self, X):
-        """(entry-point suffix, three column pointers, n, keep-alive) of a numpy array or a CUDA/HIP torch tensor."""
-        if _is_torch(X):
-            import torch
-            if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == 3):
-                raise ValueError("torch input must be a (N, 3) float32 tensor on the GPU")
-            cols = [X[:, k].contiguous() for k in range(3)]
-            torch.cuda.synchronize(X.device)          # the copies run on torch's stream; the library reads on its own
-            return "_device", [c.data_ptr() for c in cols], int(X.shape[0]), cols
-        X = np.asarray(X)
-        if X.ndim != 2 or X.shape[1] != 3:
-            raise ValueError("clouds are (N, 3)")
-        cols = [np.ascontiguousarray(X[:, k], dtype=np.float32) for k in range(3)]
-        return "", [c.ctypes.data for c in cols], int(X.shape[0]), cols
+    def _upload(self, name, X, *tail):
+        """n of the (n, 3) numpy array or GPU torch tensor X after `name`(h, x, y, z, n, *tail), or its _device twin, on X's
+        columns."""
+        dev, ptr, n, keep = _B.cols(X)
+        self._chk(getattr(self.L, name + "_device" if dev else name)(self.h, *ptr, n, *tail))
+        return n
 
     def set_target(self, P, max_distance):
-        suf, ptr, n, keep = self._cols(P)
-        self._chk(getattr(self.L, "s4p_icp_set_target" + suf)(self.h, ptr[0], ptr[1], ptr[2], n, float(max_distance)))
-        self.n_p = n
-        del keep
+        self.n_p = self._upload("s4p_icp_set_target", P, float(max_distance))
 
     def set_source(self, Q):
-        suf, ptr, n, keep = self._cols(Q)
-        self._chk(getattr(self.L, "s4p_icp_set_source" + suf)(self.h, ptr[0], ptr[1], ptr[2], n))
-        self.n_q = n
-        del keep
+        self.n_q = self._upload("s4p_icp_set_source", Q)
 
     def frame(self):
         c = np.empty(3, np.float32)
@@ -482,9 +404,7 @@ class ICP:
 
     def set_target_normals(self, N):
         """One normal per target point (N, 3), in the uploaded order: normalised in double, zero / non-finite -> 0."""
-        suf, ptr, n, keep = self._cols(N)
-        self._chk(getattr(self.L, "s4p_icp_set_target_normals" + suf)(self.h, ptr[0], ptr[1], ptr[2], n))
-        del keep
+        self._upload("s4p_icp_set_target_normals", N)
 
     def estimate_normals(self, radius, min_neighbours=MIN_NEIGHBOURS):
         """Target normals on the device from the neighbours within radius (0 < radius <= max_distance)."""
@@ -501,9 +421,7 @@ class ICP:
     def set_source_normals(self, N):
         """One normal per source point (N, 3), in the uploaded order and the frame of the source as uploaded (the library
         rotates them with T): normalised in double, zero / non-finite -> 0.  set_source invalidates them."""
-        suf, ptr, n, keep = self._cols(N)
-        self._chk(getattr(self.L, "s4p_icp_set_source_normals" + suf)(self.h, ptr[0], ptr[1], ptr[2], n))
-        del keep
+        self._upload("s4p_icp_set_source_normals", N)
 
     def source_normals(self):
         """float32 (n_Q, 3): the stored source normals, in the uploaded order."""
@@ -519,12 +437,12 @@ class ICP:
 
     def _scalars(self, v):
         """(entry-point suffix, pointer, n, keep-alive) of one float per point: numpy, or a torch tensor on the GPU."""
-        if _is_torch(v):
+        if _B.is_torch(v):
             import torch
             if not (v.is_cuda and v.dim() == 1):
                 raise ValueError("torch input must be a (N,) tensor on the GPU")
             c = v.to(torch.float32).contiguous()
-            torch.cuda.synchronize(v.device)
+            _B.sync(v)                                # the copy runs on torch's stream; the library reads on its own
             return "_device", c.data_ptr(), int(c.shape[0]), c
         c = np.ascontiguousarray(v, dtype=np.float32)
         if c.ndim != 1:

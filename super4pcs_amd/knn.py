@@ -17,15 +17,12 @@ import ctypes as C
 
 import numpy as np
 
+from . import _binding as _B
 from . import normals as _N
-from .normals import NormalsError, _cols, _is_torch, _radius
+from ._binding import TWIN
+from .normals import NormalsError, _radius, session
 
 MIN_K, MAX_K = 1, 32
-
-SYMBOLS = [
-    "s4p_knn_search", "s4p_knn_search_device", "s4p_knn_search_at", "s4p_knn_search_at_device",
-    "s4p_outliers_statistical", "s4p_outliers_statistical_device", "s4p_outliers_radius", "s4p_outliers_radius_device",
-]
 
 
 class OutlierStats(C.Structure):
@@ -35,112 +32,65 @@ class OutlierStats(C.Structure):
         return {"n": self.n, "mean": self.mean, "stddev": self.stddev, "threshold": self.threshold, "kept": self.kept}
 
 
-_DECLARED = False
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_knn.h
+    "s4p_knn_search" + TWIN: [_VP, C.c_int32, C.c_float, C.c_int32, _VP, _VP, _VP],
+    "s4p_knn_search_at" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_float, _VP, _VP, _VP],
+    "s4p_outliers_statistical" + TWIN: [_VP, C.c_int32, C.c_double, _VP, _VP, C.POINTER(OutlierStats)],
+    "s4p_outliers_radius" + TWIN: [_VP, C.c_float, C.c_int32, _VP],
+}
+SYMBOLS = _B.names(SIGNATURES)
 
 
-def load_library():
+def load_library(path=None, *tables):
     """The normals library with the s4p_knn.h entry points declared; a library without them is an error."""
-    global _DECLARED
-    L = _N.load_library()
-    if _DECLARED:
-        return L
-    vp = C.c_void_p
-    missing = [s for s in SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    for name in ("s4p_knn_search", "s4p_knn_search_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_int32, C.c_float, C.c_int32, vp, vp, vp]
-    for name in ("s4p_knn_search_at", "s4p_knn_search_at_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp, vp, vp]
-    for name in ("s4p_outliers_statistical", "s4p_outliers_statistical_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_int32, C.c_double, vp, vp, C.POINTER(OutlierStats)]
-    for name in ("s4p_outliers_radius", "s4p_outliers_radius_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_float, C.c_int32, vp]
-    _DECLARED = True
-    return L
+    return _N.load_library(path, SIGNATURES, *tables)
 
 
-def _empty(like, shape, np_dtype):
-    """(array, pointer): a torch tensor on like's device when like is a tensor, else a numpy array."""
-    if like is not None:
-        import torch
-        t = torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=like.device)
-        return t, t.data_ptr()
-    a = np.empty(shape, np_dtype)
-    return a, a.ctypes.data
+def _lists(like, rows, k):
+    """((idx (rows, k) int32, d2 (rows, k) float32, cnt (rows,) int32), their pointers), empty, of like's kind."""
+    idx, pi = _B.empty(like, (rows, max(k, 0)), np.int32)
+    d2, pd = _B.empty(like, (rows, max(k, 0)), np.float32)
+    cnt, pc = _B.empty(like, (rows,), np.int32)
+    return (idx, d2, cnt), (pi, pd, pc)
 
 
 class Knn(_N.Normals):
     """An s4p_normals context (one GPU, one cloud and its grid) with the neighbour queries and the outlier filters; the
     normals methods (estimate, estimate_at, grid) work on it too."""
-
-    def __init__(self, device=0):
-        load_library()
-        super().__init__(device)
-        self._like = None
-
-    def set_cloud(self, X):
-        super().set_cloud(X)
-        self._like = X if _is_torch(X) else None          # device results follow the cloud's kind
-
-    def _sync(self):
-        if self._like is not None:
-            import torch
-            torch.cuda.synchronize(self._like.device)     # torch's allocations before the library writes on its own stream
+    _load = staticmethod(load_library)
 
     def search(self, k, radius=None, exclude_self=False):
         """(idx (n, k) int32, d2 (n, k) float32, cnt (n,) int32) of the cloud's own points."""
-        k = int(k)
-        rows = max(k, 0)
-        idx, pi = _empty(self._like, (self.n, rows), np.int32)
-        d2, pd = _empty(self._like, (self.n, rows), np.float32)
-        cnt, pc = _empty(self._like, (self.n,), np.int32)
-        self._sync()
-        fn = self.L.s4p_knn_search_device if self._like is not None else self.L.s4p_knn_search
-        self._chk(fn(self.h, k, _radius(radius), 1 if exclude_self else 0, pi, pd, pc))
-        return idx, d2, cnt
+        out, ptrs = _lists(self._like, self.n, int(k))
+        self._call("s4p_knn_search", self._like, int(k), _radius(radius), 1 if exclude_self else 0, *ptrs)
+        return out
 
     def search_at(self, Q, k, radius=None):
         """(idx (m, k), d2 (m, k), cnt (m,)) of the query positions Q (numpy in, numpy out; GPU tensor in, GPU tensor out)."""
-        k = int(k)
-        dev, ptr, m, keep = _cols(Q)
+        dev, ptr, m, keep = _B.cols(Q)
         like = Q if dev else None
-        idx, pi = _empty(like, (m, max(k, 0)), np.int32)
-        d2, pd = _empty(like, (m, max(k, 0)), np.float32)
-        cnt, pc = _empty(like, (m,), np.int32)
-        if dev:
-            import torch
-            torch.cuda.synchronize(Q.device)
-        fn = self.L.s4p_knn_search_at_device if dev else self.L.s4p_knn_search_at
-        self._chk(fn(self.h, ptr[0], ptr[1], ptr[2], m, k, _radius(radius), pi, pd, pc))
-        del keep
-        return idx, d2, cnt
+        out, ptrs = _lists(like, m, int(k))
+        self._call("s4p_knn_search_at", like, *ptr, m, int(k), _radius(radius), *ptrs)
+        return out
 
     def statistical_outliers(self, k=16, std_ratio=2.0, want_mean_dist=True):
         """(keep (n,) bool, stats dict, mean_dist (n,) float64 or None): keep_j = (m_j <= mu + std_ratio * sigma)."""
-        keep, pk = _empty(self._like, (self.n,), np.uint8)
-        md, pm = _empty(self._like, (self.n,), np.float64) if want_mean_dist else (None, None)
+        keep, pk = _B.empty(self._like, (self.n,), np.uint8)
+        md, pm = _B.empty(self._like, (self.n,), np.float64) if want_mean_dist else (None, None)
         st = OutlierStats()
-        self._sync()
-        fn = self.L.s4p_outliers_statistical_device if self._like is not None else self.L.s4p_outliers_statistical
-        self._chk(fn(self.h, int(k), float(std_ratio), pm, pk, C.byref(st)))
+        self._call("s4p_outliers_statistical", self._like, int(k), float(std_ratio), pm, pk, C.byref(st))
         return _as_bool(keep), st.as_dict(), md
 
     def radius_outliers(self, radius, min_neighbours):
         """keep (n,) bool: at least min_neighbours other points within radius."""
-        keep, pk = _empty(self._like, (self.n,), np.uint8)
-        self._sync()
-        fn = self.L.s4p_outliers_radius_device if self._like is not None else self.L.s4p_outliers_radius
-        self._chk(fn(self.h, float(radius), int(min_neighbours), pk))
+        keep, pk = _B.empty(self._like, (self.n,), np.uint8)
+        self._call("s4p_outliers_radius", self._like, float(radius), int(min_neighbours), pk)
         return _as_bool(keep)
 
 
 def _as_bool(keep):
-    if _is_torch(keep):
+    if _B.is_torch(keep):
         return keep != 0
     return keep.astype(bool)
 
@@ -151,38 +101,26 @@ def knn(xyz, k, radius=None, queries=None, exclude_self=False, device=0):
     only).  Returns (idx, d2, cnt): rows in ascending (d2, index) order padded with -1 / +inf, and how many were found."""
     if queries is not None and exclude_self:
         raise ValueError("exclude_self applies to the cloud's own points, not to queries")
-    ctx = Knn(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Knn, xyz, device) as ctx:
         if queries is not None:
             return ctx.search_at(queries, k, radius)
         return ctx.search(k, radius, exclude_self)
-    finally:
-        ctx.close()
 
 
 def remove_statistical_outliers(xyz, k=16, std_ratio=2.0, device=0):
     """Statistical outlier removal: a point is kept when the mean distance to its k nearest other points is at most
     mu + std_ratio * sigma of those means over the cloud.  Returns (kept_xyz, keep_mask, stats); kept_xyz = xyz[keep_mask]
     keeps the input order."""
-    xyz = xyz if _is_torch(xyz) else np.asarray(xyz)
-    ctx = Knn(device)
-    try:
-        ctx.set_cloud(xyz)
+    xyz = xyz if _B.is_torch(xyz) else np.asarray(xyz)
+    with session(Knn, xyz, device) as ctx:
         keep, stats, _ = ctx.statistical_outliers(k, std_ratio, want_mean_dist=False)
         return xyz[keep], keep, stats
-    finally:
-        ctx.close()
 
 
 def remove_radius_outliers(xyz, radius, min_neighbours, device=0):
     """Radius outlier removal: a point is kept when at least min_neighbours (1..32) other points lie within radius.
     Returns (kept_xyz, keep_mask)."""
-    xyz = xyz if _is_torch(xyz) else np.asarray(xyz)
-    ctx = Knn(device)
-    try:
-        ctx.set_cloud(xyz)
+    xyz = xyz if _B.is_torch(xyz) else np.asarray(xyz)
+    with session(Knn, xyz, device) as ctx:
         keep = ctx.radius_outliers(radius, min_neighbours)
         return xyz[keep], keep
-    finally:
-        ctx.close()

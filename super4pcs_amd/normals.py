@@ -12,10 +12,14 @@ Clouds are (N, 3) float32 numpy arrays, or (N, 3) float32 torch tensors on the G
 points, device to device, and the result is a torch tensor on the same device).  There is no CPU fallback: without a
 device, Normals() raises NormalsError with code -2.
 """
+import contextlib
 import ctypes as C
 import os
 
 import numpy as np
+
+from . import _binding as _B
+from ._binding import TWIN
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsuper4pcs_normals.so")
@@ -23,18 +27,12 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsuper4pcs_normals.so")
 MIN_K, MAX_K = 3, 32
 ERR_NAMES = {0: "OK", -1: "BAD_ARG", -2: "NO_DEVICE", -3: "HIP", -4: "OOM", -7: "STATE", -8: "INTERNAL"}
 
-SYMBOLS = [
-    "s4p_normals_create", "s4p_normals_destroy", "s4p_normals_last_error", "s4p_normals_set_cloud",
-    "s4p_normals_set_cloud_device", "s4p_normals_estimate", "s4p_normals_estimate_device", "s4p_normals_estimate_at",
-    "s4p_normals_estimate_at_device", "s4p_normals_grid",
-]
-
-# include/s4p_normals_orient.h
-ORIENT_SYMBOLS = ["s4p_orient_consistent", "s4p_orient_consistent_device", "s4p_orient_towards", "s4p_orient_towards_device"]
-ORIENT_OUTWARD, ORIENT_VIEWPOINT = 0, 1
+ORIENT_OUTWARD, ORIENT_VIEWPOINT = 0, 1              # include/s4p_normals_orient.h
 
 
 class NormalsError(RuntimeError):
+    REBUILD = "build.build_normals()"
+
     def __init__(self, code, msg):
         super().__init__("s4p_normals error %s (%d): %s" % (ERR_NAMES.get(code, "?"), code, msg))
         self.code = code
@@ -60,77 +58,47 @@ class OrientStats(C.Structure):
                 "max_jumps": self.max_jumps}
 
 
-_LIB = None
-_ORIENT_DECLARED = False
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_normals.h
+    "s4p_normals_create": [C.c_int32, C.POINTER(_VP)],
+    "s4p_normals_destroy": (None, [_VP]),
+    "s4p_normals_last_error": (C.c_char_p, [_VP]),
+    "s4p_normals_set_cloud" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64],
+    "s4p_normals_estimate" + TWIN: [_VP, C.c_int32, C.c_float, _VP],
+    "s4p_normals_estimate_at" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_float, _VP],
+    "s4p_normals_grid": [_VP, C.POINTER(GridInfo)],
+}
+ORIENT_SIGNATURES = {                                  # include/s4p_normals_orient.h
+    "s4p_orient_consistent" + TWIN: [_VP, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), _VP, _VP, _VP, C.POINTER(OrientStats)],
+    "s4p_orient_towards" + TWIN: [_VP, _VP, C.POINTER(C.c_float), _VP],
+}
+SYMBOLS, ORIENT_SYMBOLS = _B.names(SIGNATURES), _B.names(ORIENT_SIGNATURES)
+
+_LOADED = {}           # library path -> (the library, the tables declared on it): _binding.load
 
 
-def load_library():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    if not os.path.exists(LIB_PATH):
-        raise NormalsError(-7, "libsuper4pcs_normals.so not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-    L = C.CDLL(LIB_PATH)
-    vp = C.c_void_p
-    L.s4p_normals_create.restype = C.c_int32
-    L.s4p_normals_create.argtypes = [C.c_int32, C.POINTER(vp)]
-    L.s4p_normals_destroy.restype = None
-    L.s4p_normals_destroy.argtypes = [vp]
-    L.s4p_normals_last_error.restype = C.c_char_p
-    L.s4p_normals_last_error.argtypes = [vp]
-    for name in ("s4p_normals_set_cloud", "s4p_normals_set_cloud_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64]
-    for name in ("s4p_normals_estimate", "s4p_normals_estimate_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_int32, C.c_float, vp]
-    for name in ("s4p_normals_estimate_at", "s4p_normals_estimate_at_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, vp]
-    L.s4p_normals_grid.restype = C.c_int32
-    L.s4p_normals_grid.argtypes = [vp, C.POINTER(GridInfo)]
-    _LIB = L
-    return L
+def load_library(path=None, *tables):
+    """The library at path (default LIB_PATH), opened once per process, with s4p_normals.h and the tables of the families on top
+    of it declared; a library without one of their functions is an error."""
+    return _B.load(_LOADED, path or LIB_PATH, (SIGNATURES,) + tables, NormalsError, "libsuper4pcs_normals.so")
 
 
-def load_orient():
+def load_orient(path=None):
     """The library with the s4p_normals_orient.h entry points declared; a library without them is an error."""
-    global _ORIENT_DECLARED
-    L = load_library()
-    if _ORIENT_DECLARED:
-        return L
-    missing = [s for s in ORIENT_SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    vp = C.c_void_p
-    for name in ("s4p_orient_consistent", "s4p_orient_consistent_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_int32, C.c_float, C.c_int32, C.POINTER(C.c_float), vp, vp, vp, C.POINTER(OrientStats)]
-    for name in ("s4p_orient_towards", "s4p_orient_towards_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, C.POINTER(C.c_float), vp]
-    _ORIENT_DECLARED = True
-    return L
+    return load_library(path, ORIENT_SIGNATURES)
 
 
-def _is_torch(t):
-    return type(t).__module__.startswith("torch")
-
-
-def _cols(X):
-    """(device?, three column pointers, n, keep-alive) of a numpy array or a GPU torch tensor."""
-    if _is_torch(X):
-        import torch
-        if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == 3):
-            raise ValueError("torch input must be a (N, 3) float32 tensor on the GPU")
-        cols = [X[:, k].contiguous() for k in range(3)]
-        torch.cuda.synchronize(X.device)              # the copies run on torch's stream; the library reads on its own
-        return True, [c.data_ptr() for c in cols], int(X.shape[0]), cols
-    X = np.asarray(X)
-    if X.ndim != 2 or X.shape[1] != 3:
-        raise ValueError("clouds are (N, 3)")
-    cols = [np.ascontiguousarray(X[:, k], dtype=np.float32) for k in range(3)]
-    return False, [c.ctypes.data for c in cols], int(X.shape[0]), cols
+@contextlib.contextmanager
+def session(cls, xyz, device=0):
+    """One context of cls (Normals or a class on it) for one convenience call, closed on every path; with the cloud xyz
+    unless it is None."""
+    ctx = cls(device)
+    try:
+        if xyz is not None:
+            ctx.set_cloud(xyz)
+        yield ctx
+    finally:
+        ctx.close()
 
 
 def _radius(radius):
@@ -139,9 +107,12 @@ def _radius(radius):
 
 class Normals:
     """One s4p_normals context (one GPU) holding one cloud and its grid."""
+    _load = staticmethod(load_library)         # a class on this one names the loader of its own family
 
-    def __init__(self, device=0):
-        self.L = load_library()
+    def __init__(self, device=0, lib=None):
+        """lib: the path of another copy or build of the library, bound next to the package's (None)."""
+        self.lib = lib
+        self.L = self._load(lib)
         self.device = device
         h = C.c_void_p()
         rc = self.L.s4p_normals_create(device, C.byref(h))
@@ -149,6 +120,7 @@ class Normals:
             raise NormalsError(rc, self.L.s4p_normals_last_error(None).decode())
         self.h = h
         self.n = 0
+        self._like = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -165,37 +137,34 @@ class Normals:
         if rc != 0:
             raise NormalsError(rc, self.L.s4p_normals_last_error(self.h).decode())
 
-    def set_cloud(self, X):
-        dev, ptr, n, keep = _cols(X)
-        fn = self.L.s4p_normals_set_cloud_device if dev else self.L.s4p_normals_set_cloud
-        self._chk(fn(self.h, ptr[0], ptr[1], ptr[2], n))
-        self.n = n
-        del keep
+    def _sync(self):
+        _B.sync(self._like)
 
-    def _out(self, like_torch, like, m):
-        if like_torch:
-            import torch
-            t = torch.empty((m, 3), dtype=torch.float32, device=like.device)
-            torch.cuda.synchronize(like.device)
-            return t, t.data_ptr()
-        a = np.empty((m, 3), np.float32)
-        return a, a.ctypes.data
+    def _call(self, name, like, *args, synced=False):
+        """The library's `name`(h, *args), or its _device twin when like is a tensor, after a synchronise of like's device
+        (_binding.sync) unless cols() has just done it (synced); an error code raises."""
+        if not synced:
+            _B.sync(like)
+        self._chk(getattr(self.L, name if like is None else name + "_device")(self.h, *args))
+
+    def set_cloud(self, X):
+        dev, ptr, n, keep = _B.cols(X)
+        like = X if dev else None
+        self._call("s4p_normals_set_cloud", like, *ptr, n, synced=True)
+        self.n, self._like = n, like                      # device results follow the cloud's kind
 
     def estimate(self, k=16, radius=None, device_out=None):
         """(n, 3) float32 normals of the cloud itself; a torch tensor on the cloud's device when device_out is a tensor."""
-        like_torch = device_out is not None
-        out, ptr = self._out(like_torch, device_out, self.n)
-        fn = self.L.s4p_normals_estimate_device if like_torch else self.L.s4p_normals_estimate
-        self._chk(fn(self.h, int(k), _radius(radius), ptr))
+        out, ptr = _B.empty(device_out, (self.n, 3), np.float32)
+        self._call("s4p_normals_estimate", device_out, int(k), _radius(radius), ptr)
         return out
 
     def estimate_at(self, Q, k=16, radius=None):
         """(m, 3) float32 normals at the query positions Q (numpy in, numpy out; GPU tensor in, GPU tensor out)."""
-        dev, ptr, m, keep = _cols(Q)
-        out, optr = self._out(dev, Q, m)
-        fn = self.L.s4p_normals_estimate_at_device if dev else self.L.s4p_normals_estimate_at
-        self._chk(fn(self.h, ptr[0], ptr[1], ptr[2], m, int(k), _radius(radius), optr))
-        del keep
+        dev, ptr, m, keep = _B.cols(Q)
+        like = Q if dev else None
+        out, optr = _B.empty(like, (m, 3), np.float32)
+        self._call("s4p_normals_estimate_at", like, *ptr, m, int(k), _radius(radius), optr)
         return out
 
     def grid(self):
@@ -204,26 +173,18 @@ class Normals:
         return g.as_dict()
 
     def _normals_copy(self, normals):
-        """(torch?, a contiguous float32 (n, 3) copy of normals, its pointer): the library rewrites the copy in place."""
-        if _is_torch(normals):
+        """(like, a contiguous float32 (n, 3) copy of normals, its pointer): the library rewrites the copy in place; like is
+        the copy when it is a tensor, else None."""
+        if _B.is_torch(normals):
             import torch
             if not (normals.is_cuda and normals.dtype == torch.float32 and tuple(normals.shape) == (self.n, 3)):
                 raise ValueError("torch normals must be a (n, 3) float32 tensor on the GPU, n the cloud's size")
             out = normals.contiguous().clone()
-            return True, out, out.data_ptr()
+            return out, out, out.data_ptr()
         out = np.array(normals, dtype=np.float32, order="C", copy=True)
         if out.shape != (self.n, 3):
             raise ValueError("normals are (n, 3), n the cloud's size")
-        return False, out, out.ctypes.data
-
-    @staticmethod
-    def _extra(dev, like, shape, np_dtype):
-        if dev:
-            import torch
-            t = torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=like.device)
-            return t, t.data_ptr()
-        a = np.empty(shape, np_dtype)
-        return a, a.ctypes.data
+        return None, out, out.ctypes.data
 
     def orient(self, normals, k=8, radius=None, viewpoint=None, return_info=False):
         """The normals of the cloud's points with one consistent sign per connected component of the k-nearest-neighbour
@@ -231,36 +192,27 @@ class Normals:
         that faces the viewpoint, or, with viewpoint=None, away from the centre of the cloud's bounds.  Returns a new
         (n, 3) array of the kind it was given; with return_info also a dict with the mask `flipped`, `component` (the
         anchor's index, -1 without a normal) and the counts of s4p_orient_stats."""
-        L = load_orient()
-        dev, out, ptr = self._normals_copy(normals)
-        fl, pf = self._extra(dev, out, (self.n,), np.uint8) if return_info else (None, None)
-        co, pc = self._extra(dev, out, (self.n,), np.int32) if return_info else (None, None)
+        load_orient(self.lib)
+        like, out, ptr = self._normals_copy(normals)
+        fl, pf = _B.empty(like, (self.n,), np.uint8) if return_info else (None, None)
+        co, pc = _B.empty(like, (self.n,), np.int32) if return_info else (None, None)
         vp = None if viewpoint is None else (C.c_float * 3)(*[float(v) for v in viewpoint])
         st = OrientStats()
-        if dev:
-            import torch
-            torch.cuda.synchronize(out.device)
-        fn = L.s4p_orient_consistent_device if dev else L.s4p_orient_consistent
-        self._chk(fn(self.h, int(k), _radius(radius), ORIENT_OUTWARD if viewpoint is None else ORIENT_VIEWPOINT, vp, ptr, pf, pc,
-                     C.byref(st)))
+        self._call("s4p_orient_consistent", like, int(k), _radius(radius), ORIENT_OUTWARD if viewpoint is None else ORIENT_VIEWPOINT,
+                   vp, ptr, pf, pc, C.byref(st))
         if not return_info:
             return out
         info = st.as_dict()
         info["flipped_count"] = info.pop("flipped")
-        info["flipped"] = (fl != 0) if dev else fl.astype(bool)
+        info["flipped"] = (fl != 0) if like is not None else fl.astype(bool)
         info["component"] = co
         return out, info
 
     def orient_towards(self, normals, viewpoint):
         """The normals of the cloud's points, each negated when it faces away from the viewpoint (n . (v - x) < 0)."""
-        L = load_orient()
-        dev, out, ptr = self._normals_copy(normals)
-        vp = (C.c_float * 3)(*[float(v) for v in viewpoint])
-        if dev:
-            import torch
-            torch.cuda.synchronize(out.device)
-        fn = L.s4p_orient_towards_device if dev else L.s4p_orient_towards
-        self._chk(fn(self.h, ptr, vp, None))
+        load_orient(self.lib)
+        like, out, ptr = self._normals_copy(normals)
+        self._call("s4p_orient_towards", like, ptr, (C.c_float * 3)(*[float(v) for v in viewpoint]), None)
         return out
 
 
@@ -275,26 +227,18 @@ def estimate_normals(xyz, k=16, radius=None, queries=None, device=0, orient=None
         raise ValueError("orient applies to the cloud's own normals, not to queries")
     if isinstance(orient, str) and orient != "outward":
         raise ValueError('orient is None, "outward" or a viewpoint (x, y, z)')
-    ctx = Normals(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Normals, xyz, device) as ctx:
         if queries is not None:
             return ctx.estimate_at(queries, k, radius)
-        N = ctx.estimate(k, radius, device_out=xyz if _is_torch(xyz) else None)
+        N = ctx.estimate(k, radius, device_out=ctx._like)
         if orient is None:
             return N
         return ctx.orient(N, orient_k, None, None if isinstance(orient, str) else orient)
-    finally:
-        ctx.close()
 
 
 def orient_normals(xyz, normals, k=8, radius=None, viewpoint=None, device=0):
     """normals of the points xyz with one consistent sign per connected component of the k-nearest-neighbour graph
     (1 <= k <= 32): facing the viewpoint, or outward (away from the centre of the bounds) when viewpoint is None.  Zero
     normals stay zero.  numpy in, numpy out; GPU tensors in, a GPU tensor out.  See Normals.orient."""
-    ctx = Normals(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Normals, xyz, device) as ctx:
         return ctx.orient(normals, k, radius, viewpoint)
-    finally:
-        ctx.close()

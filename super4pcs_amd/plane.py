@@ -18,13 +18,12 @@ import ctypes as C
 
 import numpy as np
 
+from . import _binding as _B
 from . import cluster as _CL
-from .knn import _empty
-from .normals import NormalsError, _is_torch
+from ._binding import TWIN
+from .normals import NormalsError, session
 
 MAX_TRIALS, MAX_REFINE, SUM_BLOCK = 1 << 20, 16, 128
-
-SYMBOLS = ["s4p_plane_segment", "s4p_plane_segment_device"]
 
 
 class PlaneOptions(C.Structure):
@@ -43,33 +42,22 @@ class PlaneResult(C.Structure):
                 "alive": self.alive, "trial": self.trial, "valid_trials": self.valid_trials}
 
 
-_DECLARED = False
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_plane.h
+    "s4p_plane_segment" + TWIN: [_VP, C.POINTER(PlaneOptions), _VP, C.POINTER(PlaneResult), _VP],
+}
+SYMBOLS = _B.names(SIGNATURES)
 
 
-def load_library():
+def load_library(path=None, *tables):
     """The normals library with the s4p_plane.h entry points declared; a library without them is an error."""
-    global _DECLARED
-    L = _CL.load_library()
-    if _DECLARED:
-        return L
-    vp = C.c_void_p
-    missing = [s for s in SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    for name in SYMBOLS:
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.POINTER(PlaneOptions), vp, C.POINTER(PlaneResult), vp]
-    _DECLARED = True
-    return L
+    return _CL.load_library(path, SIGNATURES, *tables)
 
 
 class Plane(_CL.Cluster):
     """An s4p_normals context (one GPU, one cloud) with the plane call; the clustering, neighbour-list and normals methods work
     on it too.  Results follow the cloud's kind: numpy for a numpy cloud, torch tensors on its device for a GPU tensor."""
-
-    def __init__(self, device=0):
-        load_library()
-        super().__init__(device)
+    _load = staticmethod(load_library)
 
     def _exclude(self, exclude):
         """(pointer or None, keep-alive) of an exclude mask of the cloud's kind, any integer or bool type, nonzero = excluded."""
@@ -91,24 +79,17 @@ class Plane(_CL.Cluster):
         inliers, alive, trial and valid_trials).  trial is -1, the plane zero and the mask empty when no candidate was
         valid."""
         pe, keep = self._exclude(exclude)
-        mask, pm = _empty(self._like, (self.n,), np.uint8)
+        mask, pm = _B.empty(self._like, (self.n,), np.uint8)
         opt = PlaneOptions(float(distance), int(trials), int(seed) & 0xFFFFFFFFFFFFFFFF, int(refine))
         res = PlaneResult()
-        self._sync()
-        fn = self.L.s4p_plane_segment_device if self._like is not None else self.L.s4p_plane_segment
-        self._chk(fn(self.h, C.byref(opt), pe, C.byref(res), pm))
-        del keep
+        self._call("s4p_plane_segment", self._like, C.byref(opt), pe, C.byref(res), pm)
         return res.plane(), mask, res.as_dict()
 
 
 def segment_plane(xyz, distance, trials=1024, seed=0, refine=1, exclude=None, device=0):
     """The dominant plane of the cloud: (plane, mask, info) as Plane.segment returns them."""
-    ctx = Plane(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Plane, xyz, device) as ctx:
         return ctx.segment(distance, trials, seed, refine, exclude)
-    finally:
-        ctx.close()
 
 
 def peel_planes(segment, n, max_planes=4, min_inliers=3, like=None):
@@ -118,7 +99,7 @@ def peel_planes(segment, n, max_planes=4, min_inliers=3, like=None):
     a GPU tensor, as the masks then are."""
     if max_planes < 1 or min_inliers < 1:
         raise ValueError("max_planes and min_inliers must be at least 1")
-    labels, _ = _empty(like, (n,), np.int32)
+    labels, _ = _B.empty(like, (n,), np.int32)
     labels[:] = -1
     planes = []
     for p in range(max_planes):
@@ -134,18 +115,14 @@ def segment_planes(xyz, distance, max_planes=4, min_inliers=3, trials=1024, seed
     """Up to max_planes planes peeled off one uploaded cloud, largest remaining first: plane p uses the seed seed + p and
     excludes the inliers of the planes before it; the loop stops at the first plane with fewer than min_inliers inliers.
     Returns (planes (P, 4) float32, labels (n,) int32, -1 = no plane); for a GPU tensor the labels are a tensor on its device."""
-    ctx = Plane(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Plane, xyz, device) as ctx:
         return peel_planes(lambda p, ex: ctx.segment(distance, trials, seed + p, refine, ex), ctx.n, max_planes, min_inliers, ctx._like)
-    finally:
-        ctx.close()
 
 
 def remove_planes(xyz, distance, count=1, min_inliers=3, trials=1024, seed=0, refine=1, device=0):
     """The cloud without its `count` dominant planes (segment_planes with max_planes = count): returns (kept_xyz, keep_mask,
     planes); kept_xyz = xyz[keep_mask] keeps the input order."""
-    xyz = xyz if _is_torch(xyz) else np.asarray(xyz)
+    xyz = xyz if _B.is_torch(xyz) else np.asarray(xyz)
     planes, labels = segment_planes(xyz, distance, count, min_inliers, trials, seed, refine, device)
     keep = labels < 0
     return xyz[keep], keep, planes

@@ -11,8 +11,6 @@ import ctypes as C
 
 import numpy as np
 
-from . import icp as _icp
-
 MAX_NODES = 256                                            # S4P_ICP_POSEGRAPH_MAX_NODES
 MAX_ITERATIONS, CONVERGED, STAGE2_SKIPPED, STALLED = 0, 1, 2, 3       # S4P_ICP_POSEGRAPH_*
 STATUS_NAMES = {MAX_ITERATIONS: "max iterations", CONVERGED: "converged",
@@ -40,15 +38,14 @@ class Result(C.Structure):
                 "cost_end": self.cost_end}
 
 
-def bind(L):
-    """The argument types of the three exports on a loaded library (icp.load_library calls it)."""
-    dp = C.POINTER(C.c_double)
-    L.s4p_icp_posegraph_default_params.restype = None
-    L.s4p_icp_posegraph_default_params.argtypes = [C.POINTER(Params)]
-    L.s4p_icp_posegraph_cost.restype = C.c_double
-    L.s4p_icp_posegraph_cost.argtypes = [C.c_int32, dp, C.c_int32, C.POINTER(Edge), C.c_double, dp]
-    L.s4p_icp_posegraph_optimize.restype = C.c_int32
-    L.s4p_icp_posegraph_optimize.argtypes = [C.c_int32, dp, C.c_int32, C.POINTER(Edge), C.POINTER(Params), dp, C.POINTER(Result)]
+_DP = C.POINTER(C.c_double)
+SIGNATURES = {                                             # include/s4p_icp_posegraph.h; icp.load_library declares it
+    "s4p_icp_posegraph_default_params": (None, [C.POINTER(Params)]),
+    "s4p_icp_posegraph_cost": (C.c_double, [C.c_int32, _DP, C.c_int32, C.POINTER(Edge), C.c_double, _DP]),
+    "s4p_icp_posegraph_optimize": [C.c_int32, _DP, C.c_int32, C.POINTER(Edge), C.POINTER(Params), _DP, C.POINTER(Result)],
+}
+
+from . import icp as _icp  # noqa: E402 -- after the table: icp imports this module for it, whichever of the two comes first
 
 
 class PoseGraph:

@@ -19,66 +19,43 @@ import ctypes as C
 
 import numpy as np
 
+from . import _binding as _B
 from . import plane as _PL
-from .knn import _empty
-from .normals import NormalsError, _cols, _is_torch
+from ._binding import TWIN
+from .normals import NormalsError, session
 
-SYMBOLS = ["s4p_shape_estimate", "s4p_shape_estimate_device", "s4p_shape_estimate_at", "s4p_shape_estimate_at_device"]
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_shape.h
+    "s4p_shape_estimate" + TWIN: [_VP, C.c_float, C.c_int32, _VP, _VP, _VP],
+    "s4p_shape_estimate_at" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, C.c_int32, _VP, _VP, _VP],
+}
+SYMBOLS = _B.names(SIGNATURES)
 
-_DECLARED = False
 
-
-def load_library():
+def load_library(path=None, *tables):
     """The normals library with the s4p_shape.h entry points declared; a library without them is an error."""
-    global _DECLARED
-    L = _PL.load_library()
-    if _DECLARED:
-        return L
-    vp = C.c_void_p
-    missing = [s for s in SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    for name in ("s4p_shape_estimate", "s4p_shape_estimate_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, C.c_float, C.c_int32, vp, vp, vp]
-    for name in ("s4p_shape_estimate_at", "s4p_shape_estimate_at_device"):
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, C.c_int32, vp, vp, vp]
-    _DECLARED = True
-    return L
+    return _PL.load_library(path, SIGNATURES, *tables)
 
 
 class Shape(_PL.Plane):
     """An s4p_normals context (one GPU, one cloud) with the radius-normals call; the plane, clustering, neighbour-list and
     orientation methods work on it too.  estimate here is the radius call: the k-nearest-neighbour estimate of the same
     context is normals.Normals.estimate(ctx, k)."""
-
-    def __init__(self, device=0):
-        load_library()
-        super().__init__(device)
+    _load = staticmethod(load_library)
 
     def estimate(self, radius, min_neighbours=3, queries=None):
         """(normals (rows, 3) float32, eig (rows, 3) float32 l1 >= l2 >= l3, count (rows,) int32) of the cloud's own points,
         or of the query positions when queries is given.  The cloud's rows follow the cloud's kind, the queries' rows the
         queries' kind: numpy in, numpy out; a GPU tensor in, tensors out."""
         if queries is None:
-            like, rows = self._like, self.n
+            name, like, rows, where = "s4p_shape_estimate", self._like, self.n, ()
         else:
-            dev, ptr, rows, keep = _cols(queries)
-            like = queries if dev else None
-        normals, pn = _empty(like, (rows, 3), np.float32)
-        eig, pe = _empty(like, (rows, 3), np.float32)
-        count, pc = _empty(like, (rows,), np.int32)
-        if like is not None:
-            import torch
-            torch.cuda.synchronize(like.device)           # torch's allocations before the library writes on its own stream
-        if queries is None:
-            fn = self.L.s4p_shape_estimate_device if like is not None else self.L.s4p_shape_estimate
-            self._chk(fn(self.h, float(radius), int(min_neighbours), pn, pe, pc))
-        else:
-            fn = self.L.s4p_shape_estimate_at_device if like is not None else self.L.s4p_shape_estimate_at
-            self._chk(fn(self.h, ptr[0], ptr[1], ptr[2], rows, float(radius), int(min_neighbours), pn, pe, pc))
-            del keep
+            dev, ptr, rows, keep = _B.cols(queries)
+            name, like, where = "s4p_shape_estimate_at", queries if dev else None, (*ptr, rows)
+        normals, pn = _B.empty(like, (rows, 3), np.float32)
+        eig, pe = _B.empty(like, (rows, 3), np.float32)
+        count, pc = _B.empty(like, (rows,), np.int32)
+        self._call(name, like, *where, float(radius), int(min_neighbours), pn, pe, pc)
         return normals, eig, count
 
 
@@ -92,21 +69,17 @@ def estimate_normals_radius(xyz, radius, min_neighbours=3, queries=None, orient=
         raise ValueError("orient applies to the cloud's own normals, not to queries")
     if isinstance(orient, str) and orient != "outward":
         raise ValueError('orient is None, "outward" or a viewpoint (x, y, z)')
-    ctx = Shape(device)
-    try:
-        ctx.set_cloud(xyz)
+    with session(Shape, xyz, device) as ctx:
         N, eig, count = ctx.estimate(radius, min_neighbours, queries)
         if orient is not None:
             N = ctx.orient(N, orient_k, None, None if isinstance(orient, str) else orient)
         return N, eig, count
-    finally:
-        ctx.close()
 
 
 def surface_variation(eig):
     """l3 / (l1 + l2 + l3) of every row of eig (rows, 3), 0 where the sum is not > 0: 0 on a plane, up to 1 / 3 where the
     neighbourhood has no direction.  float32; numpy in, numpy out; a tensor in, a tensor out."""
-    if _is_torch(eig):
+    if _B.is_torch(eig):
         import torch
         total = (eig[:, 0] + eig[:, 1]) + eig[:, 2]
         ok = total > 0

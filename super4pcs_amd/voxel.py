@@ -15,40 +15,23 @@ import ctypes as C
 
 import numpy as np
 
+from . import _binding as _B
 from . import normals as _N
-from .normals import NormalsError, _cols, _is_torch
+from ._binding import TWIN
+from .normals import NormalsError, session
 
 MAX_ATTR = 8
 
-SYMBOLS = ["s4p_voxel_downsample", "s4p_voxel_downsample_device"]
+_VP = C.c_void_p
+SIGNATURES = {                                         # include/s4p_voxel.h
+    "s4p_voxel_downsample" + TWIN: [_VP, _VP, _VP, _VP, C.c_int64, C.c_float, _VP, C.c_int32, _VP, _VP, _VP, _VP, C.POINTER(C.c_int64)],
+}
+SYMBOLS = _B.names(SIGNATURES)
 
-_DECLARED = False
 
-
-def load_library():
+def load_library(path=None):
     """The normals library with the s4p_voxel.h entry points declared; a library without them is an error."""
-    global _DECLARED
-    L = _N.load_library()
-    if _DECLARED:
-        return L
-    vp = C.c_void_p
-    missing = [s for s in SYMBOLS if not hasattr(L, s)]
-    if missing:
-        raise NormalsError(-7, "libsuper4pcs_normals.so lacks %s: rebuild it (build.build_normals())" % ", ".join(missing))
-    for name in SYMBOLS:
-        getattr(L, name).restype = C.c_int32
-        getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(C.c_int64)]
-    _DECLARED = True
-    return L
-
-
-def _empty(like, shape, np_dtype):
-    if like is not None:
-        import torch
-        t = torch.empty(shape, dtype=getattr(torch, np.dtype(np_dtype).name), device=like.device)
-        return t, t.data_ptr()
-    a = np.empty(shape, np_dtype)
-    return a, a.ctypes.data
+    return _N.load_library(path, SIGNATURES)
 
 
 def _attr_block(attrs, n, dev, like):
@@ -57,11 +40,11 @@ def _attr_block(attrs, n, dev, like):
         return None, 0
     if dev:
         import torch
-        if not (_is_torch(attrs) and attrs.is_cuda and attrs.device == like.device and attrs.dtype == torch.float32):
+        if not (_B.is_torch(attrs) and attrs.is_cuda and attrs.device == like.device and attrs.dtype == torch.float32):
             raise ValueError("with a GPU cloud, attributes are float32 tensors on the same device")
         a = attrs.reshape(attrs.shape[0], -1).contiguous()
     else:
-        if _is_torch(attrs):
+        if _B.is_torch(attrs):
             raise ValueError("with a numpy cloud, attributes are numpy arrays")
         a = np.asarray(attrs)
         a = np.ascontiguousarray(a.reshape(a.shape[0], -1), dtype=np.float32)
@@ -75,28 +58,20 @@ def _attr_block(attrs, n, dev, like):
 class VoxelGrid(_N.Normals):
     """An s4p_normals context (one GPU) with the voxel-grid downsample.  The cloud is passed per call; a cloud given to
     set_cloud, and what estimate returns on it, stay as they are."""
-
-    def __init__(self, device=0):
-        load_library()
-        super().__init__(device)
+    _load = staticmethod(load_library)
 
     def downsample(self, xyz, voxel_size, attrs=None):
         """(xyz_m (m, 3) float32, attrs_m (m, nattr) float32 or None, counts (m,) int32, voxel_of (n,) int32)."""
-        dev, ptr, n, keep = _cols(xyz)
+        dev, ptr, n, keep = _B.cols(xyz)
         like = xyz if dev else None
         a, nattr = _attr_block(attrs, n, dev, like)
-        out_xyz, pxyz = _empty(like, (n, 3), np.float32)
-        out_attr, pattr = _empty(like, (n, nattr), np.float32) if nattr else (None, None)
-        counts, pcnt = _empty(like, (n,), np.int32)
-        vof, pvof = _empty(like, (n,), np.int32)
+        out_xyz, pxyz = _B.empty(like, (n, 3), np.float32)
+        out_attr, pattr = _B.empty(like, (n, nattr), np.float32) if nattr else (None, None)
+        counts, pcnt = _B.empty(like, (n,), np.int32)
+        vof, pvof = _B.empty(like, (n,), np.int32)
         pa = None if a is None else (a.data_ptr() if dev else a.ctypes.data)
-        if dev:
-            import torch
-            torch.cuda.synchronize(xyz.device)        # torch's allocations and copies before the library's own stream
         m = C.c_int64(0)
-        fn = self.L.s4p_voxel_downsample_device if dev else self.L.s4p_voxel_downsample
-        self._chk(fn(self.h, ptr[0], ptr[1], ptr[2], n, float(voxel_size), pa, nattr, pxyz, pattr, pcnt, pvof, C.byref(m)))
-        del keep, a
+        self._call("s4p_voxel_downsample", like, *ptr, n, float(voxel_size), pa, nattr, pxyz, pattr, pcnt, pvof, C.byref(m))
         m = int(m.value)
         return out_xyz[:m], (None if out_attr is None else out_attr[:m]), counts[:m], vof
 
@@ -104,7 +79,7 @@ class VoxelGrid(_N.Normals):
 def renormalise(mean_normals):
     """Unit normals from averaged ones: n / sqrt((x*x + y*y) + z*z) in double, rounded to float; a mean of norm 0, or a
     non-finite one, gives (0, 0, 0), "no normal".  Done on the host for both kinds of input, so that they agree in bits."""
-    if _is_torch(mean_normals):
+    if _B.is_torch(mean_normals):
         import torch
         return torch.from_numpy(renormalise(mean_normals.cpu().numpy())).to(mean_normals.device)
     d = np.asarray(mean_normals, np.float32).astype(np.float64)
@@ -121,7 +96,7 @@ def voxel_downsample(xyz, voxel_size, attrs=None, normals=None, device=0):
     ((n,) or (n, c)) are averaged per voxel as they are.  normals ride as three extra channels and are renormalised
     afterwards (renormalise); at most 8 channels in all.  numpy in gives numpy out, a GPU torch tensor in gives tensors on
     its device, with the same bits."""
-    is_t = _is_torch(xyz)
+    is_t = _B.is_torch(xyz)
     block, na = attrs, 0
     if attrs is not None:
         block = attrs.reshape(attrs.shape[0], -1) if is_t else np.asarray(attrs, np.float32).reshape(len(attrs), -1)
@@ -134,11 +109,8 @@ def voxel_downsample(xyz, voxel_size, attrs=None, normals=None, device=0):
         else:
             nrm = np.asarray(normals, np.float32).reshape(-1, 3)
             block = nrm if block is None else np.concatenate([block, nrm], axis=1)
-    ctx = VoxelGrid(device)
-    try:
+    with session(VoxelGrid, None, device) as ctx:
         xyz_m, block_m, counts, vof = ctx.downsample(xyz, voxel_size, block)
-    finally:
-        ctx.close()
     attrs_m = normals_m = None
     if attrs is not None:
         attrs_m = block_m[:, :na]

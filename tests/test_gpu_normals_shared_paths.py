@@ -166,7 +166,7 @@ def test_calls_without_their_optional_outputs_equal_the_full_calls(clu, form):
     voxel_of): the call without them returns, in what remains, the bits of the call with them.  Where the binding always
     passes the output (search, search_at, voxel_downsample), the C entry point is called as the binding calls it, with a null."""
     import ctypes as C
-    from super4pcs_amd import knn, normals, voxel
+    from super4pcs_amd import _binding as B, voxel
     if form == "torch":
         import torch
         wrap, dev = S.to_device, True
@@ -180,21 +180,18 @@ def test_calls_without_their_optional_outputs_equal_the_full_calls(clu, form):
     like = Xw if dev else None
     ctx = clu.Cluster(0)
     ctx.set_cloud(Xw)
-    L = ctx.L
 
     idx, d2, _ = ctx.search(8, 0.1)
-    gi, pi = knn._empty(like, (1000, 8), np.int32)
-    gd, pd = knn._empty(like, (1000, 8), np.float32)
-    ctx._sync()
-    ctx._chk((L.s4p_knn_search_device if dev else L.s4p_knn_search)(ctx.h, 8, 0.1, 0, pi, pd, None))
+    gi, pi = B.empty(like, (1000, 8), np.int32)
+    gd, pd = B.empty(like, (1000, 8), np.float32)
+    ctx._call("s4p_knn_search", like, 8, 0.1, 0, pi, pd, None)
     assert _flat([gi, gd]) == _flat([idx, d2])
 
     idx, d2, _ = ctx.search_at(Qw, 8, 0.1)
-    _, ptr, m, keep = normals._cols(Qw)
-    gi, pi = knn._empty(like, (m, 8), np.int32)
-    gd, pd = knn._empty(like, (m, 8), np.float32)
-    ctx._sync()
-    ctx._chk((L.s4p_knn_search_at_device if dev else L.s4p_knn_search_at)(ctx.h, ptr[0], ptr[1], ptr[2], m, 8, 0.1, pi, pd, None))
+    _, ptr, m, keep = B.cols(Qw)
+    gi, pi = B.empty(like, (m, 8), np.int32)
+    gd, pd = B.empty(like, (m, 8), np.float32)
+    ctx._call("s4p_knn_search_at", like, ptr[0], ptr[1], ptr[2], m, 8, 0.1, pi, pd, None)
     assert _flat([gi, gd]) == _flat([idx, d2])
 
     full = ctx.statistical_outliers(8, 1.5)
@@ -206,12 +203,10 @@ def test_calls_without_their_optional_outputs_equal_the_full_calls(clu, form):
         assert _flat(ctx.orient(Nw, 8, None, viewpoint)) == _flat(out), viewpoint
 
     xyz, _, _, _ = voxel.VoxelGrid.downsample(ctx, Vw, 0.7)
-    _, ptr, n, keep = normals._cols(Vw)
-    gx, px = knn._empty(Vw if dev else None, (n, 3), np.float32)
-    ctx._sync()
+    _, ptr, n, keep = B.cols(Vw)
+    gx, px = B.empty(like, (n, 3), np.float32)
     m = C.c_int64(0)
-    fn = L.s4p_voxel_downsample_device if dev else L.s4p_voxel_downsample
-    ctx._chk(fn(ctx.h, ptr[0], ptr[1], ptr[2], n, 0.7, None, 0, px, None, None, None, C.byref(m)))
+    ctx._call("s4p_voxel_downsample", like, ptr[0], ptr[1], ptr[2], n, 0.7, None, 0, px, None, None, None, C.byref(m))
     assert int(m.value) == len(xyz) and _flat(gx[:len(xyz)]) == _flat(xyz)
     del keep
     ctx.close()

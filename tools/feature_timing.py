@@ -25,15 +25,12 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from super4pcs_amd import build as B, datasets as D, normals  # noqa: E402
+from super4pcs_amd import build as B, datasets as D, features  # noqa: E402
 
-LIB = None
+LIB = None                                      # --lib: the path every context of this run binds (Features(0, lib=LIB))
 if "--lib" in sys.argv:
     LIB = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
     del sys.argv[sys.argv.index("--lib"):sys.argv.index("--lib") + 2]
-    normals.LIB_PATH = LIB                      # before the first load_library
-
-from super4pcs_amd import features  # noqa: E402
 
 REPS = 10
 OUT = os.path.join(ROOT, "profiles", "feature_timing.json")
@@ -74,7 +71,7 @@ def _cpu():
 
 def time_fpfh(with_cpu):
     X, N = cloud()
-    ctx = features.Features(0)
+    ctx = features.Features(0, lib=LIB)
     ctx.set_cloud(torch.from_numpy(X).cuda())
     Nt = torch.from_numpy(N).cuda()
     rows = []
@@ -97,7 +94,7 @@ def time_fpfh(with_cpu):
 
 
 def time_match(with_cpu):
-    ctx = features.Features(0)
+    ctx = features.Features(0, lib=LIB)
     rows = []
     for m in MATCH_SIZES:
         fa, fb = tables(m)
@@ -141,7 +138,7 @@ def run(out_path, with_cpu):
 
 def quick():
     X, N = cloud()
-    ctx = features.Features(0)
+    ctx = features.Features(0, lib=LIB)
     ctx.set_cloud(torch.from_numpy(X).cuda())
     Nt = torch.from_numpy(N).cuda()
     fa, fb = tables(MATCH_SIZES[0])

@@ -49,22 +49,12 @@ class LibCtx:
     normals, and refine(metric, iterations) for plane / gicp / symmetric (the last only where the build exports it)."""
 
     def __init__(self, lib_path, P, Q, Nq, d):
-        from super4pcs_amd import icp
+        from super4pcs_amd import _binding, icp
         self.icp = icp
         L = self.L = C.CDLL(lib_path)
-        vp, dp = C.c_void_p, C.POINTER(C.c_double)
-        L.s4p_icp_create.argtypes = [C.c_int32, C.POINTER(vp)]
-        L.s4p_icp_destroy.argtypes = [vp]; L.s4p_icp_destroy.restype = None
-        L.s4p_icp_set_target.argtypes = [vp, vp, vp, vp, C.c_int64, C.c_float]
-        L.s4p_icp_set_source.argtypes = [vp, vp, vp, vp, C.c_int64]
-        L.s4p_icp_set_source_normals.argtypes = [vp, vp, vp, vp, C.c_int64]
-        L.s4p_icp_estimate_normals.argtypes = [vp, C.c_float, C.c_int32]
-        L.s4p_icp_default_params.argtypes = [C.POINTER(icp.Params)]; L.s4p_icp_default_params.restype = None
-        L.s4p_icp_refine_plane.argtypes = [vp, C.POINTER(icp.Params), dp, C.POINTER(icp.Result)]
-        L.s4p_icp_refine_gicp.argtypes = [vp, C.POINTER(icp.Params), C.c_double, dp, C.POINTER(icp.Result)]
-        if hasattr(L, "s4p_icp_refine_symm"):
-            L.s4p_icp_refine_symm.argtypes = [vp, C.POINTER(icp.Params), dp, C.POINTER(icp.Result)]
-        self.h = vp()
+        for table in icp.TABLES:
+            _binding.declare(L, table)                 # without an error class: a parent build may lack s4p_icp_refine_symm
+        self.h = C.c_void_p()
         assert L.s4p_icp_create(0, C.byref(self.h)) == 0
         cols = lambda X: [np.ascontiguousarray(X[:, k], np.float32) for k in range(3)]
         pc, qc, nc = cols(P), cols(Q), cols(Nq)

@@ -16,7 +16,6 @@ sum of the counts the call returns.
     python tools/shape_timing.py --stats DIR/.../*_kernel_stats.csv [out.json]          (merges the kernel rows)
 No target is fixed: the parent of this feature has no such call."""
 import csv
-import ctypes as C
 import glob
 import hashlib
 import json
@@ -97,42 +96,7 @@ def distance_tests(X, radius, rings):
     return total
 
 
-# ---- other builds of the library, through the C ABI -------------------------------------------------------------------------------
-
-class RawLib:
-    def __init__(self, path):
-        self.path = path
-        L = self.L = C.CDLL(path)
-        vp = C.c_void_p
-        L.s4p_normals_create.restype = C.c_int32; L.s4p_normals_create.argtypes = [C.c_int32, C.POINTER(vp)]
-        L.s4p_normals_destroy.restype = None; L.s4p_normals_destroy.argtypes = [vp]
-        L.s4p_normals_last_error.restype = C.c_char_p; L.s4p_normals_last_error.argtypes = [vp]
-        L.s4p_normals_set_cloud_device.restype = C.c_int32; L.s4p_normals_set_cloud_device.argtypes = [vp, vp, vp, vp, C.c_int64]
-        L.s4p_shape_estimate_device.restype = C.c_int32; L.s4p_shape_estimate_device.argtypes = [vp, C.c_float, C.c_int32, vp, vp, vp]
-        self.h = vp()
-        self._chk(L.s4p_normals_create(0, C.byref(self.h)))
-
-    def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError("%s: %d %s" % (self.path, rc, self.L.s4p_normals_last_error(self.h)))
-
-    def set_cloud(self, Xt):
-        cols = [Xt[:, k].contiguous() for k in range(3)]
-        torch.cuda.synchronize()
-        self._chk(self.L.s4p_normals_set_cloud_device(self.h, cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(), Xt.shape[0]))
-        self.n = Xt.shape[0]
-        self.out = (torch.empty((self.n, 3), dtype=torch.float32, device="cuda"), torch.empty((self.n, 3), dtype=torch.float32, device="cuda"),
-                    torch.empty((self.n,), dtype=torch.int32, device="cuda"))
-        torch.cuda.synchronize()
-
-    def estimate(self, radius, min_neighbours=3):
-        N, E, cnt = self.out
-        self._chk(self.L.s4p_shape_estimate_device(self.h, radius, min_neighbours, N.data_ptr(), E.data_ptr(), cnt.data_ptr()))
-        return self.out
-
-    def close(self):
-        self.L.s4p_normals_destroy(self.h)
-
+# ---- other builds of the library: shape.Shape(0, lib=path), next to the package's in one process ----------------------------------
 
 def _equal(a, b):
     return bool(torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32)) and
@@ -149,7 +113,7 @@ def time_variants(label, Xt, radii, libs):
         times = {name: [] for name in libs}
         same = {}
         for name, lib in libs.items():                     # warm-up, and the bits
-            got = tuple(t.clone() for t in lib.estimate(r))
+            got = lib.estimate(r)
             ref = got if ref is None else ref
             same[name] = _equal(got, ref)
         for _ in range(REPS):
@@ -216,9 +180,9 @@ def run(out_path, with_cpu, variants_dir):
            "rows": [], "variants": []}
     libs = {}
     if variants_dir:
-        libs["package"] = RawLib(normals.LIB_PATH)
+        libs["package"] = shape.Shape(0)
         for path in sorted(glob.glob(os.path.join(variants_dir, "libshape_*.so"))):
-            libs[os.path.basename(path)[len("libshape_"):-3]] = RawLib(path)
+            libs[os.path.basename(path)[len("libshape_"):-3]] = shape.Shape(0, lib=path)
     for label, X, start in clouds():
         row, Xt = time_cloud(label, X, start, with_cpu)
         res["rows"].append(row)
